@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the hot path: eight-coefficient parameter-points per second (BASELINE.json's metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 A step = one pass of the hot path, N x (full_calculation + compute_all_dimensionless) with ALL EIGHT coefficients per
 point (lib.rs:178-191), over one batch of `--points` synthetic power-law points per GPU (the generator of
@@ -56,8 +56,30 @@ FP64_VECTOR_PEAK_TFLOPS = 78.6      # MI355X public spec, 256 CUs x 128 flop/clk
 # HBM bytes and executed fp64 instructions per sample / per pass, quoted only for the build they were taken on
 PMC_PROFILES = {"group_kernel": "profiles/r4_pmc_group_powerlaw8.json", "Heyvaerts": "profiles/r4_pmc_faraday_powerlaw8.json"}
 TABLE = 1_000_000
+DUMP_BYTES = 60 << 20       # --dump-outputs: at most this much in both files (under 64 MB with the headers)
 REFERENCE_HINT = ("the reference's only timing statement: benches/powerlaw.rs:6-8, 'about 40 minutes' for 16 single-coefficient "
                   "benchmarks x >= 300 iterations on its author's machine, i.e. about 0.5 s per coefficient on one core")
+
+
+def dump_outputs(path, table):
+    """The [rows, 8] float64 table that compute() returned in the last timed step (rank 0: the gathered table of all
+    ranks), as two finite arrays:
+      DIR/out.npy            float64, the table with 0 in place of every non-finite entry
+      DIR/out_nonfinite.npy  float32, per entry 0 = finite, 1 = NaN (a failed quadrature: the reference's NaN),
+                             2 = +inf, 3 = -inf
+    Beyond DUMP_BYTES the rows are a fixed, seeded sample, in table order (the same rows in both files)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    table = np.asarray(table, dtype=np.float64)
+    rows = DUMP_BYTES // (table.shape[1] * (8 + 4))
+    if table.shape[0] > rows:
+        table = table[np.sort(np.random.default_rng(0).choice(table.shape[0], rows, replace=False))]
+    code = np.zeros(table.shape, dtype=np.float32)
+    code[np.isnan(table)] = 1
+    code[np.isposinf(table)] = 2
+    code[np.isneginf(table)] = 3
+    np.save(os.path.join(path, "out.npy"), np.where(np.isfinite(table), table, 0.))
+    np.save(os.path.join(path, "out_nonfinite.npy"), code)
 
 
 def main():
@@ -71,7 +93,13 @@ def main():
                     help="rows of the all-cores eight-coefficient CPU baseline (the other three are scaled from it; 0 = skip)")
     ap.add_argument("--side-rows", type=int, default=65536, help="rows per GPU per step of the side legs (0 = skip them)")
     ap.add_argument("--no-parity", action="store_true", help="skip the comparison with the literal-oracle vectors")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the table of the last timed step to DIR/out.npy (float64 [rows, 8], non-finite entries "
+                         "0) and DIR/out_nonfinite.npy (0 finite, 1 NaN, 2 +inf, 3 -inf); a fixed, seeded sample of the "
+                         "rows beyond %d MiB" % (DUMP_BYTES >> 20))
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     from rimphony_amd import launch
     if args.gpus > 1 and not launch.launched_by_launcher():
@@ -137,9 +165,11 @@ def main():
 
     def timed_leg(config, rows, steps, warmup, start0, wrap, mask_override=None):
         """`warmup` untimed + `steps` timed steps of `rows` rows per GPU; timed region bracketed by barrier + synchronize on
-        both sides, max over ranks.  Returns the whole-job time, per-kernel HIP-event times and device work counters."""
+        both sides, max over ranks.  Returns the whole-job time, per-kernel HIP-event times, device work counters and
+        the table of the last step (the gathered [rows * world, 8] table on rank 0, None on the other ranks)."""
         shards = [stage(config, rows, start0 + (st * rows * world) % wrap) for st in range(warmup + steps)]
         sym_ms, far_ms, sym_samples, sym_passes, far_samples, far_passes = [], [], [], [], [], []
+        last = [None]
 
         def run(i, record):
             kind, mask, d = shards[i]
@@ -148,7 +178,9 @@ def main():
             out, _ = ctx.compute_batch_device(kind, d[0], d[1], d[2], mask)
             if distributed:
                 # RCCL gather of the output table (host tensors in the gloo rehearsal)
-                sharding.gather_table(out.cpu() if rehearse else out, rows * world, rank, world, dst=0, force=force_dist)
+                out = sharding.gather_table(out.cpu() if rehearse else out, rows * world, rank, world, dst=0, force=force_dist)
+            if i == warmup + steps - 1:
+                last[0] = out
             if record:
                 if mask & 0x3F:
                     sym_ms.append(ctx.last_symphony_ms())          # HIP events on the launch stream
@@ -169,7 +201,7 @@ def main():
         barrier()
         dt = max_over_ranks(time.perf_counter() - t0)
         return {"dt": dt, "sym_ms": sym_ms, "far_ms": far_ms, "sym_samples": sym_samples, "sym_passes": sym_passes,
-                "far_samples": far_samples, "far_passes": far_passes}
+                "far_samples": far_samples, "far_passes": far_passes, "last_out": last[0]}
 
     def pmc_record(kernel):
         """The committed PMC record of `kernel`'s family, or (None, why): only a profile of THIS build is quoted."""
@@ -260,6 +292,8 @@ def main():
     roof_far = roofline("coop_kernel<HeyvaertsProblem<%d>>" % kind, FARADAY_FLOPS.get(base_cfg, 498.0), primary["far_ms"],
                         primary["far_samples"], primary["far_passes"], with_traffic=True, kind=kind) if primary["far_ms"] else None
     tail = ctx.last_tail()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, primary["last_out"].cpu().numpy())
 
 
     # ---------------------------------------------------------------- side legs

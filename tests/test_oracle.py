@@ -209,15 +209,14 @@ def test_qag_against_known_integrals(oracle):
 def test_coefficient_tables_match_the_reference_sources(tmp_path):
     """tools/check_literals.py: every polynomial of bessel.c and the Heyvaerts elements, parsed from the reference
     sources as text, equals -- coefficient by coefficient, sign and position included -- what dev_bessel.h /
-    dev_heyvaerts.h / the oracle evaluate.  Only where the reference is mounted (build container); a mutated copy of
-    dev_bessel.h (one sign flipped in a Meissel row, one Debye coefficient altered) must be caught."""
+    dev_heyvaerts.h / the oracle evaluate.  The reference side is the one stored from its sources
+    (tests/golden/check_literals.json, tools/ref_golden.py); a mutated copy of dev_bessel.h (one sign flipped in a
+    Meissel row, one Debye coefficient altered) must be caught."""
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    if not os.path.isdir("/root/reference"):
-        pytest.skip("reference sources not mounted")
     tool = os.path.join(root, "tools", "check_literals.py")
-    r = subprocess.run([sys.executable, tool], capture_output=True, text=True, timeout=900)
+    r = subprocess.run([sys.executable, tool, "--golden"], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     assert "all tables identical" in r.stdout
     src = open(os.path.join(root, "rimphony_amd", "csrc", "dev_bessel.h")).read()
@@ -227,7 +226,7 @@ def test_coefficient_tables_match_the_reference_sources(tmp_path):
         bad = tmp_path / "dev_bessel_mutated.h"
         bad.write_text(src.replace(old, new, 1))
         env = dict(os.environ, RIMPHONY_CHECK_DEV_BESSEL=str(bad))
-        r = subprocess.run([sys.executable, tool], capture_output=True, text=True, timeout=900, env=env)
+        r = subprocess.run([sys.executable, tool, "--golden"], capture_output=True, text=True, timeout=900, env=env)
         assert r.returncode == 1 and "DIFFERENT" in r.stdout, r.stdout[-1500:]
 
 
@@ -236,15 +235,13 @@ def test_formulas_match_the_reference_sources(tmp_path):
     with both branches of gamma sin(xi), the gamma limits, the prefactors, calc_f / calc_f_derivatives of the four
     distributions, fill_coord_vars, dfdsigma, the limits of the Heyvaerts inner integrals, the final scalings and the
     cgs layer -- is algebraically identical (sympy) in dev_symphony.h / symphony_wave.h / dev_heyvaerts.h /
-    heyvaerts_wave.h and in the oracle.  Only where the reference is mounted; one flipped sign in each of three files
-    must be caught."""
+    heyvaerts_wave.h and in the oracle.  The reference side is the one stored from its sources
+    (tests/golden/check_formulas.json, tools/ref_golden.py); one flipped sign in each of three files must be caught."""
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    if not os.path.isdir("/root/reference"):
-        pytest.skip("reference sources not mounted")
     tool = os.path.join(root, "tools", "check_formulas.py")
-    r = subprocess.run([sys.executable, tool], capture_output=True, text=True, timeout=900)
+    r = subprocess.run([sys.executable, tool, "--golden"], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
     assert ", 0 DIFFERENT" in r.stdout and r.stdout.count("identical") >= 120
     mutations = (
@@ -260,5 +257,5 @@ def test_formulas_match_the_reference_sources(tmp_path):
         assert src.count(old) >= 1, old
         bad = tmp_path / ("mutated_" + os.path.basename(path))
         bad.write_text(src.replace(old, new, 1))
-        r = subprocess.run([sys.executable, tool], capture_output=True, text=True, timeout=900, env=dict(os.environ, **{var: str(bad)}))
+        r = subprocess.run([sys.executable, tool, "--golden"], capture_output=True, text=True, timeout=900, env=dict(os.environ, **{var: str(bad)}))
         assert r.returncode == 1 and "DIFFERENT" in r.stdout, (var, r.stdout[-1500:])

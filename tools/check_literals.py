@@ -18,15 +18,23 @@ as DATA: no header stand-ins, nothing compiled):
   (Rust method syntax rewritten to infix by regular expressions), the constants of heyvaerts.rs:28-33, the region
   intercepts and slope of bessel.c:313-316, and the At[m] table (bessel.c:171-174) against mpmath.
 
-Exit status 0 = everything identical.  usage: python tools/check_literals.py [/root/reference]"""
+Where the reference is not mounted (or with --golden), the reference side is the one stored in
+tests/golden/check_literals.json by `--record` (tools/ref_golden.py): the project's side is compared with its values.
+
+Exit status 0 = everything identical.  usage: python tools/check_literals.py [--golden | --record] [/root/reference]"""
 import os
 import re
 import sys
 
 import sympy as sp
 
+import ref_golden
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = sys.argv[1] if len(sys.argv) > 1 else "/root/reference"
+_ARGS = [a for a in sys.argv[1:] if not a.startswith("--")]
+REF = _ARGS[0] if _ARGS else "/root/reference"
+G = ref_golden.Reference(REF, os.path.join(ROOT, "tests", "golden", "check_literals.json"), sys.argv[1:])
+Z = sp.S.Zero           # stands in for a reference quantity that is not derived here (the stored side is compared)
 NUM = re.compile(r"(?<![\w.])(\d+\.?\d*(?:[eE][-+]?\d+)?|\.\d+(?:[eE][-+]?\d+)?)(?![\w.(])")
 failures = []
 
@@ -86,35 +94,39 @@ def between(text, start, stop):
 
 
 def same(name, ours, ref):
-    d = sp.expand(sp.together(ours - ref))
-    if d != 0:
-        d = sp.simplify(d)
-    ok = d == 0
+    def symbolic():
+        d = sp.expand(sp.together(ours - ref))
+        if d != 0:
+            d = sp.simplify(d)
+        return d == 0
+    ok = G.compare(G.key(name), ours, ref, symbolic)
     print("%-62s %s" % (name, "identical" if ok else "DIFFERENT"))
     if not ok:
         failures.append(name)
 
 
 def main():
-    if not os.path.isdir(REF):
-        print("reference not mounted at %s: nothing to check" % REF)
-        return 0
-    bc = open(os.path.join(REF, "leung-bessel", "src", "bessel.c")).read()
+    mounted = G.mounted
+    if not mounted:
+        print("reference side: stored values (tests/golden/check_literals.json)")
+    bc = open(os.path.join(REF, "leung-bessel", "src", "bessel.c")).read() if mounted else None
     # (RIMPHONY_CHECK_DEV_BESSEL: another file in place of dev_bessel.h -- the test suite feeds a mutated copy to
     # show that a flipped sign is caught)
     dev = open(os.environ.get("RIMPHONY_CHECK_DEV_BESSEL") or os.path.join(ROOT, "rimphony_amd", "csrc", "dev_bessel.h")).read()
     orc = open(os.path.join(ROOT, "oracle", "rimo_bessel.c")).read()
-    t1, t2, U, eps, Z, ninv, n, x, z, ez, t3, t4, t10 = sp.symbols("t1 t2 U eps Z ninv n x z ez t3 t4 t10")
+    t1, t2, U, eps, Z_, ninv, n, x, z, ez, t3, t4, t10 = sp.symbols("t1 t2 U eps Z ninv n x z ez t3 t4 t10")
     At = sp.symbols("At0:16")
 
     # ---------------- Meissel "first" (bessel.c:94-149) ----------------
-    first = between(bc, "BesselJ_Meissel_First(const double n", "/* The Debye")
-    ref_v1 = ev(c_statement(first, "Vsum1"), {"U": U, "t1": t1})
-    ref_v2 = ev(c_statement(first, "Vsum2"), {"ninv": ninv, "t2": t2})
-    ref_lg = ev(c_statement(first, "loggamma_exp"), {"ninv": ninv, "t2": t2, "t3": t2 * t2})
-    ref_e2 = ev(c_statement(first, "exp2").replace("sqrt(2.*eps)", "S"), {"n": n, "eps": eps, "S": sp.Symbol("S")})
-    m = re.search(r"invZp1\s*=\s*(1 \+ .*?);", first, re.S)
-    ref_iz = ev(m.group(1).replace("\n", " "), {"Z": Z})
+    ref_v1 = ref_v2 = ref_lg = ref_e2 = ref_iz = Z
+    if mounted:
+        first = between(bc, "BesselJ_Meissel_First(const double n", "/* The Debye")
+        ref_v1 = ev(c_statement(first, "Vsum1"), {"U": U, "t1": t1})
+        ref_v2 = ev(c_statement(first, "Vsum2"), {"ninv": ninv, "t2": t2})
+        ref_lg = ev(c_statement(first, "loggamma_exp"), {"ninv": ninv, "t2": t2, "t3": t2 * t2})
+        ref_e2 = ev(c_statement(first, "exp2").replace("sqrt(2.*eps)", "S"), {"n": n, "eps": eps, "S": sp.Symbol("S")})
+        m = re.search(r"invZp1\s*=\s*(1 \+ .*?);", first, re.S)
+        ref_iz = ev(m.group(1).replace("\n", " "), {"Z": Z_})
 
     # (oracle/rimo_bessel.c keeps these coefficients in tables walked by loops -- a structurally different
     # transcription; it is held to dev_bessel.h bit for bit by tests/test_host_side.py and the GPU parity tests, so
@@ -129,7 +141,7 @@ def main():
                               "o": None})
         same("Meissel-first small-eps series (bessel.c:131-135) vs %s" % label, e["exp2"], ref_e2)
         series = between(body, "if (Z < 1.e-3) {", "} else {" if label == "dev_bessel.h" else "else")
-        e = run_chain(series.replace("invZp1 = q", "res = q"), {"Z": Z})
+        e = run_chain(series.replace("invZp1 = q", "res = q"), {"Z": Z_})
         same("Meissel-first 1/(1+Z) series (bessel.c:143)      vs %s" % label, e.get("res", e.get("invZp1")), ref_iz)
     # order-only pieces hoisted into leung_order (dev) / computed in place (oracle)
     lo = between(dev, "RIM_DEV LeungOrder leung_order(double n)", "return o;")
@@ -140,24 +152,29 @@ def main():
     same("log-gamma 1/n^k part (bessel.c:130)                 vs dev_bessel.h", e["loggamma_exp"].subs(1 / n, ninv), ref_lg.subs(t2, ninv ** 2))
     for nm, val in (("thr_lo", "0.174857"), ("thr_hi", "0.295966"), ("thr_plus_lo", "0.151550")):
         refv = {"thr_lo": "MINUS_ETA_A_INTERCEPT", "thr_hi": "MINUS_ETA_B_INTERCEPT", "thr_plus_lo": "PLUS_ETA_A_INTERCEPT"}[nm]
-        rm = re.search(r"const\s+double\s+" + refv + r"\s*=\s*([-\d.eE]+)", bc)
-        # the slope literal as the reference writes it in its region test: "-0.6666666 * log10(n) + <intercept>"
-        sl = re.search(r"(-?0\.6666666\d*)\s*\*\s*logn\s*\+\s*" + refv, bc)
-        if sl is None:
-            raise SystemExit("slope of the region test not found next to " + refv)
+        want = Z
+        if mounted:
+            rm = re.search(r"const\s+double\s+" + refv + r"\s*=\s*([-\d.eE]+)", bc)
+            # the slope literal as the reference writes it in its region test: "-0.6666666 * log10(n) + <intercept>"
+            sl = re.search(r"(-?0\.6666666\d*)\s*\*\s*logn\s*\+\s*" + refv, bc)
+            if sl is None:
+                raise SystemExit("slope of the region test not found next to " + refv)
+            want = sp.Rational(sl.group(1)) * sp.Symbol("L10") + sp.Rational(rm.group(1))
         ours = e["o_" + nm]
-        want = sp.Rational(sl.group(1)) * sp.Symbol("L10") + sp.Rational(rm.group(1))
         same("region threshold %s (bessel.c:313-316)       vs dev_bessel.h" % nm.ljust(11), ours, want)
-    rm = re.search(r"const\s+double\s+PLUS_ETA_B_INTERCEPT\s*=\s*([-\d.eE]+)", bc)
-    print("%-62s %s" % ("PLUS_ETA_B_INTERCEPT %s in dev_bessel.h bessel_j" % rm.group(1),
-                        "present" if rm.group(1) in between(dev, "RIM_DEV double bessel_j(", "RIM_DEV double bessel_dj(") else "MISSING"))
-    if rm.group(1) not in between(dev, "RIM_DEV double bessel_j(", "RIM_DEV double bessel_dj("):
+    pb = G.datum("PLUS_ETA_B_INTERCEPT",
+                 lambda: re.search(r"const\s+double\s+PLUS_ETA_B_INTERCEPT\s*=\s*([-\d.eE]+)", bc).group(1))
+    print("%-62s %s" % ("PLUS_ETA_B_INTERCEPT %s in dev_bessel.h bessel_j" % pb,
+                        "present" if pb in between(dev, "RIM_DEV double bessel_j(", "RIM_DEV double bessel_dj(") else "MISSING"))
+    if pb not in between(dev, "RIM_DEV double bessel_j(", "RIM_DEV double bessel_dj("):
         failures.append("PLUS_ETA_B_INTERCEPT")
 
     # ---------------- Meissel "second" (bessel.c:57-88) ----------------
-    second = between(bc, "BesselJ_Meissel_Second(const double n", "/* Meissel's \"first\"")
-    ref_p = ev(c_statement(second, "exp_val"), {"t1": t1, "t2": t2})
-    ref_q = ev(c_statement(second, "Qsum"), {"t1": t1, "t2": t2, "U": U})
+    ref_p = ref_q = Z
+    if mounted:
+        second = between(bc, "BesselJ_Meissel_Second(const double n", "/* Meissel's \"first\"")
+        ref_p = ev(c_statement(second, "exp_val"), {"t1": t1, "t2": t2})
+        ref_q = ev(c_statement(second, "Qsum"), {"t1": t1, "t2": t2, "U": U})
     for label, text, fn in (("dev_bessel.h", dev, "RIM_DEV double meissel_second("),):
         if fn not in text:
             print("(no %s in %s)" % (fn, label))
@@ -170,13 +187,15 @@ def main():
         same("Meissel-second Q_n sum (bessel.c:77-83)              vs %s" % label, e["Qsum"], ref_q.subs(t2, U * U))
 
     # ---------------- Debye epsilon expansion (bessel.c:159-213) ----------------
-    deb = between(bc, "BesselJ_Debye_Eps_Exp(const double n", "#define MINUS_ETA_A_INTERCEPT" if "#define MINUS_ETA_A_INTERCEPT" in bc else "return t149;")
-    env = {"At": list(At), "t3": t3, "t4": t4, "t10": t10, "z": z, "ez": ez, "x": x, "M_PI": sp.pi}
-    env["t38"] = ev(c_statement(deb, "t38"), env)
-    env["t44"] = x
-    for nm in ("t70", "t93", "t107", "t114", "t146"):
-        env[nm] = ev(c_statement(deb, nm), env)
-    ref_d = ev(c_statement(deb, "t149"), env)
+    ref_d = Z
+    if mounted:
+        deb = between(bc, "BesselJ_Debye_Eps_Exp(const double n", "#define MINUS_ETA_A_INTERCEPT" if "#define MINUS_ETA_A_INTERCEPT" in bc else "return t149;")
+        env = {"At": list(At), "t3": t3, "t4": t4, "t10": t10, "z": z, "ez": ez, "x": x, "M_PI": sp.pi}
+        env["t38"] = ev(c_statement(deb, "t38"), env)
+        env["t44"] = x
+        for nm in ("t70", "t93", "t107", "t114", "t146"):
+            env[nm] = ev(c_statement(deb, nm), env)
+        ref_d = ev(c_statement(deb, "t149"), env)
     atenv = {"RIM_AT%d" % k: At[k] for k in range(16)}
     atenv.update({"t3": t3, "t4": t4, "t10": t10, "z": z, "x": x, "ez": ez, "RIM_PI": sp.pi})
     body = between(dev, "RIM_DEV double debye_eps(double n, double x)", "// The same for two orders at one x")
@@ -216,32 +235,35 @@ def main():
         failures.append("At table")
 
     # ---------------- exp_factor Taylor series (bessel.c:22-51) ----------------
-    ef = between(bc, "exp_factor(", "/* Meissel's \"second\"")
-    m = re.search(r"(\(?\s*40320[^;]*?)/\s*40320", ef, re.S) or re.search(r"return[^;]*?(\(.*?)\s*/\s*40320[^;]*;", ef, re.S)
     fe = sp.Symbol("f_exp")
     refq = None
-    for cand in re.findall(r"=\s*([^;]*40320[^;]*);|return\s+([^;]*40320[^;]*);", ef, re.S):
-        txt = (cand[0] or cand[1]).replace("\n", " ")
-        try:
-            refq = ev(txt, {"f_exp": fe, "f_factor": sp.Symbol("F"), "x": fe})
-            break
-        except Exception:
-            continue
+    ef_name = "exp_factor Taylor series (bessel.c:22-51)              vs dev_bessel.h"
+    if mounted:
+        ef = between(bc, "exp_factor(", "/* Meissel's \"second\"")
+        for cand in re.findall(r"=\s*([^;]*40320[^;]*);|return\s+([^;]*40320[^;]*);", ef, re.S):
+            txt = (cand[0] or cand[1]).replace("\n", " ")
+            try:
+                refq = ev(txt, {"f_exp": fe, "f_factor": sp.Symbol("F"), "x": fe})
+                break
+            except Exception:
+                continue
+    elif G.has(ef_name):
+        refq = Z
     body = between(dev, "if (a < 1e-3) {", "}")
     e = run_chain(body.replace("return ", "res = "), {"f_exp": fe, "f_factor": sp.Symbol("F")})
     if refq is not None:
-        same("exp_factor Taylor series (bessel.c:22-51)              vs dev_bessel.h", e["res"], refq)
+        same(ef_name, e["res"], refq)
     else:
         print("exp_factor series: reference expression not isolated (skipped)")
 
     # ---------------- heyvaerts.rs ----------------
-    hv = open(os.path.join(REF, "src", "heyvaerts.rs")).read()
+    hv = open(os.path.join(REF, "src", "heyvaerts.rs")).read() if mounted else None
     dh = open(os.path.join(ROOT, "rimphony_amd", "csrc", "dev_heyvaerts.h")).read()
     oh = open(os.path.join(ROOT, "oracle", "rimo_heyvaerts.c")).read()
     for rust, ours in (("FOUR_OVER_SQRT_27", "RIM_FOUR_OVER_SQRT_27"), ("INVERSE_SQRT_3", "RIM_INVERSE_SQRT_3"),
                        ("SQRT_8_OVER_3", "RIM_SQRT_8_OVER_3"), ("THREE_TWO_THIRDS", "RIM_THREE_TWO_THIRDS"),
                        ("G_APPROXIMATION_CUTOFF", "RIM_G_APPROXIMATION_CUTOFF")):
-        rv = re.search(r"const\s+" + rust + r":\s*f64\s*=\s*([-\d.eE]+)", hv).group(1)
+        rv = G.datum("constant " + rust, lambda: re.search(r"const\s+" + rust + r":\s*f64\s*=\s*([-\d.eE]+)", hv).group(1))
         ov = re.search(r"#define\s+" + ours + r"\s+([-\d.eE]+)", dh).group(1)
         cv = re.search(r"#define\s+" + rust + r"\s+([-\d.eE]+)", oh)
         ok = float(rv) == float(ov) and (cv is None or float(cv.group(1)) == float(rv))
@@ -347,7 +369,7 @@ def main():
     nr_q = nr_q[:nr_q.rindex("}")]
     nr_v = member[member.index("const double z ="):]
     for fn, body in (("h_nr_element", nr_q), ("f_nr_element", nr_v)):
-        ref, _ = run_rust(fn)
+        ref = run_rust(fn)[0] if mounted else Z
         body = body.replace("sh.dfds", "dfdsigma()")
         e = run_dev("X;\n" + body + "\nEND", "X", "END", extra={k: common[k] for k in ("a1", "a2", "xa1p", "x_sq", "u", "u2")})
         same("%s (heyvaerts.rs:379-394 / 453-468)            vs dev_heyvaerts.h" % fn, e["RESULT"], ref)
@@ -359,7 +381,7 @@ def main():
     gsym = sp.Symbol("S83") * (sig - xx) ** sp.Rational(3, 2) / sp.sqrt(xx)
     for fn in ("h_qr_element", "f_qr_element"):
         for branch in ("small", "large"):
-            ref, _ = run_rust(fn, branch)
+            ref = run_rust(fn, branch)[0] if mounted else Z
             # oracle (a literal restatement: bessel calls in place)
             body = between(oh, "static double %s(const hey_state *st)" % fn, "\n}\n")
             body = re.sub(r"if \(g < G_APPROXIMATION_CUTOFF\) \{(.*?)\} else \{(.*?)\}",
@@ -386,6 +408,7 @@ def main():
     if failures:
         print("FAILED:", ", ".join(failures))
         return 1
+    G.save()
     print("all tables identical to the reference sources")
     return 0
 
