@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the hot path: eight-coefficient parameter-points per second (BASELINE.json's metric).
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 A step = one pass of the hot path, N x (full_calculation + compute_all_dimensionless) with ALL EIGHT coefficients per
 point (lib.rs:178-191), over one batch of `--points` synthetic power-law points per GPU (the generator of
@@ -9,7 +9,8 @@ rimphony_amd/workload.py, rows 1000000.. of its table), inputs resident in HBM b
 batch is sharded interleaved over the ranks (one process per GPU) and the per-rank tables are gathered to rank 0 with
 one RCCL gather per step; `value` = points of all ranks / max-over-ranks time, "scaling": "weak".
 
-Side objects of the JSON line:
+A plain run does only what the headline needs: stage the inputs, warm up, time the K steps, dump the outputs if asked,
+print the line.  Side objects of the JSON line:
   roofline          the dominant kernel of a step (group_kernel<0>: the six Symphony coefficients of a point in
                     lock-step): algorithmic flops = device-counted integrand samples (the REFERENCE's count: every
                     coefficient's own samples, whether or not the kernel shared their evaluation) x the hand-counted flops
@@ -19,6 +20,9 @@ Side objects of the JSON line:
                     `executed` = the fp64 work the vector unit really did (PMC instruction counts per pass x this run's
                     passes): the hardware-utilisation figure, below `achieved` where samples are shared
   roofline_faraday  the same for coop_kernel<HeyvaertsProblem<0>> (rho_Q, rho_V)
+  tail_of_last_step the longest chain of batches of a coefficient per kernel in the last timed step
+The three above come from the timed steps themselves.  The rest take runs of their own (about a minute on one GPU) and
+are measured only with --full; a plain run prints them as null:
   two_coeff         BASELINE configs[1] (power law, j_I + alpha_I only), with its own roofline
   thermal_eight     configs[2]'s table (thermal Juettner, eight coefficients)
   pitchypl_eight, pitchykappa_eight   configs[3] / configs[4]'s tables (the anisotropic distributions), with both rooflines
@@ -89,10 +93,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--points", type=int, default=131072, help="table rows per GPU per step")
     ap.add_argument("--config", default="cfg2_powerlaw_8")
-    ap.add_argument("--cpu-sample", type=int, default=256,
-                    help="rows of the all-cores eight-coefficient CPU baseline (the other three are scaled from it; 0 = skip)")
-    ap.add_argument("--side-rows", type=int, default=65536, help="rows per GPU per step of the side legs (0 = skip them)")
-    ap.add_argument("--no-parity", action="store_true", help="skip the comparison with the literal-oracle vectors")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the side legs, the parity against the literal-oracle vectors and the CPU baseline")
+    ap.add_argument("--cpu-sample", type=int, default=None,
+                    help="with --full: rows of the all-cores eight-coefficient CPU baseline (the other three are scaled "
+                         "from it; default 256, 0 = skip)")
+    ap.add_argument("--side-rows", type=int, default=None,
+                    help="with --full: rows per GPU per step of the side legs (default 65536, 0 = skip them)")
+    ap.add_argument("--no-parity", action="store_true", help="with --full: skip the comparison with the literal-oracle vectors")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write the table of the last timed step to DIR/out.npy (float64 [rows, 8], non-finite entries "
                          "0) and DIR/out_nonfinite.npy (0 finite, 1 NaN, 2 +inf, 3 -inf); a fixed, seeded sample of the "
@@ -100,6 +108,10 @@ def main():
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full and (args.cpu_sample or args.side_rows):
+        ap.error("--cpu-sample and --side-rows size what --full measures: a plain run measures neither")
+    args.cpu_sample = 256 if args.cpu_sample is None else args.cpu_sample
+    args.side_rows = 65536 if args.side_rows is None else args.side_rows
 
     from rimphony_amd import launch
     if args.gpus > 1 and not launch.launched_by_launcher():
@@ -298,7 +310,7 @@ def main():
 
     # ---------------------------------------------------------------- side legs
     two = thermal = corner = gmin1 = pitchypl = pitchykappa = None
-    if args.side_rows > 0:
+    if args.full and args.side_rows > 0:
         R = args.side_rows
         two = side_leg("cfg2_powerlaw_jI_aI", min(4 * R, 262144), 2, 0)
         thermal = side_leg("cfg3_thermal_8", R, 2, 0)
@@ -311,7 +323,7 @@ def main():
 
     # ---------------------------------------------------------------- parity vs the literal-flavour vectors (rank 0)
     parity = None
-    if rank == 0 and not args.no_parity:
+    if args.full and rank == 0 and not args.no_parity:
         parity = {}
         control = {}
         for cfg in ("cfg2_powerlaw_jI_aI", "cfg2_powerlaw_8", "cfg3_thermal_8", "cfg4_pitchypl_8", "cfg5_pitchykappa_8"):
@@ -337,7 +349,7 @@ def main():
         value = points / elapsed
 
         cpu = None
-        if args.cpu_sample > 0 and world == 1:
+        if args.full and args.cpu_sample > 0 and world == 1:
             sys.path.insert(0, os.path.join(ROOT, "tests"))
             import oracle_bind
             L = oracle_bind.load("det")
@@ -388,7 +400,7 @@ def main():
                                   "faraday_heaviest_coefficient_batches": tail["faraday_heaviest_batches"],
                                   "faraday_heaviest_row": tail["faraday_heaviest_row"],
                                   "note": "the sequential chain of batches of the heaviest task bounds how early a launch can end"},
-            "cpu_baseline": cpu,
+            "full": args.full, "cpu_baseline": cpu,
             "two_coeff": two, "thermal_eight": thermal, "pitchypl_eight": pitchypl, "pitchykappa_eight": pitchykappa,
             "corner_theta_lt_0.05": corner, "gamma_min_1": gmin1, "parity": parity,
             "shared_mode": int(ctx.shared_mode()) if hasattr(ctx, "shared_mode") else None,

@@ -281,6 +281,22 @@ def test_bench_runs_the_rccl_path_in_a_world_of_one():
     assert "kernel_ms_min_max_over_ranks" in line["roofline"]      # only present when the collectives ran
 
 
+def test_bench_side_objects_only_with_full(gpu_ctx):
+    """A plain bench run does only what its headline needs: the side legs, `parity` and `cpu_baseline` are printed as
+    null.  --full measures them (here on tiny sizes) in the same line."""
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "0", "--points", "64"]
+    side = ("two_coeff", "thermal_eight", "pitchypl_eight", "pitchykappa_eight", "corner_theta_lt_0.05", "gamma_min_1",
+            "parity", "cpu_baseline")
+    with gpu_ctx.released():
+        for extra, full in (([], False), (["--full", "--side-rows", "64", "--cpu-sample", "8"], True)):
+            r = subprocess.run(cmd + extra, capture_output=True, text=True, env=env, timeout=900)
+            assert r.returncode == 0, r.stderr[-3000:]
+            line = json.loads(r.stdout.strip().splitlines()[-1])
+            assert line["full"] is full and line["value"] > 0 and line["roofline"]["frac"] > 0
+            assert [k for k in side if (line[k] is not None) != full] == []
+
+
 def test_f32_integrand_is_refused_and_slower_where_it_still_runs(gpu_ctx):
     """RIMPHONY_PRECISION_F32_INTEGRAND (BASELINE configs[4]) is not a mode of the product: RIMPHONY_ENOTSUP for every
     distribution (include/rimphony_hip.h says why), as is an unknown precision.  The claim behind the refusal is

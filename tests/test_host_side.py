@@ -371,6 +371,15 @@ def test_bench_parent_never_touches_the_gpu():
     assert "import torch" not in head.split("def main")[1]
 
 
+def test_bench_refuses_full_only_sizes_without_full():
+    """--side-rows and --cpu-sample size what only --full measures: a plain run that is given one refuses it instead of
+    ignoring it (before any import of torch)."""
+    for opt in ("--side-rows", "--cpu-sample"):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), opt, "8"], capture_output=True, text=True,
+                           timeout=120)
+        assert r.returncode == 2 and "--full" in r.stderr, r.stderr
+
+
 def test_api_refuses_bad_device_inputs():
     """compute_batch_device takes raw pointers: strided views, wrong dtype, wrong length and host tensors are
     refused before any pointer reaches the C ABI (no GPU needed for these checks)."""
