@@ -52,8 +52,8 @@ struct GroupArgs {
 };
 
 // faraday = 0: the Symphony groups ({j_I, alpha_I, j_Q, alpha_Q}, {j_V, alpha_V}); 1: the Faraday pair {rho_Q, rho_V}
+// (the kernel is launched through this pointer: rimphony_hip.hip, launch_persistent)
 const void *rim_group_kernel(int kind, int faraday);
 int rim_group_waves(int faraday);
-int rim_group_launch(int kind, int faraday, unsigned grid, hipStream_t st, const GroupArgs &ga);
 
 #endif

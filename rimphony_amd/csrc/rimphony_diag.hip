@@ -209,12 +209,7 @@ extern "C" int rimphony_n_integral_batch_device(rimphony_ctx *c, int kind, const
     if (rc) return rc;
     const double *norm = rim_ctx_norm(c);
     double *spill = rim_ctx_spill(c);
-    switch (kind) {
-    case 0: hipLaunchKernelGGL(n_integral_kernel<0>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pa, norm, count, d_n_lo, d_n_hi, d_out, spill); break;
-    case 1: hipLaunchKernelGGL(n_integral_kernel<1>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pa, norm, count, d_n_lo, d_n_hi, d_out, spill); break;
-    case 2: hipLaunchKernelGGL(n_integral_kernel<2>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pa, norm, count, d_n_lo, d_n_hi, d_out, spill); break;
-    default: hipLaunchKernelGGL(n_integral_kernel<3>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pa, norm, count, d_n_lo, d_n_hi, d_out, spill); break;
-    }
+    rim_with_kind(kind, [&](auto K) { hipLaunchKernelGGL(n_integral_kernel<decltype(K)::value>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pa, norm, count, d_n_lo, d_n_hi, d_out, spill); });
     HIP_TRY(hipGetLastError());
     return RIMPHONY_OK;
 }
@@ -236,12 +231,7 @@ extern "C" int rimphony_deriv_probe_batch_device(rimphony_ctx *c, int kind, cons
     if (rc) return rc;
     const double *norm = rim_ctx_norm(c);
     double *spill = rim_ctx_spill(c);
-    switch (kind) {
-    case 0: hipLaunchKernelGGL(deriv_probe_kernel<0>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pa, norm, count, d_n_start, d_out, spill); break;
-    case 1: hipLaunchKernelGGL(deriv_probe_kernel<1>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pa, norm, count, d_n_start, d_out, spill); break;
-    case 2: hipLaunchKernelGGL(deriv_probe_kernel<2>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pa, norm, count, d_n_start, d_out, spill); break;
-    default: hipLaunchKernelGGL(deriv_probe_kernel<3>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pa, norm, count, d_n_start, d_out, spill); break;
-    }
+    rim_with_kind(kind, [&](auto K) { hipLaunchKernelGGL(deriv_probe_kernel<decltype(K)::value>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pa, norm, count, d_n_start, d_out, spill); });
     HIP_TRY(hipGetLastError());
     return RIMPHONY_OK;
 }
@@ -263,12 +253,7 @@ extern "C" int rimphony_gamma_contribution_batch_device(rimphony_ctx *c, int kin
     if (rc) return rc;
     const double *norm = rim_ctx_norm(c);
     double *spill = rim_ctx_spill(c);
-    switch (kind) {
-    case 0: hipLaunchKernelGGL(gamma_contribution_kernel<0>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pa, norm, count, d_gamma, d_out, spill); break;
-    case 1: hipLaunchKernelGGL(gamma_contribution_kernel<1>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pa, norm, count, d_gamma, d_out, spill); break;
-    case 2: hipLaunchKernelGGL(gamma_contribution_kernel<2>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pa, norm, count, d_gamma, d_out, spill); break;
-    default: hipLaunchKernelGGL(gamma_contribution_kernel<3>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pa, norm, count, d_gamma, d_out, spill); break;
-    }
+    rim_with_kind(kind, [&](auto K) { hipLaunchKernelGGL(gamma_contribution_kernel<decltype(K)::value>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pa, norm, count, d_gamma, d_out, spill); });
     HIP_TRY(hipGetLastError());
     return RIMPHONY_OK;
 }
@@ -310,12 +295,7 @@ extern "C" int rimphony_calc_f_batch_device(rimphony_ctx *c, int kind, const dou
     if (count == 0) return RIMPHONY_OK;
     const double *norm = rim_ctx_norm(c);
     const dim3 grid((unsigned) ((count + 63) / 64)), block(64);
-    switch (kind) {
-    case 0: hipLaunchKernelGGL(calc_f_kernel<0>, grid, block, RIM_DYN_LDS, st, pa, norm, norm_override, count, d_gamma, d_cos_xi, d_f, d_dfdg, d_dfdcx); break;
-    case 1: hipLaunchKernelGGL(calc_f_kernel<1>, grid, block, RIM_DYN_LDS, st, pa, norm, norm_override, count, d_gamma, d_cos_xi, d_f, d_dfdg, d_dfdcx); break;
-    case 2: hipLaunchKernelGGL(calc_f_kernel<2>, grid, block, RIM_DYN_LDS, st, pa, norm, norm_override, count, d_gamma, d_cos_xi, d_f, d_dfdg, d_dfdcx); break;
-    default: hipLaunchKernelGGL(calc_f_kernel<3>, grid, block, RIM_DYN_LDS, st, pa, norm, norm_override, count, d_gamma, d_cos_xi, d_f, d_dfdg, d_dfdcx); break;
-    }
+    rim_with_kind(kind, [&](auto K) { hipLaunchKernelGGL(calc_f_kernel<decltype(K)::value>, grid, block, RIM_DYN_LDS, st, pa, norm, norm_override, count, d_gamma, d_cos_xi, d_f, d_dfdg, d_dfdcx); });
     HIP_TRY(hipGetLastError());
     return RIMPHONY_OK;
 }
@@ -415,12 +395,7 @@ extern "C" int rimphony_hey_element_batch_device(rimphony_ctx *c, int kind, cons
     if (count == 0) return RIMPHONY_OK;
     const double *norm = rim_ctx_norm(c);
     const dim3 grid((unsigned) ((count + 63) / 64)), block(64);
-    switch (kind) {
-    case 0: hipLaunchKernelGGL(hey_element_kernel<0>, grid, block, RIM_DYN_LDS, st, pa, norm, qr, count, d_fixed, d_v, d_out); break;
-    case 1: hipLaunchKernelGGL(hey_element_kernel<1>, grid, block, RIM_DYN_LDS, st, pa, norm, qr, count, d_fixed, d_v, d_out); break;
-    case 2: hipLaunchKernelGGL(hey_element_kernel<2>, grid, block, RIM_DYN_LDS, st, pa, norm, qr, count, d_fixed, d_v, d_out); break;
-    default: hipLaunchKernelGGL(hey_element_kernel<3>, grid, block, RIM_DYN_LDS, st, pa, norm, qr, count, d_fixed, d_v, d_out); break;
-    }
+    rim_with_kind(kind, [&](auto K) { hipLaunchKernelGGL(hey_element_kernel<decltype(K)::value>, grid, block, RIM_DYN_LDS, st, pa, norm, qr, count, d_fixed, d_v, d_out); });
     HIP_TRY(hipGetLastError());
     return RIMPHONY_OK;
 }
@@ -440,12 +415,7 @@ extern "C" int rimphony_hey_outer_batch_device(rimphony_ctx *c, int kind, const 
     rc = rim_wave_grid(c, count, 16, &grid);
     if (rc) return rc;
     const double *norm = rim_ctx_norm(c);
-    switch (kind) {
-    case 0: hipLaunchKernelGGL(hey_outer_kernel<0>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pa, norm, qr, count, d_u, d_out, rim_ctx_spill(c)); break;
-    case 1: hipLaunchKernelGGL(hey_outer_kernel<1>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pa, norm, qr, count, d_u, d_out, rim_ctx_spill(c)); break;
-    case 2: hipLaunchKernelGGL(hey_outer_kernel<2>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pa, norm, qr, count, d_u, d_out, rim_ctx_spill(c)); break;
-    default: hipLaunchKernelGGL(hey_outer_kernel<3>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pa, norm, qr, count, d_u, d_out, rim_ctx_spill(c)); break;
-    }
+    rim_with_kind(kind, [&](auto K) { hipLaunchKernelGGL(hey_outer_kernel<decltype(K)::value>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pa, norm, qr, count, d_u, d_out, rim_ctx_spill(c)); });
     HIP_TRY(hipGetLastError());
     return RIMPHONY_OK;
 }

@@ -606,54 +606,13 @@ __global__ __launch_bounds__(64, P::WAVES) void group_kernel(GroupArgs ga)
 }
 
 // ---- launch interface (group_launch.h) -----------------------------------------------------------------------
-template <class P>
-static const void *kernel_ptr() { return reinterpret_cast<const void *>(group_kernel<P>); }
-
 const void *rim_group_kernel(int kind, int faraday)
 {
-    if (faraday) {
-        switch (kind) {
-        case 0: return kernel_ptr<HeyGroupProblem<0>>();
-        case 1: return kernel_ptr<HeyGroupProblem<1>>();
-        case 2: return kernel_ptr<HeyGroupProblem<2>>();
-        default: return kernel_ptr<HeyGroupProblem<3>>();
-        }
-    }
-    switch (kind) {
-    case 0: return kernel_ptr<SymGroupProblem<0>>();
-    case 1: return kernel_ptr<SymGroupProblem<1>>();
-    case 2: return kernel_ptr<SymGroupProblem<2>>();
-    default: return kernel_ptr<SymGroupProblem<3>>();
-    }
+    return rim_with_kind(kind, [&](auto K) -> const void * {
+        constexpr int KIND = decltype(K)::value;
+        return faraday ? reinterpret_cast<const void *>(group_kernel<HeyGroupProblem<KIND>>)
+                       : reinterpret_cast<const void *>(group_kernel<SymGroupProblem<KIND>>);
+    });
 }
 
 int rim_group_waves(int faraday) { return faraday ? RIM_HEY_GROUP_WAVES : RIM_GROUP_WAVES; }
-
-template <class P>
-static void launch(unsigned grid, hipStream_t st, const GroupArgs &ga)
-{
-    hipLaunchKernelGGL(group_kernel<P>, dim3(grid), dim3(64), RIM_DYN_LDS, st, ga);
-}
-
-int rim_group_launch(int kind, int faraday, unsigned grid, hipStream_t st, const GroupArgs &ga)
-{
-    if (faraday) {
-        switch (kind) {
-        case 0: launch<HeyGroupProblem<0>>(grid, st, ga); break;
-        case 1: launch<HeyGroupProblem<1>>(grid, st, ga); break;
-        case 2: launch<HeyGroupProblem<2>>(grid, st, ga); break;
-        default: launch<HeyGroupProblem<3>>(grid, st, ga); break;
-        }
-    } else {
-        switch (kind) {
-        case 0: launch<SymGroupProblem<0>>(grid, st, ga); break;
-        case 1: launch<SymGroupProblem<1>>(grid, st, ga); break;
-        case 2: launch<SymGroupProblem<2>>(grid, st, ga); break;
-        default: launch<SymGroupProblem<3>>(grid, st, ga); break;
-        }
-    }
-    const hipError_t e = hipGetLastError();
-    if (e == hipSuccess) return RIMPHONY_OK;
-    rim_set_last_error("group_kernel launch", hipGetErrorString(e));
-    return RIMPHONY_EHIP;
-}

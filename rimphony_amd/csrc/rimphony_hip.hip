@@ -12,9 +12,11 @@
 // workgroups; per-task cost spans orders of magnitude, so
 // tasks are handed out dynamically, one atomicAdd per task.
 #include <hip/hip_runtime.h>
+#include <climits>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <new>
 #include <string>
 #include <vector>
@@ -35,6 +37,7 @@ using namespace rim;
 #include "rimphony_internal.h"
 #include "coop_common.h"
 #include "group_launch.h"
+#include "launch_plan.h"
 
 // ------------------------------------------------------------------------------
 // normalisation integrands (power_law.rs:95-96, pitchy_kappa.rs:100-104; the
@@ -988,24 +991,111 @@ __global__ __launch_bounds__(64) void qag_selftest_kernel(size_t count, const in
 // host side
 // ------------------------------------------------------------------------------
 
+// A device buffer of the context's workspace.  It only ever grows; `cap` counts what its user counts (points, waves,
+// board slots).  A failed growth leaves it empty, so that a smaller call can still be served.
+template <class T>
+struct RimDevBuf {
+    T *p;
+    size_t cap;
+    void release()
+    {
+        if (p) (void) hipFree(p);
+        p = nullptr;
+        cap = 0;
+    }
+    // room for n elements in `bytes` bytes; `what` names the buffer in the error text
+    int grow(size_t n, size_t bytes, const char *what)
+    {
+        if (cap >= n) return RIMPHONY_OK;
+        release();
+        if (hipMalloc(&p, bytes) != hipSuccess) {
+            (void) hipGetLastError();       // reported here: it must not stick to the next HIP call
+            p = nullptr;
+            char msg[200];
+            snprintf(msg, sizeof msg, "%zu MB for %s", bytes >> 20, what);
+            rim_set_last_error("hipMalloc", msg);
+            return RIMPHONY_ENOMEM;
+        }
+        cap = n;
+        return RIMPHONY_OK;
+    }
+};
+
+// ---- the knobs: environment variables read once, when a context is created (DESIGN.md "Environment variables") ----
+struct RimKnobs {
+    long long no_assist, sym_solo, faraday_symphony_order, rounds, early_squad, early_min, f32_variant, faraday_group, owner_wait_us;
+};
+enum RimKnobKind {
+    KNOB_ON_1,          // on when the value starts with '1'
+    KNOB_OFF_0,         // on unless the value starts with '0'
+    KNOB_LETTER,        // on when the value starts with the letter in `lo`
+    KNOB_INT,           // atoi of the value (also of an empty one), clamped to [lo, hi]
+    KNOB_U64            // strtoull of a non-empty value
+};
+struct RimKnobDef {
+    const char *name;
+    RimKnobKind kind;
+    long long RimKnobs::*field;
+    long long dflt, lo, hi;
+    const char *text;
+};
+static const RimKnobDef RIM_KNOBS[] = {
+    { "RIMPHONY_NO_ASSIST", KNOB_ON_1, &RimKnobs::no_assist, 0, 0, 0,
+      "=1: one wave per task to the end, no cooperative tail (A/B measurements)" },
+    { "RIMPHONY_SYM_SOLO", KNOB_ON_1, &RimKnobs::sym_solo, 0, 0, 0,
+      "=1: one wave per (point, coefficient) for the Symphony slots, the round-2 kernel (A/B measurements)" },
+    { "RIMPHONY_FARADAY_ORDER", KNOB_LETTER, &RimKnobs::faraday_symphony_order, 0, 's', 0,
+      "=symphony: the Faraday launch visits the points in the Symphony order (A/B measurements)" },
+    { "RIMPHONY_ROUNDS", KNOB_OFF_0, &RimKnobs::rounds, 1, 0, 0,
+      "=0: a long outer quadrature evaluates one interval per batch, as until round 4 (A/B measurements)" },
+    { "RIMPHONY_EARLY_SQUAD", KNOB_INT, &RimKnobs::early_squad, -1, INT_MIN, 1024,
+      "waves of the Faraday grid that serve the longest chain from the start (0: off; unset or negative: the kind's default)" },
+    { "RIMPHONY_EARLY_MIN", KNOB_INT, &RimKnobs::early_min, 16, 1, INT_MAX,
+      "batches after which a task competes for that help" },
+    { "RIMPHONY_F32_VARIANT", KNOB_ON_1, &RimKnobs::f32_variant, 0, 0, 0,
+      "=1: accept RIMPHONY_PRECISION_F32_INTEGRAND (measurement hook)" },
+    { "RIMPHONY_FARADAY_GROUP", KNOB_ON_1, &RimKnobs::faraday_group, 0, 0, 0,
+      "=1: rho_Q and rho_V of a point in lock-step (measured slower: DESIGN.md section 5)" },
+    { "RIMPHONY_OWNER_WAIT_US", KNOB_U64, &RimKnobs::owner_wait_us, 120000000, 0, 0,
+      "microseconds an owner waits for its helpers before it recomputes a batch itself (test hook; 0 is accepted)" },
+};
+
+static RimKnobs rim_read_knobs()
+{
+    RimKnobs k;
+    for (const RimKnobDef &d : RIM_KNOBS) {
+        const char *e = getenv(d.name);
+        long long v = d.dflt;
+        switch (d.kind) {
+        case KNOB_ON_1: v = (e && e[0] == '1'); break;
+        case KNOB_OFF_0: v = (e && e[0] == '0') ? 0 : 1; break;
+        case KNOB_LETTER: v = (e && e[0] == (char) d.lo); break;
+        case KNOB_INT:
+            if (e) v = atoi(e);
+            if (v < d.lo) v = d.lo;
+            if (v > d.hi) v = d.hi;
+            break;
+        case KNOB_U64: if (e && e[0]) v = (long long) strtoull(e, nullptr, 10); break;
+        }
+        k.*d.field = v;
+    }
+    return k;
+}
+
 struct rimphony_ctx {
     int device;
     int n_cu;
-    unsigned long long *d_queue;   // 4 words
-    double *d_norm;
-    unsigned *d_perm;               // [norm_cap] task order + ORDER_BUCKETS histogram words behind it
-    double *d_spill;                // [spill_waves][SPILL_DOUBLES_PER_WAVE]
-    size_t spill_waves;
-    AssistSlot *d_board;            // [board_slots] + flags behind
-    size_t board_slots;
-    int no_assist;                  // RIMPHONY_NO_ASSIST=1: one wave per task to the end (A/B measurements)
-    size_t norm_cap;
+    RimKnobs knobs;
+    int no_assist;                  // knobs.no_assist, or shared mode: one wave per task to the end
+    RimDevBuf<unsigned long long> d_queue;  // 16 words
+    RimDevBuf<double> d_norm;       // [cap], and with it
+    RimDevBuf<unsigned> d_perm;     // [cap] task order + ORDER_BUCKETS histogram words behind it
+    RimDevBuf<double> d_spill;      // [cap waves][SPILL_DOUBLES_PER_WAVE]
+    RimDevBuf<char> d_board;        // [cap] AssistSlot + flag words behind
     // staging for the host-buffer entry point
-    double *d_in;
-    size_t in_cap;
-    double *d_out;
-    int32_t *d_status;
-    size_t out_cap;
+    RimDevBuf<double> d_in;
+    RimDevBuf<double> d_out;        // [cap][8], and with it
+    RimDevBuf<int32_t> d_status;    // [cap][8] status words, then [cap][8] uint64 work counters
     // HIP events bracketing the most recent Symphony / Faraday launch
     hipEvent_t ev_start, ev_stop;   // Symphony launch
     int ev_valid;
@@ -1015,10 +1105,11 @@ struct rimphony_ctx {
     unsigned long long *hb_host;
     unsigned long long *hb_dev;
     unsigned long long hb_task;
-    // resident workgroups per CU of coop_kernel<P>, by problem (0 Symphony, 1 Heyvaerts) and distribution kind:
-    // queried once per context (= per device) and instantiation
+    // what hipOccupancyMaxActiveBlocksPerMultiprocessor answered (-1: the query failed), asked once per context
+    // (= per device) and instantiation: coop_kernel<P> by problem (0 Symphony, 1 Heyvaerts) and distribution kind,
     int resident[2][4];
-    int resident_f32[4];            // ... and of the Symphony kernels' fp32-integrand variants
+    int resident_f32[4];            // ... the Symphony kernels' fp32-integrand variants,
+    int resident_group[2][4];       // ... group_kernel<P> [Symphony groups / Faraday pair][kind]
     // 0: this context has the GPU to itself (it holds the device's lock file); 1: another context or process had
     // the device first -- smaller persistent grids, no cooperative tail (see rimphony_ctx_create)
     int shared_mode;
@@ -1030,20 +1121,10 @@ struct rimphony_ctx {
     hipEvent_t ev_batch;
     int ev_batch_valid;
     std::recursive_mutex *mu;
-    // group kernel (rimphony_group.hip): per-wave spill regions and board, resident workgroups per CU by kind
-    double *d_gspill;
-    size_t gspill_waves;
+    // group kernel (rimphony_group.hip): per-wave spill regions and board
+    RimDevBuf<double> d_gspill;     // [cap waves]
     int gspill_faraday;             // the region is sized for the Faraday pair's longer outer lists
-    GroupSlot *d_gboard;            // [gboard_slots] + flag words behind
-    size_t gboard_slots;
-    int resident_group[2][4];       // [Symphony groups / Faraday pair][kind]
-    int f32_variant;                // RIMPHONY_F32_VARIANT=1: accept RIMPHONY_PRECISION_F32_INTEGRAND (measurement hook)
-    int sym_solo;                   // RIMPHONY_SYM_SOLO=1: one wave per (point, coefficient), the round-2 kernel (A/B measurements)
-    int faraday_symphony_order;     // RIMPHONY_FARADAY_ORDER=symphony: the Faraday launch visits the points in the Symphony order (A/B measurements)
-    int rounds;                     // RIMPHONY_ROUNDS=0: a long outer quadrature evaluates one interval per batch, as until round 4 (A/B measurements)
-    int early_squad;                // RIMPHONY_EARLY_SQUAD: waves of the Faraday grid that serve the longest chain from the start (0: off; -1: the kind's default)
-    int early_min;                  // RIMPHONY_EARLY_MIN: batches after which a task competes for that help
-    int faraday_group;              // RIMPHONY_FARADAY_GROUP=1: rho_Q and rho_V of a point in lock-step (measured slower: DESIGN.md section 5)
+    RimDevBuf<char> d_gboard;       // [cap] GroupSlot + flag words behind
 };
 
 // ---- last error (thread-local text; the codes are in rimphony_hip.h) ---------------------------
@@ -1057,14 +1138,6 @@ void rim_clear_last_error() { t_last_error[0] = 0; }
 
 void rim_ctx_lock(rimphony_ctx *c) { c->mu->lock(); }
 void rim_ctx_unlock(rimphony_ctx *c) { c->mu->unlock(); }
-
-static const int NPARAMS[4] = { 4, 1, 5, 4 };
-
-extern "C" int rimphony_dist_nparams(int kind)
-{
-    if (kind < 0 || kind > 3) return RIMPHONY_EINVAL;
-    return NPARAMS[kind];
-}
 
 extern "C" const char *rimphony_strerror(int code)
 {
@@ -1112,16 +1185,16 @@ static int take_device_lock(int device, int *fd_out)
 
 static void ctx_free(rimphony_ctx *c)
 {
-    if (c->d_queue) (void) hipFree(c->d_queue);
-    if (c->d_norm) (void) hipFree(c->d_norm);
-    if (c->d_perm) (void) hipFree(c->d_perm);
-    if (c->d_spill) (void) hipFree(c->d_spill);
-    if (c->d_board) (void) hipFree(c->d_board);
-    if (c->d_gspill) (void) hipFree(c->d_gspill);
-    if (c->d_gboard) (void) hipFree(c->d_gboard);
-    if (c->d_in) (void) hipFree(c->d_in);
-    if (c->d_out) (void) hipFree(c->d_out);
-    if (c->d_status) (void) hipFree(c->d_status);
+    c->d_queue.release();
+    c->d_norm.release();
+    c->d_perm.release();
+    c->d_spill.release();
+    c->d_board.release();
+    c->d_gspill.release();
+    c->d_gboard.release();
+    c->d_in.release();
+    c->d_out.release();
+    c->d_status.release();
     if (c->hb_host) (void) hipHostFree(c->hb_host);
     if (c->ev_start) (void) hipEventDestroy(c->ev_start);
     if (c->ev_stop) (void) hipEventDestroy(c->ev_stop);
@@ -1150,14 +1223,8 @@ extern "C" int rimphony_ctx_create(int device, rimphony_ctx **out)
     c->lock_fd = -1;
     c->mu = new (std::nothrow) std::recursive_mutex();
     if (!c->mu) { delete c; return RIMPHONY_ENOMEM; }
-    { const char *e = getenv("RIMPHONY_NO_ASSIST"); c->no_assist = (e && e[0] == '1'); }
-    { const char *e = getenv("RIMPHONY_SYM_SOLO"); c->sym_solo = (e && e[0] == '1'); }
-    { const char *e = getenv("RIMPHONY_FARADAY_ORDER"); c->faraday_symphony_order = (e && e[0] == 's'); }
-    { const char *e = getenv("RIMPHONY_ROUNDS"); c->rounds = (e && e[0] == '0') ? 0 : 1; }
-    { const char *e = getenv("RIMPHONY_EARLY_SQUAD"); c->early_squad = e ? atoi(e) : -1; if (c->early_squad > 1024) c->early_squad = 1024; }
-    { const char *e = getenv("RIMPHONY_EARLY_MIN"); c->early_min = e ? atoi(e) : 16; if (c->early_min < 1) c->early_min = 1; }
-    { const char *e = getenv("RIMPHONY_F32_VARIANT"); c->f32_variant = (e && e[0] == '1'); }
-    { const char *e = getenv("RIMPHONY_FARADAY_GROUP"); c->faraday_group = (e && e[0] == '1'); }
+    c->knobs = rim_read_knobs();
+    c->no_assist = c->knobs.no_assist != 0;
     c->shared_mode = take_device_lock(device, &c->lock_fd);
     if (c->shared_mode) {
         const char *e = getenv("RIMPHONY_EXCLUSIVE");
@@ -1169,16 +1236,11 @@ extern "C" int rimphony_ctx_create(int device, rimphony_ctx **out)
         int khz = 0;
         if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, device) != hipSuccess || khz <= 0) khz = 100000;
         c->ticks_per_s = (unsigned long long) khz * 1000ull;
-        c->owner_wait_ticks = 120ull * c->ticks_per_s;
-        // test hook: RIMPHONY_OWNER_WAIT_US=<microseconds> shortens the bound so that the recompute path runs
+        // 120 s; the test hook RIMPHONY_OWNER_WAIT_US shortens the bound so that the recompute path runs
         // (tests/test_gpu_boundary.py::test_owner_fallback_changes_no_bit)
-        const char *e = getenv("RIMPHONY_OWNER_WAIT_US");
-        if (e && e[0]) {
-            const unsigned long long us = strtoull(e, nullptr, 10);
-            c->owner_wait_ticks = us * c->ticks_per_s / 1000000ull;
-        }
+        c->owner_wait_ticks = (unsigned long long) c->knobs.owner_wait_us * c->ticks_per_s / 1000000ull;
     }
-    if (hipMalloc(&c->d_queue, 16 * sizeof(unsigned long long)) != hipSuccess) { ctx_free(c); return RIMPHONY_ENOMEM; }
+    if (c->d_queue.grow(16, 16 * sizeof(unsigned long long), "the task queue words")) { ctx_free(c); return RIMPHONY_ENOMEM; }
     if (hipEventCreate(&c->ev_start) != hipSuccess || hipEventCreate(&c->ev_stop) != hipSuccess ||
         hipEventCreate(&c->ev_fstart) != hipSuccess || hipEventCreate(&c->ev_fstop) != hipSuccess ||
         hipEventCreateWithFlags(&c->ev_batch, hipEventDisableTiming) != hipSuccess) {
@@ -1221,32 +1283,18 @@ void rim_ctx_leave(rimphony_ctx *c, hipStream_t st)
 
 static int ensure_spill(rimphony_ctx *c, size_t waves)
 {
-    if (c->spill_waves >= waves) return RIMPHONY_OK;
-    if (c->d_spill) (void) hipFree(c->d_spill);
-    c->d_spill = nullptr;
-    c->spill_waves = 0;
-    if (hipMalloc(&c->d_spill, waves * SPILL_DOUBLES_PER_WAVE * sizeof(double)) != hipSuccess) return RIMPHONY_ENOMEM;
-    c->spill_waves = waves;
-    return RIMPHONY_OK;
+    return c->d_spill.grow(waves, waves * SPILL_DOUBLES_PER_WAVE * sizeof(double), "the subinterval spill region");
 }
 
 static int ensure_norm(rimphony_ctx *c, size_t n)
 {
-    if (c->norm_cap >= n) return RIMPHONY_OK;
-    if (c->d_norm) (void) hipFree(c->d_norm);
-    if (c->d_perm) (void) hipFree(c->d_perm);
-    c->d_norm = nullptr;
-    c->d_perm = nullptr;
-    c->norm_cap = 0;
-    if (hipMalloc(&c->d_norm, n * sizeof(double)) != hipSuccess) { c->d_norm = nullptr; return RIMPHONY_ENOMEM; }
-    if (hipMalloc(&c->d_perm, (n + ORDER_BUCKETS) * sizeof(unsigned)) != hipSuccess) {
-        (void) hipFree(c->d_norm);
-        c->d_norm = nullptr;
-        c->d_perm = nullptr;
-        return RIMPHONY_ENOMEM;
-    }
-    c->norm_cap = n;
-    return RIMPHONY_OK;
+    if (c->d_norm.cap >= n) return RIMPHONY_OK;
+    // the pair grows together
+    c->d_perm.release();
+    int rc = c->d_norm.grow(n, n * sizeof(double), "the normalisations");
+    if (!rc) rc = c->d_perm.grow(n, (n + ORDER_BUCKETS) * sizeof(unsigned), "the visiting order");
+    if (rc) c->d_norm.release();
+    return rc;
 }
 
 // persistent grid: enough single-wave workgroups to fill every SIMD several times over
@@ -1258,140 +1306,197 @@ static unsigned persistent_grid(const rimphony_ctx *c, unsigned long long ntasks
     return (unsigned) g;
 }
 
-template <int KIND>
-static int launch_norm(rimphony_ctx *c, size_t n, const ParamPtrs &pp, double *d_norm, hipStream_t st)
+static int launch_norm(rimphony_ctx *c, int kind, size_t n, const ParamPtrs &pp, double *d_norm, hipStream_t st)
 {
-    HIP_TRY(hipMemsetAsync(c->d_queue, 0, sizeof(unsigned long long), st));
+    HIP_TRY(hipMemsetAsync(c->d_queue.p, 0, sizeof(unsigned long long), st));
     const unsigned grid = persistent_grid(c, n, 16);
     int rc = ensure_spill(c, grid);
     if (rc) return rc;
-    hipLaunchKernelGGL(norm_kernel<KIND>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pp, n, d_norm, c->d_queue, c->d_spill);
+    rim_with_kind(kind, [&](auto K) {
+        hipLaunchKernelGGL(norm_kernel<decltype(K)::value>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pp, n, d_norm, c->d_queue.p, c->d_spill.p);
+    });
     HIP_TRY(hipGetLastError());
+    return RIMPHONY_OK;
+}
+
+static const int NPARAMS[4] = { 4, 1, 5, 4 };
+
+extern "C" int rimphony_dist_nparams(int kind)
+{
+    if (kind < 0 || kind > 3) return RIMPHONY_EINVAL;
+    return NPARAMS[kind];
+}
+
+static int rim_precision_check(const rimphony_ctx *c, int kind, int precision);
+
+// The argument checks of the batch entries, in the order every entry applies them: the kind and the `head` pointers
+// (RIMPHONY_EINVAL), the precision (prec_ctx != null; RIMPHONY_ENOTSUP), the empty batch (*empty set, RIMPHONY_OK: nothing
+// to read or write), the `data` pointers and the kind's parameter arrays (params != null; RIMPHONY_EINVAL).  Which code an
+// odd call gets depends on which pointers an entry puts before and which after the empty batch, so each entry says so.
+static int check_batch_args(int kind, std::initializer_list<const void *> head, const rimphony_ctx *prec_ctx, int precision,
+                            size_t n, bool *empty, std::initializer_list<const void *> data, const double *const *params)
+{
+    *empty = false;
+    if (kind < 0 || kind > 3) return RIMPHONY_EINVAL;
+    for (const void *q : head) if (!q) return RIMPHONY_EINVAL;
+    if (prec_ctx) { const int prc = rim_precision_check(prec_ctx, kind, precision); if (prc) return prc; }
+    if (n == 0) { *empty = true; return RIMPHONY_OK; }
+    for (const void *q : data) if (!q) return RIMPHONY_EINVAL;
+    if (params)
+        for (int k = 0; k < NPARAMS[kind]; k++) if (!params[k]) return RIMPHONY_EINVAL;
     return RIMPHONY_OK;
 }
 
 static int make_param_ptrs(int kind, const double *const *d_params, ParamPtrs &pp)
 {
-    if (kind < 0 || kind > 3 || !d_params) return RIMPHONY_EINVAL;
-    for (int k = 0; k < 5; k++) pp.p[k] = nullptr;
-    for (int k = 0; k < NPARAMS[kind]; k++) {
-        if (!d_params[k]) return RIMPHONY_EINVAL;
-        pp.p[k] = d_params[k];
-    }
+    bool empty;
+    const int rc = check_batch_args(kind, { d_params }, nullptr, 0, 1, &empty, {}, d_params);
+    if (rc) return rc;
+    for (int k = 0; k < 5; k++) pp.p[k] = k < NPARAMS[kind] ? d_params[k] : nullptr;
     return RIMPHONY_OK;
 }
 
 extern "C" int rimphony_batch_norm_device(rimphony_ctx *c, int kind, size_t n, const double *const *d_params,
                                           double *d_norm, void *stream)
 {
-    if (!c || kind < 0 || kind > 3) return RIMPHONY_EINVAL;
-    if (n == 0) return RIMPHONY_OK;
-    if (!d_norm) return RIMPHONY_EINVAL;
+    bool empty;
+    int rc = check_batch_args(kind, { c }, nullptr, 0, n, &empty, { d_norm, d_params }, d_params);
+    if (rc || empty) return rc;
     ParamPtrs pp;
-    int rc = make_param_ptrs(kind, d_params, pp);
+    rc = make_param_ptrs(kind, d_params, pp);
     if (rc) return rc;
     hipStream_t st = (hipStream_t) stream;
     RimCtxScope scope(c, st);
     rc = scope.enter();
     if (rc) return rc;
-    switch (kind) {
-    case 0: return launch_norm<0>(c, n, pp, d_norm, st);
-    case 1: return launch_norm<1>(c, n, pp, d_norm, st);
-    case 2: return launch_norm<2>(c, n, pp, d_norm, st);
-    default: return launch_norm<3>(c, n, pp, d_norm, st);
-    }
+    return launch_norm(c, kind, n, pp, d_norm, st);
 }
 
+// ---- the persistent launch ----------------------------------------------------------------------------------------
+// What differs between the kernels that run as a persistent grid with a cooperative tail: coop_kernel<P> (one wave per
+// coefficient) and group_kernel<P> (rimphony_group.hip: the coefficients of a point in lock-step).
+struct PersistentKernel {
+    const void *fn;                 // kernel entry: occupancy and attribute queries, launch
+    int waves;                      // waves per SIMD of its launch bounds
+    bool early_help;                // it has the early-help protocol (coop_common.h) ...
+    unsigned early_squad;           // ... with this default squad
+    bool faraday;                   // which pair of timing events brackets it
+    int *resident;                  // the context's cache cell for the occupancy answer
+    RimDevBuf<double> *spill;       // per-wave spill region and
+    size_t spill_doubles;           // ... its doubles per wave
+    RimDevBuf<char> *board;         // the board,
+    size_t slot_bytes;              // ... the size of a slot
+    size_t clear_bytes;             // ... and how much of a slot is zeroed before a launch
+    const char *launch_what;        // names a failed launch in the error text
+};
+
+// coop_kernel<P> of a problem (0: Symphony, prec 1: its fp32-integrand variant; 1: Heyvaerts) and distribution kind
 template <class P>
-static int launch_coop(rimphony_ctx *c, const SymArgs &a, hipStream_t st, hipEvent_t ev_start, hipEvent_t ev_stop, int *resident)
+static PersistentKernel coop_kernel_of()
 {
-    const unsigned long long ntasks = (unsigned long long) a.n * (unsigned) a.nslots;
-    // more waves than tasks on small batches: the surplus waves start as helpers right away
-    const unsigned long long want_waves = (ntasks > (1ull << 40) || c->no_assist) ? ntasks : ntasks * 64ull;
-    // Every wave of the grid should be resident: an idle wave waits for the waves that still own a task.  Ask the
-    // runtime how many of these workgroups a CU really holds (registers, LDS) instead of trusting the launch bounds;
-    // cached per context (= per device) and kernel instantiation.  The query knows nothing of other work on the
-    // device: should part of the grid not be resident after all, helpers leave after 2 s without work and an owner
-    // that waits in vain recomputes its batch itself (coop_kernel), so every wait ends and no result changes.
-    if (*resident == 0) {
+    PersistentKernel k = {};
+    k.fn = reinterpret_cast<const void *>(coop_kernel<P>);
+    k.waves = (int) P::WAVES;
+    k.early_help = P::EARLY_HELP != 0;
+    k.early_squad = (unsigned) P::EARLY_SQUAD;
+    return k;
+}
+static PersistentKernel rim_coop_kernel(int problem, int kind, int prec)
+{
+    return rim_with_kind(kind, [&](auto K) -> PersistentKernel {
+        constexpr int KIND = decltype(K)::value;
+        if (problem) return coop_kernel_of<HeyvaertsProblem<KIND>>();
+        if (!prec) return coop_kernel_of<SymphonyProblem<KIND>>();
+#if defined(RIM_F32_SMOOTH)
+        constexpr int F32_KIND = KIND;                  // the measurement build of the "smooth" variant serves all four kinds
+#else
+        constexpr int F32_KIND = KIND == 0 ? 0 : 1;     // (kinds 2 and 3 were refused at the entry: RIMPHONY_ENOTSUP)
+#endif
+        return coop_kernel_of<SymphonyProblem<F32_KIND, 1>>();
+    });
+}
+
+// Plans the grid, grows the spill region and the board, lets `fill(plan)` complete the kernel's argument struct (`base` is
+// the SymArgs inside it, `kargs` the struct itself) and enqueues: board clear, board_init_kernel, start event, kernel, stop
+// event.
+template <class Fill>
+static int launch_persistent(rimphony_ctx *c, const PersistentKernel &k, unsigned long long ntasks, SymArgs &base, void *kargs,
+                             hipStream_t st, Fill &&fill)
+{
+    // how many of these workgroups a CU holds (launch_plan.h): asked once per context and instantiation
+    if (*k.resident == 0) {
         int nb = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, coop_kernel<P>, 64, RIM_DYN_LDS) != hipSuccess || nb < 1)
-            nb = 4;       // conservative: one wave per SIMD
-        *resident = nb < 4 * (int) P::WAVES ? nb : 4 * (int) P::WAVES;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k.fn, 64, RIM_DYN_LDS) != hipSuccess || nb < 1) nb = -1;
+        *k.resident = nb;
     }
-    int resident_per_cu = *resident;
-    {   // The occupancy query has been seen to count one workgroup too many when the grid is LDS-bound to the last
-        // granule (a grid with non-resident waves does not fail, it stalls: every helper's 2 s idle bound).  Re-derive
-        // the LDS limit here with the 512-byte allocation granule and one granule of slack.
-        hipFuncAttributes fa;
-        if (hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(coop_kernel<P>)) == hipSuccess) {
-            const size_t lds = ((fa.sharedSizeBytes + RIM_DYN_LDS + 511) / 512) * 512;
-            if (lds > 0) {
-                const int by_lds = (int) ((160 * 1024 - 512) / lds);
-                if (by_lds >= 1 && by_lds < resident_per_cu) resident_per_cu = by_lds;
-            }
-        }
+    size_t static_lds = 0, dyn_lds = 0;
+    hipFuncAttributes fa;
+    if (hipFuncGetAttributes(&fa, k.fn) == hipSuccess) { static_lds = fa.sharedSizeBytes; dyn_lds = RIM_DYN_LDS; }
+    const unsigned want_squad = c->knobs.early_squad >= 0 ? (unsigned) c->knobs.early_squad : k.early_squad;
+    const RimGridPlan plan = rim_plan_grid(c->n_cu, ntasks, *k.resident, static_lds, dyn_lds, k.waves, c->shared_mode != 0,
+                                           c->no_assist != 0, want_squad, k.early_help);
+    const unsigned grid = plan.grid;
+    // The group kernels' region holds, per wave, four members' lists at the GSL limits of the path -- 0.86 MB for the
+    // Symphony groups (5000 + 1000 entries), 1.3 MB for the Faraday pair in lock-step (4096 + 4096; off by default): 4.4 GB
+    // of the 288 for a full persistent grid of 5120 waves, held until the context is destroyed.  One sized for the Symphony
+    // groups does not serve the Faraday pair.
+    const bool group = k.spill == &c->d_gspill;
+    if (group && k.faraday && !c->gspill_faraday) c->d_gspill.release();
+    if (k.spill->cap < grid) {
+        char what[160];
+        snprintf(what, sizeof what, "the subinterval spill region of %u waves (lists beyond the LDS part)", grid);
+        const int rc = k.spill->grow(grid, (size_t) grid * k.spill_doubles * sizeof(double), what);
+        if (rc) return rc;
+        if (group) c->gspill_faraday = k.faraday;
     }
-    if (c->shared_mode) resident_per_cu = resident_per_cu >= 8 ? resident_per_cu / 4 : 2;   // leave room for the other tenant
-    const unsigned grid = persistent_grid(c, want_waves, resident_per_cu);
-    int rc = ensure_spill(c, grid);
+    int rc = k.board->grow(grid, (size_t) grid * k.slot_bytes + BOARD_FLAG_WORDS * sizeof(unsigned), "the board of the cooperative tail");
     if (rc) return rc;
-    if (c->board_slots < grid) {
-        if (c->d_board) (void) hipFree(c->d_board);
-        c->d_board = nullptr;
-        c->board_slots = 0;
-        if (hipMalloc(&c->d_board, (size_t) grid * sizeof(AssistSlot) + BOARD_FLAG_WORDS * sizeof(unsigned)) != hipSuccess)
-            return RIMPHONY_ENOMEM;
-        c->board_slots = grid;
+    base.board_flags = (unsigned *) (k.board->p + k.board->cap * k.slot_bytes);
+    base.idle_ticks = 2ull * c->ticks_per_s;
+    base.owner_ticks = c->owner_wait_ticks;
+    rc = fill(plan);
+    if (rc) return rc;
+    // every claim word starts closed (count 0; the payload arrays of a GroupSlot need no reset: an entry is written before
+    // its round is opened); flags: not exhausted, the waves that may fetch a task (the squad never does), nobody idle
+    if (k.clear_bytes == k.slot_bytes) HIP_TRY(hipMemsetAsync(k.board->p, 0, (size_t) grid * k.slot_bytes, st));
+    else HIP_TRY(hipMemset2DAsync(k.board->p, k.slot_bytes, 0, k.clear_bytes, grid, st));
+    hipLaunchKernelGGL(board_init_kernel, dim3(1), dim3(128), RIM_DYN_LDS, st, base.board_flags, grid - plan.early_squad);
+    HIP_TRY(hipEventRecord(k.faraday ? c->ev_fstart : c->ev_start, st));
+    void *params[] = { kargs };
+    hipError_t e = hipLaunchKernel(k.fn, dim3(grid), dim3(64), params, RIM_DYN_LDS, st);
+    const hipError_t last = hipGetLastError();
+    if (e == hipSuccess) e = last;
+    if (e != hipSuccess) {
+        rim_set_last_error(k.launch_what, hipGetErrorString(e));
+        return RIMPHONY_EHIP;
     }
-    SymArgs b = a;
-    b.spill = c->d_spill;
-    b.board = c->no_assist ? nullptr : c->d_board;
-    b.board_flags = (unsigned *) (c->d_board + c->board_slots);
-    b.idle_ticks = 2ull * c->ticks_per_s;
-    b.owner_ticks = c->owner_wait_ticks;
-    // the squad that serves the longest chain from the start (coop_common.h): only where there is a bulk to overlap
-    // with (many more tasks than waves) and the GPU is this context's own; blocks k * stride with an odd stride, so
-    // that the squad is spread over the XCDs (blocks go to them round-robin) and their CUs
-    b.early_squad = 0;
-    b.early_stride = 1;
-    b.early_classes = 1;
-    b.early_min = c->early_min;
-    b.turbo = c->rounds;
-    const unsigned want_squad = c->early_squad >= 0 ? (unsigned) c->early_squad : (unsigned) P::EARLY_SQUAD;
-    if (P::EARLY_HELP && b.board && !c->shared_mode && want_squad && ntasks >= 4ull * grid && grid >= 16u * want_squad) {
-        b.early_stride = (grid / want_squad) | 1u;
-        const unsigned fit = (grid - 1u) / b.early_stride + 1u;
-        b.early_squad = want_squad < fit ? want_squad : fit;
-        // one title per 64 waves of the squad (a batch has up to 62 requests), at most four
-        b.early_classes = b.early_squad >= 256u ? 4u : b.early_squad >= 128u ? 2u : 1u;
-    }
-    // every claim word starts closed (count 0); flags: not exhausted, `grid` waves that may fetch a task (the squad
-    // never does), nobody idle
-    HIP_TRY(hipMemsetAsync(c->d_board, 0, (size_t) grid * sizeof(AssistSlot), st));
-    hipLaunchKernelGGL(board_init_kernel, dim3(1), dim3(128), RIM_DYN_LDS, st, b.board_flags, grid - b.early_squad);
-    HIP_TRY(hipEventRecord(ev_start, st));
-    hipLaunchKernelGGL(coop_kernel<P>, dim3(grid), dim3(64), RIM_DYN_LDS, st, b);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(ev_stop, st));
+    HIP_TRY(hipEventRecord(k.faraday ? c->ev_fstop : c->ev_stop, st));
+    if (k.faraday) c->evf_valid = 1; else c->ev_valid = 1;
     return RIMPHONY_OK;
 }
 
-template <int KIND, int PREC = 0>
-static int launch_symphony(rimphony_ctx *c, const SymArgs &a, hipStream_t st)
+// One wave per (point, coefficient): coop_kernel<SymphonyProblem> (problem 0) or coop_kernel<HeyvaertsProblem> (1).
+static int launch_coop(rimphony_ctx *c, int problem, int kind, int prec, const SymArgs &a, hipStream_t st)
 {
-    const int rc = launch_coop<SymphonyProblem<KIND, PREC>>(c, a, st, c->ev_start, c->ev_stop,
-                                                           PREC ? &c->resident_f32[KIND] : &c->resident[0][KIND]);
-    if (rc == RIMPHONY_OK) c->ev_valid = 1;
-    return rc;
-}
-
-template <int KIND>
-static int launch_heyvaerts(rimphony_ctx *c, const SymArgs &a, hipStream_t st)
-{
-    const int rc = launch_coop<HeyvaertsProblem<KIND>>(c, a, st, c->ev_fstart, c->ev_fstop, &c->resident[1][KIND]);
-    if (rc == RIMPHONY_OK) c->evf_valid = 1;
-    return rc;
+    PersistentKernel k = rim_coop_kernel(problem, kind, prec);
+    k.faraday = problem != 0;
+    k.resident = prec ? &c->resident_f32[kind] : &c->resident[problem][kind];
+    k.spill = &c->d_spill;
+    k.spill_doubles = SPILL_DOUBLES_PER_WAVE;
+    k.board = &c->d_board;
+    k.slot_bytes = k.clear_bytes = sizeof(AssistSlot);
+    k.launch_what = "hipGetLastError()";
+    SymArgs b = a;
+    return launch_persistent(c, k, (unsigned long long) a.n * (unsigned) a.nslots, b, &b, st, [&](const RimGridPlan &plan) -> int {
+        b.spill = c->d_spill.p;
+        b.board = c->no_assist ? nullptr : (AssistSlot *) c->d_board.p;
+        b.early_squad = plan.early_squad;
+        b.early_stride = plan.early_stride;
+        b.early_classes = plan.early_classes;
+        b.early_min = (int) c->knobs.early_min;
+        b.turbo = (int) c->knobs.rounds;
+        return RIMPHONY_OK;
+    });
 }
 
 // The slots of a batch as (point, group) tasks (rimphony_group.hip).  Symphony: group 0 = the selected ones of
@@ -1399,11 +1504,8 @@ static int launch_heyvaerts(rimphony_ctx *c, const SymArgs &a, hipStream_t st)
 // {rho_Q, rho_V} (heyvaerts_group.h).
 static int launch_group(rimphony_ctx *c, int kind, const SymArgs &a, uint32_t coeff_mask, int faraday, hipStream_t st)
 {
-    GroupArgs ga;
+    GroupArgs ga = {};
     ga.base = a;
-    ga.ngroups = 0;
-    ga.gslots[0] = ga.gslots[1] = 0;
-    ga.gnmem[0] = ga.gnmem[1] = 0;
     for (int grp = 0; grp < (faraday ? 1 : 2); grp++) {
         unsigned packed = 0;
         int nm = 0;
@@ -1413,77 +1515,30 @@ static int launch_group(rimphony_ctx *c, int kind, const SymArgs &a, uint32_t co
         if (nm) { ga.gslots[ga.ngroups] = packed; ga.gnmem[ga.ngroups] = nm; ga.ngroups++; }
     }
     if (ga.ngroups == 0) return RIMPHONY_OK;
-    const unsigned long long ntasks = (unsigned long long) a.n * (unsigned) ga.ngroups;
-    const unsigned long long want_waves = (ntasks > (1ull << 40) || c->no_assist) ? ntasks : ntasks * 64ull;
-    int *resident = &c->resident_group[faraday ? 1 : 0][kind];
-    const void *kfn = rim_group_kernel(kind, faraday);
-    const int waves = rim_group_waves(faraday);
-    if (*resident == 0) {
-        int nb = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kfn, 64, RIM_DYN_LDS) != hipSuccess || nb < 1) nb = 4;
-        *resident = nb < 4 * waves ? nb : 4 * waves;
-    }
-    int resident_per_cu = *resident;
-    {   // the LDS limit re-derived with the 512-byte allocation granule and one granule of slack (see launch_coop)
-        hipFuncAttributes fa;
-        if (hipFuncGetAttributes(&fa, kfn) == hipSuccess) {
-            const size_t lds = ((fa.sharedSizeBytes + RIM_DYN_LDS + 511) / 512) * 512;
-            if (lds > 0) {
-                const int by_lds = (int) ((160 * 1024 - 512) / lds);
-                if (by_lds >= 1 && by_lds < resident_per_cu) resident_per_cu = by_lds;
-            }
-        }
-    }
-    if (c->shared_mode) resident_per_cu = resident_per_cu >= 8 ? resident_per_cu / 4 : 2;
-    const unsigned grid = persistent_grid(c, want_waves, resident_per_cu);
-    if (c->gspill_waves < grid || (faraday && !c->gspill_faraday)) {
-        if (c->d_gspill) (void) hipFree(c->d_gspill);
-        c->d_gspill = nullptr;
-        c->gspill_waves = 0;
-        // per wave: four members' lists at the GSL limits of the path -- 0.86 MB for the Symphony groups (5000 + 1000
-        // entries), 1.3 MB for the Faraday pair in lock-step (4096 + 4096; off by default): 4.4 GB of the 288 for a full
-        // persistent grid of 5120 waves, held until the context is destroyed
-        const size_t per_wave = faraday ? SPILL_HEYGROUP_DOUBLES_PER_WAVE : SPILL_GROUP_DOUBLES_PER_WAVE;
-        const size_t bytes = (size_t) grid * (per_wave > SPILL_GROUP_DOUBLES_PER_WAVE ? per_wave : SPILL_GROUP_DOUBLES_PER_WAVE) * sizeof(double);
-        if (hipMalloc(&c->d_gspill, bytes) != hipSuccess) {
-            (void) hipGetLastError();
-            char msg[160];
-            snprintf(msg, sizeof msg, "%zu MB for the subinterval spill region of %u waves (lists beyond the LDS part)", bytes >> 20, grid);
-            rim_set_last_error("hipMalloc", msg);
-            return RIMPHONY_ENOMEM;
-        }
-        c->gspill_waves = grid;
-        c->gspill_faraday = faraday;
-    }
-    if (c->gboard_slots < grid) {
-        if (c->d_gboard) (void) hipFree(c->d_gboard);
-        c->d_gboard = nullptr;
-        c->gboard_slots = 0;
-        if (hipMalloc(&c->d_gboard, (size_t) grid * sizeof(GroupSlot) + BOARD_FLAG_WORDS * sizeof(unsigned)) != hipSuccess)
-            return RIMPHONY_ENOMEM;
-        c->gboard_slots = grid;
-    }
-    ga.gspill = c->d_gspill;
-    ga.gboard = c->d_gboard;
-    ga.coop = c->no_assist ? 0 : 1;
-    ga.prof = nullptr;
+    PersistentKernel k = {};
+    k.fn = rim_group_kernel(kind, faraday);
+    k.waves = rim_group_waves(faraday);
+    k.faraday = faraday != 0;
+    k.resident = &c->resident_group[faraday ? 1 : 0][kind];
+    k.spill = &c->d_gspill;
+    // (never less than the Symphony groups' size)
+    k.spill_doubles = faraday && SPILL_HEYGROUP_DOUBLES_PER_WAVE > SPILL_GROUP_DOUBLES_PER_WAVE ? SPILL_HEYGROUP_DOUBLES_PER_WAVE
+                                                                                                : SPILL_GROUP_DOUBLES_PER_WAVE;
+    k.board = &c->d_gboard;
+    k.slot_bytes = sizeof(GroupSlot);
+    k.clear_bytes = 32;             // claim, point, done, slots
+    k.launch_what = "group_kernel launch";
+    return launch_persistent(c, k, (unsigned long long) a.n * (unsigned) ga.ngroups, ga.base, &ga, st, [&](const RimGridPlan &plan) -> int {
+        ga.gspill = c->d_gspill.p;
+        ga.gboard = (GroupSlot *) c->d_gboard.p;
+        ga.coop = c->no_assist ? 0 : 1;
+        ga.base.board = nullptr;
 #if defined(RIM_PROF)
-    if (grid <= RIM_PROF_ROWS) HIP_TRY(hipGetSymbolAddress((void **) &ga.prof, HIP_SYMBOL(g_rim_prof)));
+        if (plan.grid <= RIM_PROF_ROWS) HIP_TRY(hipGetSymbolAddress((void **) &ga.prof, HIP_SYMBOL(g_rim_prof)));
 #endif
-    ga.base.board = nullptr;
-    ga.base.board_flags = (unsigned *) (c->d_gboard + c->gboard_slots);
-    ga.base.idle_ticks = 2ull * c->ticks_per_s;
-    ga.base.owner_ticks = c->owner_wait_ticks;
-    // every claim word starts closed; flags: not exhausted, `grid` active waves, nobody idle (the payload arrays of the
-    // slots need no reset: an entry is written before its round is opened)
-    HIP_TRY(hipMemset2DAsync(c->d_gboard, sizeof(GroupSlot), 0, 32, grid, st));
-    hipLaunchKernelGGL(board_init_kernel, dim3(1), dim3(128), RIM_DYN_LDS, st, ga.base.board_flags, grid);
-    HIP_TRY(hipEventRecord(faraday ? c->ev_fstart : c->ev_start, st));
-    const int rc = rim_group_launch(kind, faraday, grid, st, ga);       // sets the thread's last error itself
-    if (rc) return rc;
-    HIP_TRY(hipEventRecord(faraday ? c->ev_fstop : c->ev_stop, st));
-    if (faraday) c->evf_valid = 1; else c->ev_valid = 1;
-    return RIMPHONY_OK;
+        (void) plan;
+        return RIMPHONY_OK;
+    });
 }
 
 // `precision` of the batch entries.  F64 is the product.  F32_INTEGRAND (BASELINE configs[4]'s fp32-core integrand) is
@@ -1497,7 +1552,7 @@ static int launch_group(rimphony_ctx *c, int kind, const SymArgs &a, uint32_t co
 static int rim_precision_check(const rimphony_ctx *c, int kind, int precision)
 {
     if (precision == RIMPHONY_PRECISION_F64) return RIMPHONY_OK;
-    if (precision != RIMPHONY_PRECISION_F32_INTEGRAND || !c || !c->f32_variant) return RIMPHONY_ENOTSUP;
+    if (precision != RIMPHONY_PRECISION_F32_INTEGRAND || !c || !c->knobs.f32_variant) return RIMPHONY_ENOTSUP;
 #if !defined(RIM_F32_SMOOTH)      // (the measurement build of the "smooth" variant serves all four kinds)
     if (kind == RIMPHONY_PITCHY_PL || kind == RIMPHONY_PITCHY_KAPPA) return RIMPHONY_ENOTSUP;
 #endif
@@ -1516,13 +1571,12 @@ extern "C" int rimphony_batch_compute_device_ex(rimphony_ctx *c, int kind, size_
                                                 const double *const *d_params, uint32_t coeff_mask, int precision,
                                                 double *d_out, int32_t *d_status, uint64_t *d_work, void *stream)
 {
-    if (!c || kind < 0 || kind > 3) return RIMPHONY_EINVAL;
-    { const int prc = rim_precision_check(c, kind, precision); if (prc) return prc; }
-    if (n == 0) return RIMPHONY_OK;          // empty batch: nothing to read or write
-    if (!d_out || !d_s || !d_theta) return RIMPHONY_EINVAL;
+    bool empty;
+    int rc = check_batch_args(kind, { c }, c, precision, n, &empty, { d_out, d_s, d_theta }, nullptr);
+    if (rc || empty) return rc;
     hipStream_t st = (hipStream_t) stream;
     RimCtxScope scope(c, st);
-    int rc = scope.enter();
+    rc = scope.enter();
     if (rc) return rc;
     return batch_compute_locked(c, kind, n, d_s, d_theta, d_params, coeff_mask, precision, d_out, d_status, d_work, st);
 }
@@ -1548,71 +1602,54 @@ static int batch_compute_locked(rimphony_ctx *c, int kind, size_t n, const doubl
     if (rc) return rc;
 
     // full_calculation()
-    switch (kind) {
-    case 0: rc = launch_norm<0>(c, n, pp, c->d_norm, st); break;
-    case 1: rc = launch_norm<1>(c, n, pp, c->d_norm, st); break;
-    case 2: rc = launch_norm<2>(c, n, pp, c->d_norm, st); break;
-    default: rc = launch_norm<3>(c, n, pp, c->d_norm, st); break;
-    }
+    rc = launch_norm(c, kind, n, pp, c->d_norm.p, st);
     if (rc) return rc;
 
-    SymArgs a;
-    a.pp = pp;
-    a.s = d_s;
-    a.theta = d_theta;
-    a.norm = c->d_norm;
-    a.out = d_out;
-    a.status = d_status;
-    a.n = n;
-    a.queue = c->d_queue;
-    a.perm = nullptr;
-    a.spill = nullptr;
-    a.board = nullptr;
-    a.board_flags = nullptr;
+    // what both launches share; the launch itself sets what it decides (launch_persistent)
+    SymArgs base = {};
+    base.early_stride = 1;
+    base.early_classes = 1;
+    base.pp = pp;
+    base.s = d_s;
+    base.theta = d_theta;
+    base.norm = c->d_norm.p;
+    base.out = d_out;
+    base.status = d_status;
+    base.n = n;
+    base.queue = c->d_queue.p;
+    base.heartbeat = c->hb_dev;
+    base.hb_task = c->hb_task;
+    base.work = (unsigned long long *) d_work;
     const bool ordered = n > 4096 && n < 0xffffffffull;
     const double *const order_gmin = (kind == RIMPHONY_POWER_LAW) ? pp.p[1] : (kind == RIMPHONY_PITCHY_PL) ? pp.p[2] : nullptr;
     const double *const order_temp = (kind == RIMPHONY_THERMAL_JUETTNER) ? pp.p[0] : nullptr;
     // the visiting order of the Symphony launch now; the Faraday launch gets its own (same array, rebuilt on the stream
     // after the Symphony kernel: see below)
     auto build_order = [&](int faraday) -> int {
-        unsigned *hist = c->d_perm + c->norm_cap;
+        unsigned *hist = c->d_perm.p + c->d_perm.cap;
         const unsigned nb = (unsigned) ((n + 255) / 256);
         HIP_TRY(hipMemsetAsync(hist, 0, ORDER_BUCKETS * sizeof(unsigned), st));
         hipLaunchKernelGGL(order_hist_kernel, dim3(nb), dim3(256), RIM_DYN_LDS, st, d_s, d_theta, order_gmin, order_temp, n, hist, faraday);
         hipLaunchKernelGGL(order_scan_kernel, dim3(1), dim3(64), RIM_DYN_LDS, st, hist);
         hipLaunchKernelGGL(order_scatter_kernel, dim3(nb), dim3(256), RIM_DYN_LDS, st, d_s, d_theta, order_gmin, order_temp, n, hist,
-                           c->d_perm, faraday);
+                           c->d_perm.p, faraday);
         HIP_TRY(hipGetLastError());
         return RIMPHONY_OK;
     };
     if (ordered) {
         rc = build_order(0);
         if (rc) return rc;
-        a.perm = c->d_perm;
+        base.perm = c->d_perm.p;
     }
-    a.heartbeat = c->hb_dev;
-    a.hb_task = c->hb_task;
-    a.work = (unsigned long long *) d_work;
-    a.idle_ticks = 0;
-    a.owner_ticks = 0;
-    a.early_squad = 0;          // (set per launch by launch_coop)
-    a.early_stride = 1;
-    a.early_classes = 1;
-    a.early_min = 0;
-    a.turbo = 0;
     if (d_work) HIP_TRY(hipMemsetAsync(d_work, 0, n * 8 * sizeof(uint64_t), st));
-    a.nslots = 0;
+    SymArgs a = base, fa = base;
     uint32_t computed = 0;
     for (int k = 0; k < 6; k++)     // symphony slots: j/alpha x I,Q,V
         if (coeff_mask & (1u << k)) { a.slot[a.nslots++] = k; computed |= 1u << k; }
-    for (int k = a.nslots; k < 8; k++) a.slot[k] = 0;
-    SymArgs fa = a;                 // Faraday slots: rho_Q, rho_V
-    fa.nslots = 0;
-    for (int k = 6; k < 8; k++)
+    for (int k = 6; k < 8; k++)     // Faraday slots: rho_Q, rho_V
         if (coeff_mask & (1u << k)) { fa.slot[fa.nslots++] = k; computed |= 1u << k; }
-    for (int k = fa.nslots; k < 8; k++) fa.slot[k] = 0;
 
-    HIP_TRY(hipMemsetAsync(c->d_queue, 0, 16 * sizeof(unsigned long long), st));
+    HIP_TRY(hipMemsetAsync(c->d_queue.p, 0, 16 * sizeof(unsigned long long), st));
     {
         const size_t total = n * 8;
         hipLaunchKernelGGL(fill_unselected_kernel, dim3((unsigned) ((total + 255) / 256)), dim3(256), RIM_DYN_LDS, st,
@@ -1623,42 +1660,27 @@ static int batch_compute_locked(rimphony_ctx *c, int kind, size_t n, const doubl
         if (precision == RIMPHONY_PRECISION_F32_INTEGRAND) {
             // the six Symphony coefficients with the fp32-core integrand (detmath.h); the Faraday pair below stays fp64
             // (kinds 2 and 3 were refused at the entry: RIMPHONY_ENOTSUP)
-            if (kind == 0) rc = launch_symphony<0, 1>(c, a, st);
-#if defined(RIM_F32_SMOOTH)
-            else if (kind == 2) rc = launch_symphony<2, 1>(c, a, st);
-            else if (kind == 3) rc = launch_symphony<3, 1>(c, a, st);
-#endif
-            else rc = launch_symphony<1, 1>(c, a, st);
-        } else if (!c->sym_solo) {
+            rc = launch_coop(c, 0, kind, 1, a, st);
+        } else if (!c->knobs.sym_solo) {
             // the coefficients of a point that share their samples advance in lock-step on one wave
             rc = launch_group(c, kind, a, coeff_mask, 0, st);
         } else {
-            switch (kind) {
-            case 0: rc = launch_symphony<0>(c, a, st); break;
-            case 1: rc = launch_symphony<1>(c, a, st); break;
-            case 2: rc = launch_symphony<2>(c, a, st); break;
-            default: rc = launch_symphony<3>(c, a, st); break;
-            }
+            rc = launch_coop(c, 0, kind, 0, a, st);
         }
         if (rc) return rc;
     }
-    if (fa.nslots > 0 && ordered && !c->faraday_symphony_order) {
+    if (fa.nslots > 0 && ordered && !c->knobs.faraday_symphony_order) {
         rc = build_order(1);
         if (rc) return rc;
     }
-    if (fa.nslots > 0 && c->faraday_group) {
+    if (fa.nslots > 0 && c->knobs.faraday_group) {
         // rho_Q and rho_V of a point in lock-step (heyvaerts_group.h): they share their samples' coordinates, distribution
         // derivatives and Bessel functions.  Bit-identical, and measured SLOWER than one wave per coefficient (an executed
         // pass serves 1.38 coefficients and costs 1.6 solo passes: DESIGN.md section 5) -- off unless asked for.
         rc = launch_group(c, kind, fa, coeff_mask, 1, st);
         if (rc) return rc;
     } else if (fa.nslots > 0) {
-        switch (kind) {
-        case 0: rc = launch_heyvaerts<0>(c, fa, st); break;
-        case 1: rc = launch_heyvaerts<1>(c, fa, st); break;
-        case 2: rc = launch_heyvaerts<2>(c, fa, st); break;
-        default: rc = launch_heyvaerts<3>(c, fa, st); break;
-        }
+        rc = launch_coop(c, 1, kind, 0, fa, st);
         if (rc) return rc;
     }
     return RIMPHONY_OK;
@@ -1678,7 +1700,7 @@ extern "C" int rimphony_debug_heartbeat(rimphony_ctx *c, uint64_t task, uint64_t
     }
     // the group kernel (the default for the Symphony slots) writes no heartbeat: a watchdog polling word [10] would
     // wait for ever
-    if (!(task & (1ull << 62)) && !c->sym_solo) {
+    if (!(task & (1ull << 62)) && !c->knobs.sym_solo) {
         rim_set_last_error("rimphony_debug_heartbeat", "Symphony tasks are only watched with RIMPHONY_SYM_SOLO=1");
         return RIMPHONY_ENOTSUP;
     }
@@ -1704,7 +1726,7 @@ extern "C" int rimphony_debug_counters(rimphony_ctx *c, uint64_t out[32])
 #endif
     for (int k = 16; k < 32; k++) out[k] = 0;
     if (c->ev_batch_valid) HIP_TRY(hipEventSynchronize(c->ev_batch));     // the launch may be on a non-blocking stream
-    HIP_TRY(hipMemcpy(out, c->d_queue, 16 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out, c->d_queue.p, 16 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     return RIMPHONY_OK;
 }
 
@@ -1734,7 +1756,7 @@ extern "C" int rimphony_last_work(rimphony_ctx *c, rimphony_work *out)
     HIP_TRY(hipSetDevice(c->device));
     unsigned long long h[8];
     if (c->ev_batch_valid) HIP_TRY(hipEventSynchronize(c->ev_batch));     // the launch may be on a non-blocking stream
-    HIP_TRY(hipMemcpy(h, c->d_queue, sizeof h, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(h, c->d_queue.p, sizeof h, hipMemcpyDeviceToHost));
     out->samples = h[1];
     out->passes = h[2];
     out->inner_qags = h[3];
@@ -1753,7 +1775,7 @@ extern "C" int rimphony_last_tail(rimphony_ctx *c, uint64_t out[8])
     HIP_TRY(hipSetDevice(c->device));
     unsigned long long h[16];
     if (c->ev_batch_valid) HIP_TRY(hipEventSynchronize(c->ev_batch));
-    HIP_TRY(hipMemcpy(h, c->d_queue, sizeof h, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(h, c->d_queue.p, sizeof h, hipMemcpyDeviceToHost));
     out[0] = h[14] >> 40; out[1] = h[14] & 0xffffffffffull;        // (batches << 40) | row: rows to 1.1e12
     out[2] = h[15] >> 40; out[3] = h[15] & 0xffffffffffull;
     out[4] = h[8]; out[5] = h[9];
@@ -1765,12 +1787,10 @@ extern "C" int rimphony_batch_compute_ex(rimphony_ctx *c, int kind, size_t n,
                                          const double *s, const double *theta, const double *const *params,
                                          uint32_t coeff_mask, int precision, double *out, int32_t *status, uint64_t *work)
 {
-    if (!c || !out || kind < 0 || kind > 3 || !params) return RIMPHONY_EINVAL;
-    { const int prc = rim_precision_check(c, kind, precision); if (prc) return prc; }
-    if (n == 0) return RIMPHONY_OK;
-    if (!s || !theta) return RIMPHONY_EINVAL;
+    bool empty;
+    const int rc0 = check_batch_args(kind, { c, out, params }, c, precision, n, &empty, { s, theta }, params);
+    if (rc0 || empty) return rc0;
     const int np = NPARAMS[kind];
-    for (int k = 0; k < np; k++) if (!params[k]) return RIMPHONY_EINVAL;
     // ONE lock across staging, launch, synchronisation and copy-out: the staging buffers belong to the context, and a
     // second thread on the same context must not overwrite or re-allocate them before this call has copied its
     // table out (include/rimphony_hip.h: "Calls on one context are serialised").  The device entry below re-locks
@@ -1783,39 +1803,30 @@ extern "C" int rimphony_batch_compute_ex(rimphony_ctx *c, int kind, size_t n,
     {
         if (c->ev_batch_valid) HIP_TRY(hipEventSynchronize(c->ev_batch));   // the staging buffers may still be in use
         const size_t need_in = n * (size_t) (2 + np);
-        if (c->in_cap < need_in) {
-            if (c->d_in) (void) hipFree(c->d_in);
-            c->d_in = nullptr; c->in_cap = 0;
-            if (hipMalloc(&c->d_in, need_in * sizeof(double)) != hipSuccess) { c->d_in = nullptr; return RIMPHONY_ENOMEM; }
-            c->in_cap = need_in;
+        int rcb = c->d_in.grow(need_in, need_in * sizeof(double), "the staged inputs");
+        if (rcb) return rcb;
+        if (c->d_out.cap < n) {
+            // the pair grows together; status and the optional work counters share one allocation: [n][8] int32, then
+            // [n][8] uint64
+            c->d_status.release();
+            rcb = c->d_out.grow(n, n * 8 * sizeof(double), "the staged table");
+            if (!rcb) rcb = c->d_status.grow(n, n * 8 * (sizeof(int32_t) + sizeof(uint64_t)), "the staged status words and work counters");
+            if (rcb) { c->d_out.release(); return rcb; }
         }
-        if (c->out_cap < n) {
-            if (c->d_out) (void) hipFree(c->d_out);
-            if (c->d_status) (void) hipFree(c->d_status);
-            c->d_out = nullptr; c->d_status = nullptr; c->out_cap = 0;
-            // status and the optional work counters share one allocation: [n][8] int32, then [n][8] uint64
-            if (hipMalloc(&c->d_out, n * 8 * sizeof(double)) != hipSuccess) { c->d_out = nullptr; return RIMPHONY_ENOMEM; }
-            if (hipMalloc(&c->d_status, n * 8 * (sizeof(int32_t) + sizeof(uint64_t))) != hipSuccess) {
-                (void) hipFree(c->d_out);
-                c->d_out = nullptr; c->d_status = nullptr;
-                return RIMPHONY_ENOMEM;
-            }
-            c->out_cap = n;
-        }
-        HIP_TRY(hipMemcpy(c->d_in, s, n * sizeof(double), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(c->d_in + n, theta, n * sizeof(double), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(c->d_in.p, s, n * sizeof(double), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(c->d_in.p + n, theta, n * sizeof(double), hipMemcpyHostToDevice));
         for (int k = 0; k < np; k++) {
-            HIP_TRY(hipMemcpy(c->d_in + (size_t) (2 + k) * n, params[k], n * sizeof(double), hipMemcpyHostToDevice));
-            dp[k] = c->d_in + (size_t) (2 + k) * n;
+            HIP_TRY(hipMemcpy(c->d_in.p + (size_t) (2 + k) * n, params[k], n * sizeof(double), hipMemcpyHostToDevice));
+            dp[k] = c->d_in.p + (size_t) (2 + k) * n;
         }
-        if (work) d_work = (uint64_t *) (c->d_status + c->out_cap * 8);
+        if (work) d_work = (uint64_t *) (c->d_status.p + c->d_status.cap * 8);
     }
-    int rc = rimphony_batch_compute_device_ex(c, kind, n, c->d_in, c->d_in + n, dp, coeff_mask, precision, c->d_out,
-                                              c->d_status, d_work, nullptr);
+    int rc = rimphony_batch_compute_device_ex(c, kind, n, c->d_in.p, c->d_in.p + n, dp, coeff_mask, precision, c->d_out.p,
+                                              c->d_status.p, d_work, nullptr);
     if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(nullptr));
-    HIP_TRY(hipMemcpy(out, c->d_out, n * 8 * sizeof(double), hipMemcpyDeviceToHost));
-    if (status) HIP_TRY(hipMemcpy(status, c->d_status, n * 8 * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out, c->d_out.p, n * 8 * sizeof(double), hipMemcpyDeviceToHost));
+    if (status) HIP_TRY(hipMemcpy(status, c->d_status.p, n * 8 * sizeof(int32_t), hipMemcpyDeviceToHost));
     if (work) HIP_TRY(hipMemcpy(work, d_work, n * 8 * sizeof(uint64_t), hipMemcpyDeviceToHost));
     return RIMPHONY_OK;
 }
@@ -1840,13 +1851,12 @@ extern "C" int rimphony_batch_compute_multi(rimphony_ctx *const *ctxs, int n_ctx
                                             const double *s, const double *theta, const double *const *params,
                                             uint32_t coeff_mask, int precision, double *out, int32_t *status, uint64_t *work)
 {
-    if (!ctxs || n_ctx < 1 || n_ctx > 64 || kind < 0 || kind > 3 || !params) return RIMPHONY_EINVAL;
+    if (!ctxs || n_ctx < 1 || n_ctx > 64) return RIMPHONY_EINVAL;
     for (int r = 0; r < n_ctx; r++) if (!ctxs[r]) return RIMPHONY_EINVAL;
-    { const int prc = rim_precision_check(ctxs[0], kind, precision); if (prc) return prc; }
-    if (n == 0) return RIMPHONY_OK;
-    if (!s || !theta || !out) return RIMPHONY_EINVAL;
+    bool empty;
+    const int rc0 = check_batch_args(kind, { params }, ctxs[0], precision, n, &empty, { s, theta, out }, params);
+    if (rc0 || empty) return rc0;
     const int np = NPARAMS[kind];
-    for (int k = 0; k < np; k++) if (!params[k]) return RIMPHONY_EINVAL;
     if (n_ctx == 1) return rimphony_batch_compute_ex(ctxs[0], kind, n, s, theta, params, coeff_mask, precision, out, status, work);
 
     std::vector<int> rcs((size_t) n_ctx, RIMPHONY_OK);
@@ -1967,21 +1977,16 @@ extern "C" int rimphony_highfreq_batch(rimphony_ctx *c, int kind, size_t n, cons
     const int np = kind == RIMPHONY_POWER_LAW ? 2 : 1;       // only p and gamma_min (or T) enter the closed forms
     for (int k = 0; k < np; k++) if (!params[k]) return RIMPHONY_EINVAL;
     const size_t need_in = n * (size_t) (2 + np + 2);
-    if (c->in_cap < need_in) {
-        if (c->d_in) (void) hipFree(c->d_in);
-        c->d_in = nullptr; c->in_cap = 0;
-        if (hipMalloc(&c->d_in, need_in * sizeof(double)) != hipSuccess) return RIMPHONY_ENOMEM;
-        c->in_cap = need_in;
-    }
-    HIP_TRY(hipMemcpy(c->d_in, s, n * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(c->d_in + n, theta, n * sizeof(double), hipMemcpyHostToDevice));
+    { const int rcb = c->d_in.grow(need_in, need_in * sizeof(double), "the staged inputs"); if (rcb) return rcb; }
+    HIP_TRY(hipMemcpy(c->d_in.p, s, n * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(c->d_in.p + n, theta, n * sizeof(double), hipMemcpyHostToDevice));
     const double *dp[2] = { nullptr, nullptr };
     for (int k = 0; k < np; k++) {
-        HIP_TRY(hipMemcpy(c->d_in + (size_t) (2 + k) * n, params[k], n * sizeof(double), hipMemcpyHostToDevice));
-        dp[k] = c->d_in + (size_t) (2 + k) * n;
+        HIP_TRY(hipMemcpy(c->d_in.p + (size_t) (2 + k) * n, params[k], n * sizeof(double), hipMemcpyHostToDevice));
+        dp[k] = c->d_in.p + (size_t) (2 + k) * n;
     }
-    double *d_res = c->d_in + (size_t) (2 + np) * n;
-    const int rc = rimphony_highfreq_batch_device(c, kind, n, c->d_in, c->d_in + n, dp, d_res, nullptr);
+    double *d_res = c->d_in.p + (size_t) (2 + np) * n;
+    const int rc = rimphony_highfreq_batch_device(c, kind, n, c->d_in.p, c->d_in.p + n, dp, d_res, nullptr);
     if (rc) return rc;
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(out, d_res, n * 2 * sizeof(double), hipMemcpyDeviceToHost));
@@ -2019,7 +2024,7 @@ static int fill_point_args(int kind, const double *params, int coeff, int stokes
     return RIMPHONY_OK;
 }
 
-// normalisation of a single host-described point -> c->d_norm[0]
+// normalisation of a single host-described point -> c->d_norm.p[0]
 static int single_point_norm(rimphony_ctx *c, int kind, const double *params, hipStream_t st)
 {
     int rc = ensure_norm(c, 8);
@@ -2027,16 +2032,11 @@ static int single_point_norm(rimphony_ctx *c, int kind, const double *params, hi
     // params live in d_norm[1..5] as five 1-element SoA arrays
     double h[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
     for (int k = 0; k < NPARAMS[kind]; k++) h[1 + k] = params[k];
-    HIP_TRY(hipMemcpyAsync(c->d_norm, h, sizeof h, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(c->d_norm.p, h, sizeof h, hipMemcpyHostToDevice, st));
     HIP_TRY(hipStreamSynchronize(st));   // h is a stack buffer
     ParamPtrs pp;
-    for (int k = 0; k < 5; k++) pp.p[k] = c->d_norm + 1 + k;
-    switch (kind) {
-    case 0: return launch_norm<0>(c, 1, pp, c->d_norm, st);
-    case 1: return launch_norm<1>(c, 1, pp, c->d_norm, st);
-    case 2: return launch_norm<2>(c, 1, pp, c->d_norm, st);
-    default: return launch_norm<3>(c, 1, pp, c->d_norm, st);
-    }
+    for (int k = 0; k < 5; k++) pp.p[k] = c->d_norm.p + 1 + k;
+    return launch_norm(c, kind, 1, pp, c->d_norm.p, st);
 }
 
 template <int KIND>
@@ -2075,12 +2075,7 @@ extern "C" int rimphony_gamma_integrand_batch_device(rimphony_ctx *c, int kind, 
     rc = single_point_norm(c, kind, params, st);
     if (rc) return rc;
     const dim3 grid((unsigned) ((count + 63) / 64)), block(64);
-    switch (kind) {
-    case 0: hipLaunchKernelGGL(integrand_kernel_n<0>, grid, block, RIM_DYN_LDS, st, pa, c->d_norm, count, d_n, d_gamma, d_out); break;
-    case 1: hipLaunchKernelGGL(integrand_kernel_n<1>, grid, block, RIM_DYN_LDS, st, pa, c->d_norm, count, d_n, d_gamma, d_out); break;
-    case 2: hipLaunchKernelGGL(integrand_kernel_n<2>, grid, block, RIM_DYN_LDS, st, pa, c->d_norm, count, d_n, d_gamma, d_out); break;
-    default: hipLaunchKernelGGL(integrand_kernel_n<3>, grid, block, RIM_DYN_LDS, st, pa, c->d_norm, count, d_n, d_gamma, d_out); break;
-    }
+    rim_with_kind(kind, [&](auto K) { hipLaunchKernelGGL(integrand_kernel_n<decltype(K)::value>, grid, block, RIM_DYN_LDS, st, pa, c->d_norm.p, count, d_n, d_gamma, d_out); });
     HIP_TRY(hipGetLastError());
     return RIMPHONY_OK;
 }
@@ -2099,8 +2094,8 @@ int rim_wave_grid(rimphony_ctx *c, size_t count, int waves_per_cu, unsigned *gri
     *grid = persistent_grid(c, count, waves_per_cu);
     return ensure_spill(c, *grid);
 }
-const double *rim_ctx_norm(const rimphony_ctx *c) { return c->d_norm; }
-double *rim_ctx_spill(const rimphony_ctx *c) { return c->d_spill; }
+const double *rim_ctx_norm(const rimphony_ctx *c) { return c->d_norm.p; }
+double *rim_ctx_spill(const rimphony_ctx *c) { return c->d_spill.p; }
 
 extern "C" int rimphony_gamma_integral_batch_device(rimphony_ctx *c, int kind, const double *params,
                                                     int coeff, int stokes, int negative_lobe, double s, double theta,
@@ -2120,12 +2115,7 @@ extern "C" int rimphony_gamma_integral_batch_device(rimphony_ctx *c, int kind, c
     const unsigned grid = persistent_grid(c, count, 16);
     rc = ensure_spill(c, grid);
     if (rc) return rc;
-    switch (kind) {
-    case 0: hipLaunchKernelGGL(gamma_integral_kernel<0>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pa, c->d_norm, count, d_n, d_out, c->d_spill); break;
-    case 1: hipLaunchKernelGGL(gamma_integral_kernel<1>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pa, c->d_norm, count, d_n, d_out, c->d_spill); break;
-    case 2: hipLaunchKernelGGL(gamma_integral_kernel<2>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pa, c->d_norm, count, d_n, d_out, c->d_spill); break;
-    default: hipLaunchKernelGGL(gamma_integral_kernel<3>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pa, c->d_norm, count, d_n, d_out, c->d_spill); break;
-    }
+    rim_with_kind(kind, [&](auto K) { hipLaunchKernelGGL(gamma_integral_kernel<decltype(K)::value>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pa, c->d_norm.p, count, d_n, d_out, c->d_spill.p); });
     HIP_TRY(hipGetLastError());
     return RIMPHONY_OK;
 }
@@ -2221,7 +2211,7 @@ extern "C" int rimphony_qag_selftest_device(rimphony_ctx *c, size_t count, const
     rc = ensure_spill(c, grid);
     if (rc) return rc;
     hipLaunchKernelGGL(qag_selftest_kernel, dim3(grid), dim3(64), 0, (hipStream_t) stream, count, d_family, d_p0, d_p1,
-                       d_a, d_b, epsabs, epsrel, (int) limit, d_result, d_abserr, d_qstatus, d_size, c->d_spill);
+                       d_a, d_b, epsabs, epsrel, (int) limit, d_result, d_abserr, d_qstatus, d_size, c->d_spill.p);
     HIP_TRY(hipGetLastError());
     return RIMPHONY_OK;
 }

@@ -7,6 +7,7 @@
 #define RIMPHONY_INTERNAL_H
 
 #include <hip/hip_runtime.h>
+#include <type_traits>
 #include "../../include/rimphony_hip.h"
 #include "symphony_wave.h"
 
@@ -92,5 +93,27 @@ struct RimCtxScope {
 };
 const double *rim_ctx_norm(const rimphony_ctx *c);
 double *rim_ctx_spill(const rimphony_ctx *c);
+
+// The one place where a run-time distribution kind picks a template instantiation: f(std::integral_constant<int, K>{}).
+// Every entry has validated `kind` before, so anything else is kind 3.
+template <class F>
+auto rim_with_kind(int kind, F &&f)
+{
+    switch (kind) {
+    case 0: return f(std::integral_constant<int, 0>{});
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    default: return f(std::integral_constant<int, 3>{});
+    }
+}
+
+// Leaves the calling thread on the device it came with, whichever way the scope ends.
+struct RimDeviceScope {
+    int device;
+    RimDeviceScope() : device(-1) { if (hipGetDevice(&device) != hipSuccess) device = -1; }
+    ~RimDeviceScope() { if (device >= 0) (void) hipSetDevice(device); }
+    RimDeviceScope(const RimDeviceScope &) = delete;
+    RimDeviceScope &operator=(const RimDeviceScope &) = delete;
+};
 
 #endif

@@ -29,6 +29,9 @@ extern "C" int rimphony_batch_compute_multi_device(rimphony_ctx *const *ctxs, in
     if (!ctxs || n_ctx < 1 || n_ctx > 64 || !n_local || !d_s || !d_theta || !d_params || !d_out) return RIMPHONY_EINVAL;
     for (int r = 0; r < n_ctx; r++)
         if (!ctxs[r] || (n_local[r] && (!d_s[r] || !d_theta[r] || !d_params[r] || !d_out[r]))) return RIMPHONY_EINVAL;
+    // the launches and the waits below select one device after the other: whichever way the call ends, the caller stays
+    // on the device it came with
+    RimDeviceScope callers_device;
     // launches are asynchronous: every device is busy before the first one is waited for
     int launched = 0, launch_rc = RIMPHONY_OK;
     std::string launch_err;
@@ -51,8 +54,6 @@ extern "C" int rimphony_batch_compute_multi_device(rimphony_ctx *const *ctxs, in
         return launch_rc;
     }
     if (synchronize) {
-        int dev0 = 0;
-        HIP_TRY(hipGetDevice(&dev0));
         for (int r = 0; r < n_ctx; r++) {
             if (n_local[r] == 0) continue;
             int dev = -1;
@@ -61,7 +62,6 @@ extern "C" int rimphony_batch_compute_multi_device(rimphony_ctx *const *ctxs, in
             HIP_TRY(hipSetDevice(dev));
             HIP_TRY(hipStreamSynchronize(streams ? (hipStream_t) streams[r] : (hipStream_t) 0));
         }
-        HIP_TRY(hipSetDevice(dev0));
     }
     return RIMPHONY_OK;
 }
@@ -103,7 +103,11 @@ void rccl_load()
     const char *cands[4] = { getenv("RIMPHONY_RCCL_LIB"), "librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1" };
     for (int i = 0; i < 4 && !g_rccl.handle; i++)
         if (cands[i] && *cands[i]) g_rccl.handle = dlopen(cands[i], RTLD_NOW | RTLD_GLOBAL);
-    if (!g_rccl.handle) { g_rccl.why = std::string("loading librccl.so.1: ") + (dlerror() ? dlerror() : "not found"); return; }
+    if (!g_rccl.handle) {
+        const char *why = dlerror();        // (a second call returns null: the message is handed out once)
+        g_rccl.why = std::string("loading librccl.so.1: ") + (why ? why : "not found");
+        return;
+    }
 #define RCCL_SYM(field, type, name) g_rccl.field = (type) dlsym(g_rccl.handle, name); \
     if (!g_rccl.field) { g_rccl.why = std::string("librccl lacks ") + name; g_rccl.handle = nullptr; return; }
     RCCL_SYM(get_unique_id, fn_get_unique_id, "ncclGetUniqueId")

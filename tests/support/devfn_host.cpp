@@ -4,6 +4,7 @@
 // Not part of the product library.
 #include "../../rimphony_amd/csrc/dev_symphony.h"
 #include "../../rimphony_amd/csrc/dev_heyvaerts.h"
+#include "../../rimphony_amd/csrc/launch_plan.h"
 using namespace rim;
 extern "C" {
 double devh_bessel_j(double n, double x) { return bessel_j(n, x); }
@@ -39,5 +40,14 @@ double devh_hey_element(int kind, int stokes, double s, double cos_th, double si
     case 2: dist_prepare<2>(d, norm); return hey_element<2>(pt, d, hc, qr != 0, fixed, v);
     default: dist_prepare<3>(d, norm); return hey_element<3>(pt, d, hc, qr != 0, fixed, v);
     }
+}
+// the grid plan of a persistent launch (launch_plan.h): out = resident_per_cu, grid, early_squad, early_stride, early_classes
+void devh_plan_grid(int n_cu, unsigned long long ntasks, int occupancy_blocks, unsigned long long static_lds,
+                    unsigned long long dyn_lds, int waves, int shared_mode, int no_assist, unsigned want_squad, int early_help,
+                    long long out[5])
+{
+    const RimGridPlan p = rim_plan_grid(n_cu, ntasks, occupancy_blocks, (size_t) static_lds, (size_t) dyn_lds, waves,
+                                        shared_mode != 0, no_assist != 0, want_squad, early_help != 0);
+    out[0] = p.resident_per_cu; out[1] = p.grid; out[2] = p.early_squad; out[3] = p.early_stride; out[4] = p.early_classes;
 }
 }

@@ -195,6 +195,72 @@ def _detsincos(x):
     return s.value, c.value
 
 
+def test_grid_plan_of_the_persistent_launch():
+    """rim_plan_grid (launch_plan.h) is the integer arithmetic between "how many tasks" and "grid, squad, stride, classes"
+    of a persistent launch.  The expected values are worked out by hand from the launch code it replaced:
+    resident = min(occupancy or 4, 4 waves), lowered to (160 KB - 512) / roundup512(LDS) where that is smaller, quartered
+    (or 2) in shared mode; grid = min(CUs x resident, 64 x tasks -- tasks alone without the cooperative tail or beyond
+    2^40 --), at least 1; squad only with early help, the tail on, tasks >= 4 grid and grid >= 16 squad:
+    stride = (grid / squad) | 1, squad = min(squad, (grid - 1) / stride + 1), classes 4 / 2 / 1 from 256 / 128 waves."""
+    so = _build.build_test_support()
+    L = ctypes.CDLL(so)
+    L.devh_plan_grid.restype = None
+    L.devh_plan_grid.argtypes = ([ctypes.c_int, ctypes.c_ulonglong, ctypes.c_int, ctypes.c_ulonglong, ctypes.c_ulonglong] +
+                                 [ctypes.c_int] * 3 + [ctypes.c_uint, ctypes.c_int, ctypes.POINTER(ctypes.c_longlong)])
+
+    def plan(n_cu=256, ntasks=262144, occ=20, lds=7680, dyn=0, waves=5, shared=0, no_assist=0, squad=0, early=0):
+        out = (ctypes.c_longlong * 5)()
+        L.devh_plan_grid(n_cu, ntasks, occ, lds, dyn, waves, shared, no_assist, squad, early, out)
+        return tuple(out)          # resident_per_cu, grid, early_squad, early_stride, early_classes
+
+    # 7680 bytes = 15 granules: (163840 - 512) // 7680 = 21 such blocks fit a CU, the clamp is idle
+    assert plan() == (20, 5120, 0, 1, 1)
+    assert plan(squad=64) == (20, 5120, 0, 1, 1)                     # a kernel without the protocol has no squad
+    assert plan(squad=64, early=1) == (20, 5120, 64, 81, 1)          # stride (5120 // 64) | 1 = 81, fit 5119 // 81 + 1 = 64
+    assert plan(squad=256, early=1) == (20, 5120, 244, 21, 2)        # stride 20 | 1 = 21, fit 5119 // 21 + 1 = 244
+    assert plan(squad=128, early=1) == (20, 5120, 125, 41, 1)        # stride 40 | 1 = 41, fit 5119 // 41 + 1 = 125
+    # four classes need 256 waves after the fit: 448 CUs x 28 = 12544 = 256 x 49, stride 49, fit 12543 // 49 + 1 = 256
+    assert plan(n_cu=448, occ=28, waves=7, lds=0, squad=256, early=1, ntasks=1 << 20) == (28, 12544, 256, 49, 4)
+    assert plan(n_cu=512, occ=24, waves=6, lds=0, squad=256, early=1, ntasks=1 << 20) == (24, 12288, 251, 49, 2)   # 12287 // 49 + 1
+    # the launches of the bench (131072 rows x 2 tasks on an MI355X: 256 CUs) with what the runtime reported there
+    # (profiles/host_refactor_bench_ab.txt): the Symphony groups (occupancy 20, 7648 bytes of LDS, 5 waves) and the
+    # Faraday kernel (occupancy 20, 6560 bytes, 5 waves; squad 64 on the power-law table, 256 on the pitchy-kappa one)
+    assert plan(occ=20, lds=7648, waves=5) == (20, 5120, 0, 1, 1)
+    assert plan(occ=20, lds=6560, waves=5, squad=64, early=1) == (20, 5120, 64, 81, 1)
+    assert plan(occ=20, lds=6560, waves=5, squad=256, early=1) == (20, 5120, 244, 21, 2)
+    # the LDS clamp: 8192 bytes -> 163328 // 8192 = 19 < 20; one granule less (7680) -> 21, idle.  Static and dynamic
+    # LDS add up before the rounding: 7600 + 256 = 7856 -> 8192 as well
+    assert plan(lds=8192)[:2] == (19, 4864)
+    assert plan(lds=8191)[:2] == (19, 4864) and plan(lds=7681)[:2] == (19, 4864)
+    assert plan(lds=7680)[:2] == (20, 5120)
+    assert plan(lds=7600, dyn=256)[:2] == (19, 4864)
+    assert plan(lds=0)[:2] == (20, 5120)                             # LDS size not known: no clamp
+    assert plan(lds=200000)[:2] == (20, 5120)                        # (a block that fits no CU is not this function's to refuse)
+    # the occupancy answer capped at 4 waves per SIMD x the launch bounds; a failed query is one wave per SIMD
+    assert plan(occ=32, lds=512)[:2] == (20, 5120)
+    assert plan(occ=32, lds=512, waves=6)[:2] == (24, 6144)
+    assert plan(occ=0)[:2] == (4, 1024) and plan(occ=-1)[:2] == (4, 1024)
+    # shared mode: >= 8 is quartered, anything smaller becomes 2; never a squad
+    assert plan(shared=1, no_assist=1) == (5, 1280, 0, 1, 1)
+    assert plan(shared=1, no_assist=1, occ=8)[:2] == (2, 512)
+    assert plan(shared=1, no_assist=1, occ=7)[:2] == (2, 512)
+    assert plan(shared=1, no_assist=1, occ=0)[:2] == (2, 512)
+    assert plan(shared=1, squad=64, early=1)[2:] == (0, 1, 1)
+    # fewer tasks than waves: 64 waves per task (helpers from the start), capped by the device; one per task without the tail
+    assert plan(ntasks=10)[:2] == (20, 640)
+    assert plan(ntasks=80)[:2] == (20, 5120) and plan(ntasks=79)[:2] == (20, 5056)
+    assert plan(ntasks=10, no_assist=1)[:2] == (20, 10)
+    assert plan(ntasks=(1 << 40) + 1)[:2] == (20, 5120) and plan(ntasks=1 << 62)[:2] == (20, 5120)
+    assert plan(ntasks=0)[:2] == (20, 1) and plan(ntasks=0, no_assist=1)[:2] == (20, 1)
+    # the squad's conditions: tasks >= 4 grid, grid >= 16 squad, the tail on
+    assert plan(ntasks=4 * 5120, squad=64, early=1)[2:] == (64, 81, 1)
+    assert plan(ntasks=4 * 5120 - 1, squad=64, early=1)[2:] == (0, 1, 1)
+    assert plan(squad=320, early=1)[2:] == (302, 17, 4)              # 5120 = 16 x 320; stride 16 | 1, fit 5119 // 17 + 1 = 302
+    assert plan(squad=321, early=1)[2:] == (0, 1, 1)
+    assert plan(squad=64, early=1, no_assist=1)[2:] == (0, 1, 1)
+    assert plan(squad=0, early=1)[2:] == (0, 1, 1)
+
+
 def test_workload_is_deterministic_and_in_range():
     k1, m1, s1, t1, p1 = workload.make_batch("cfg2_powerlaw_jI_aI", 1000)
     k2, m2, s2, t2, p2 = workload.make_batch("cfg2_powerlaw_jI_aI", 500, start=500)
