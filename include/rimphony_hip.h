@@ -47,14 +47,17 @@ enum { RIMPHONY_EMISSION = 0, RIMPHONY_ABSORPTION = 1, RIMPHONY_FARADAY = 2 };
  *   POWER_LAW         p, gamma_min, gamma_max, gamma_cutoff          (power_law.rs:27-33, 82-87)
  *   THERMAL_JUETTNER  T                                              (thermal_juettner.rs:45-50)
  *   PITCHY_PL         p, k, gamma_min, gamma_max, gamma_cutoff       (pitchy_pl.rs:73-90)
- *   PITCHY_KAPPA      kappa, width, k, gamma_cutoff                  (pitchy_kappa.rs:70-85) */
+ *   PITCHY_KAPPA      kappa, width, k, gamma_cutoff                  (pitchy_kappa.rs:70-85)
+ *   TABULATED         table index (as a double)                      (the open DistributionFunction trait, lib.rs:111-146,
+ *                     as data: rimphony_ctx_set_tables below) */
 enum {
     RIMPHONY_POWER_LAW = 0,
     RIMPHONY_THERMAL_JUETTNER = 1,
     RIMPHONY_PITCHY_PL = 2,
-    RIMPHONY_PITCHY_KAPPA = 3
+    RIMPHONY_PITCHY_KAPPA = 3,
+    RIMPHONY_TABULATED = 4
 };
-int rimphony_dist_nparams(int dist_kind);   /* 4, 1, 5, 4; negative for an unknown kind */
+int rimphony_dist_nparams(int dist_kind);   /* 4, 1, 5, 4, 1; negative for an unknown kind */
 
 /* coeff_mask bits = output slots */
 #define RIMPHONY_SLOT_J_I      (1u << 0)
@@ -133,6 +136,27 @@ const char *rimphony_strerror(int code);
  * never prints. */
 const char *rimphony_last_error(void);
 const char *rimphony_version(void);
+
+/* Tabulated distributions (RIMPHONY_TABULATED): isotropic f(gamma) given as tables of ln n(gamma), n = dN/dgamma up to a
+ * constant factor -- the convention of the power law's gamma^-p exp(-gamma / gamma_cutoff); the normalisation
+ * 1 / (4 pi int n dgamma) over [gamma_lo, gamma_hi] is computed per row like every other kind's (power_law.rs:93-103).
+ *   log_n   HOST, [n_tables][n_nodes]: ln n at nodes uniform in ln gamma from ln gamma_lo to ln gamma_hi;
+ *           8 <= n_nodes <= 65536, 1 <= gamma_lo < gamma_hi, every value finite -- else RIMPHONY_EINVAL (checked on the host).
+ * Between the nodes the library evaluates the natural cubic spline in (ln gamma, ln n), so f and df/dgamma are smooth for
+ * the quadratures and a straight line -- a pure power law -- is reproduced exactly; f = norm n / (gamma^2 beta) inside the
+ * table, f = 0 outside (the rule of power_law.rs:38,49).  A table that ENDS at a non-negligible n therefore behaves like the
+ * power law's gamma limits: a step in f, on which the reference's quadratures report round-off (NaN) for part of the
+ * coefficients.  Taper the table so that n is negligible at both ends.
+ * A context holds one table set at a time: the call copies it to the device (the slopes of the splines are solved on the
+ * host, once), replaces the previous set and returns after the context's earlier work has finished; n_tables = 0 clears
+ * the set.  A row of a batch names its table by index (the kind's one parameter, a double); a row whose index is not an
+ * integer in [0, n_tables) gets a NaN normalisation: all its selected slots are NaN with RIMPHONY_ST_NORM_FAIL.  With no
+ * table set every entry refuses the kind with RIMPHONY_EINVAL.  In the _multi entries each context uses its OWN table
+ * set: give every context the same tables.  The kind runs one wave per coefficient (never the lock-step group kernels);
+ * RIMPHONY_PRECISION_F32_INTEGRAND is RIMPHONY_ENOTSUP and the high-frequency closed forms RIMPHONY_EINVAL, as for every
+ * kind without them. */
+int rimphony_ctx_set_tables(rimphony_ctx *ctx, size_t n_tables, size_t n_nodes, double gamma_lo, double gamma_hi,
+                            const double *log_n);
 
 /* Work counters of the most recent batch call on this context (device-side
  * counts, read back synchronously): integrand samples, wave-wide evaluation

@@ -42,6 +42,7 @@ pub const RIMPHONY_POWER_LAW: c_int = 0; // p, gamma_min, gamma_max, gamma_cutof
 pub const RIMPHONY_THERMAL_JUETTNER: c_int = 1; // T
 pub const RIMPHONY_PITCHY_PL: c_int = 2; // p, k, gamma_min, gamma_max, gamma_cutoff
 pub const RIMPHONY_PITCHY_KAPPA: c_int = 3; // kappa, width, k, gamma_cutoff
+pub const RIMPHONY_TABULATED: c_int = 4; // table index (the set: rimphony_ctx_set_tables)
 
 // coeff_mask bits = output slots, in the order of compute_all_dimensionless (lib.rs:176-177)
 pub const RIMPHONY_SLOT_J_I: u32 = 1 << 0;
@@ -86,6 +87,14 @@ extern "C" {
     pub fn rimphony_strerror(code: c_int) -> *const c_char;
     pub fn rimphony_last_error() -> *const c_char;
     pub fn rimphony_version() -> *const c_char;
+    pub fn rimphony_ctx_set_tables(
+        ctx: *mut rimphony_ctx,
+        n_tables: usize,
+        n_nodes: usize,
+        gamma_lo: c_double,
+        gamma_hi: c_double,
+        log_n: *const c_double,
+    ) -> c_int;
 
     pub fn rimphony_last_work(ctx: *mut rimphony_ctx, out: *mut rimphony_work) -> c_int;
     pub fn rimphony_last_tail(ctx: *mut rimphony_ctx, out: *mut u64) -> c_int;
@@ -195,6 +204,22 @@ impl HipContext {
 
     pub fn as_ptr(&self) -> *mut rimphony_ctx {
         self.raw
+    }
+
+    /// The context's table set for RIMPHONY_TABULATED: `log_n` holds n_tables rows of n_nodes values ln n(gamma) at
+    /// nodes uniform in ln gamma from gamma_lo to gamma_hi (include/rimphony_hip.h).  Replaces the previous set; an
+    /// empty `log_n` clears it.  This is how a user's own DistributionFunction (lib.rs:111-146) reaches the GPU.
+    pub fn set_tables(&self, n_nodes: usize, gamma_lo: f64, gamma_hi: f64, log_n: &[f64]) -> Result<(), String> {
+        if n_nodes == 0 || log_n.len() % n_nodes != 0 {
+            return Err(error_text(RIMPHONY_EINVAL));
+        }
+        let rc = unsafe {
+            rimphony_ctx_set_tables(self.raw, log_n.len() / n_nodes, n_nodes, gamma_lo, gamma_hi, log_n.as_ptr())
+        };
+        if rc != RIMPHONY_OK {
+            return Err(error_text(rc));
+        }
+        Ok(())
     }
 
     /// N x (full_calculation + compute_all_dimensionless): rows are

@@ -69,6 +69,7 @@ def build_hip(force=False, verbose=False):
         raise RuntimeError("hipcc not found: cannot build librimphony_hip.so")
     cmd = [hipcc] + HIPCC_FLAGS + [os.path.join(CSRC, "rimphony_hip.hip"), os.path.join(CSRC, "rimphony_diag.hip"),
                                     os.path.join(CSRC, "rimphony_group.hip"), os.path.join(CSRC, "rimphony_multi.hip"),
+                                    os.path.join(CSRC, "rimphony_tab.hip"),
                                     "-ldl", "-o", LIB]
     if verbose:
         print(" ".join(cmd))
@@ -93,4 +94,33 @@ def build_test_support():
         return out
     subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-math-errno",
                     "-mfma", "-msse4.1", "-shared", src, "-o", out], check=True)
+    return out
+
+
+# the oracle's calculators without its distribution file (oracle/Makefile: SRCS minus rimo_dist.c), and its flags
+TAB_ORACLE_C = ["rimo_quad.c", "rimo_bessel.c", "rimo_symphony.c", "rimo_heyvaerts.c", "rimo_highfreq.c"]
+ORACLE_CFLAGS = ["-O2", "-fPIC", "-ffp-contract=off", "-fno-math-errno", "-mfma", "-msse4.1", "-fopenmp"]
+
+
+def build_tab_oracle():
+    """The CPU oracle of the tabulated distribution (tests only): tests/support/tab_oracle.cpp supplies the three
+    distribution symbols the oracle's calculators call, on top of the host build of the device functions."""
+    import tempfile
+    src = os.path.join(ROOT, "tests", "support", "tab_oracle.cpp")
+    out = os.path.join(ROOT, "tests", "support", "liboracle_tab.so")
+    csrcs = [os.path.join(ORACLE_DIR, f) for f in TAB_ORACLE_C]
+    deps = [src] + csrcs + [os.path.join(ORACLE_DIR, f) for f in ("rimo.h", "rimo_math.h")] + \
+        [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
+    if _newer(out, deps):
+        return out
+    with tempfile.TemporaryDirectory() as tmp:
+        objs = []
+        for c in csrcs:
+            o = os.path.join(tmp, os.path.basename(c)[:-2] + ".o")
+            subprocess.run(["gcc"] + ORACLE_CFLAGS + ["-std=gnu11", "-c", c, "-o", o], check=True)
+            objs.append(o)
+        o = os.path.join(tmp, "tab_oracle.o")
+        subprocess.run(["g++"] + ORACLE_CFLAGS + ["-std=c++17", "-c", src, "-o", o], check=True)
+        objs.append(o)
+        subprocess.run(["g++", "-shared", "-fopenmp", "-Wl,-z,defs"] + objs + ["-o", out, "-lm"], check=True)
     return out

@@ -12,6 +12,8 @@ behaviour; see src/lib.rs of pkgw/rimphony):
   ThermalJuettnerDistribution(T).full_calculation()                    thermal_juettner.rs:45-72
   PitchyPowerLawDistribution(p, k).gamma_limits(..).full_calculation() pitchy_pl.rs:73-115
   PitchyKappaDistribution(kappa, width, k).gamma_cutoff(..)...         pitchy_kappa.rs:70-125
+  TabulatedDistribution(gamma_lo, gamma_hi, log_n)  the open DistributionFunction trait (lib.rs:111-146) as data: a table
+                                                    of ln n(gamma), spline-interpolated inside the integrand
 
 plus the batched compute() the north star adds: `compute_batch`.  PyTorch is
 used only as plumbing (device buffers, the current HIP stream).  Everything is
@@ -46,8 +48,9 @@ class Coefficient(enum.IntEnum):
     Faraday = 2
 
 
-POWER_LAW, THERMAL_JUETTNER, PITCHY_PL, PITCHY_KAPPA = 0, 1, 2, 3
-NPARAMS = {POWER_LAW: 4, THERMAL_JUETTNER: 1, PITCHY_PL: 5, PITCHY_KAPPA: 4}
+POWER_LAW, THERMAL_JUETTNER, PITCHY_PL, PITCHY_KAPPA, TABULATED = 0, 1, 2, 3, 4
+NPARAMS = {POWER_LAW: 4, THERMAL_JUETTNER: 1, PITCHY_PL: 5, PITCHY_KAPPA: 4, TABULATED: 1}
+TAB_MIN_NODES, TAB_MAX_NODES = 8, 65536
 
 # slot order of compute_all_dimensionless (lib.rs:176-177)
 SLOTS = [
@@ -65,6 +68,29 @@ PRECISION_F32_INTEGRAND = 1     # refused by the library (RIMPHONY_ENOTSUP): slo
 
 def slot_of(coeff, stokes):
     return SLOTS.index((Coefficient(coeff), Stokes(stokes)))
+
+
+def check_param_count(kind, params):
+    """The parameter arrays of a batch: one per parameter of the kind (TABULATED: one, the table index of each row)."""
+    if kind not in NPARAMS:
+        raise ValueError("unknown distribution kind %r" % (kind,))
+    if len(params) != NPARAMS[kind]:
+        raise ValueError("distribution kind %d takes %d parameter arrays, got %d" % (kind, NPARAMS[kind], len(params)))
+
+
+def check_tables(gamma_lo, gamma_hi, log_n):
+    """A table set as rimphony_ctx_set_tables accepts it -> contiguous float64 [n_tables][n_nodes]; ValueError for what the
+    library refuses with RIMPHONY_EINVAL (include/rimphony_hip.h)."""
+    t = np.ascontiguousarray(np.atleast_2d(np.asarray(log_n, dtype=np.float64)))
+    if t.ndim != 2 or t.shape[0] < 1:
+        raise ValueError("log_n: expected [n_nodes] or [n_tables][n_nodes]")
+    if not TAB_MIN_NODES <= t.shape[1] <= TAB_MAX_NODES:
+        raise ValueError("log_n: %d nodes, expected %d .. %d" % (t.shape[1], TAB_MIN_NODES, TAB_MAX_NODES))
+    if not (math.isfinite(gamma_lo) and math.isfinite(gamma_hi) and 1.0 <= gamma_lo < gamma_hi):
+        raise ValueError("expected 1 <= gamma_lo < gamma_hi, got %r, %r" % (gamma_lo, gamma_hi))
+    if not np.isfinite(t).all():
+        raise ValueError("log_n: every value must be finite (a table cannot hold n = 0: let it roll off instead)")
+    return t
 
 
 class Context:
@@ -101,6 +127,20 @@ class Context:
         t = torch.as_tensor(x, dtype=torch.float64)
         return t.to(self._dev()).contiguous()
 
+    # -- tabulated distributions ---------------------------------------------------
+    def set_tables(self, gamma_lo, gamma_hi, log_n):
+        """The context's table set for kind TABULATED: log_n [n_tables][n_nodes] (or [n_nodes]) = ln n(gamma) at nodes
+        uniform in ln gamma from gamma_lo to gamma_hi, n = dN/dgamma up to a factor.  Replaces the previous set; None
+        clears it.  Synchronous.  Let n roll off to a negligible value at both ends: a table that ends at a sizeable n is a
+        step in f, like the power law's gamma limits (include/rimphony_hip.h)."""
+        if log_n is None:
+            capi.check(self.lib.rimphony_ctx_set_tables(self.handle, 0, 0, 1.0, 2.0, None), "rimphony_ctx_set_tables")
+            return
+        t = check_tables(gamma_lo, gamma_hi, log_n)
+        capi.check(self.lib.rimphony_ctx_set_tables(self.handle, t.shape[0], t.shape[1], float(gamma_lo), float(gamma_hi),
+                                                    t.ctypes.data_as(ctypes.POINTER(ctypes.c_double))),
+                   "rimphony_ctx_set_tables")
+
     # -- batched compute() -------------------------------------------------------
     def _check_input(self, name, t, n):
         """The C ABI takes raw device pointers and cannot see what they point to: refuse anything but a contiguous
@@ -123,10 +163,7 @@ class Context:
         """s, theta: CUDA float64 tensors [n]; params: list of CUDA float64 tensors [n].
         Returns (out [n, 8] CUDA tensor, status [n, 8] int32 CUDA tensor or None) -- and, with want_work, a third
         element: [n, 8] int64 integrand samples spent per coefficient.  Asynchronous on the current stream."""
-        if kind not in NPARAMS:
-            raise ValueError("unknown distribution kind %r" % (kind,))
-        if len(params) != NPARAMS[kind]:
-            raise ValueError("distribution kind %d takes %d parameter arrays, got %d" % (kind, NPARAMS[kind], len(params)))
+        check_param_count(kind, params)
         if not isinstance(s, torch.Tensor):
             raise TypeError("s: expected a torch.Tensor, got %s" % type(s).__name__)
         n = s.numel()
@@ -636,3 +673,46 @@ class PitchyKappaDistribution(_DistributionFunction):
 
     def full_calculation(self, ctx=None):
         return FullSynchrotronCalculator(PITCHY_KAPPA, [self.kappa, self.width, self.k, self._gamma_cutoff], ctx)
+
+
+class TabulatedDistribution(_DistributionFunction):
+    """An isotropic distribution given as a table: log_n [n_nodes] = ln n(gamma) at nodes uniform in ln gamma from gamma_lo
+    to gamma_hi (n = dN/dgamma up to a factor; f = norm n / (gamma^2 beta) inside the table, 0 outside).  The library
+    interpolates with the natural cubic spline in (ln gamma, ln n).  The object installs its table as the context's table
+    set whenever it computes, so two of them can share a context in turn; a batch over several tables uses
+    Context.set_tables and kind TABULATED directly."""
+
+    def __init__(self, gamma_lo, gamma_hi, log_n):
+        self.gamma_lo, self.gamma_hi = float(gamma_lo), float(gamma_hi)
+        self.log_n = check_tables(self.gamma_lo, self.gamma_hi, np.asarray(log_n, dtype=np.float64).reshape(1, -1))
+
+    @classmethod
+    def from_function(cls, fn, gamma_lo, gamma_hi, n_nodes=4096):
+        """Tabulate n(gamma) = fn(gamma) (vectorised, positive) on n_nodes nodes uniform in ln gamma."""
+        gamma = np.exp(np.linspace(math.log(gamma_lo), math.log(gamma_hi), int(n_nodes)))
+        gamma[0], gamma[-1] = gamma_lo, gamma_hi
+        return cls(gamma_lo, gamma_hi, np.log(np.asarray(fn(gamma), dtype=np.float64)))
+
+    def _install(self, ctx):
+        ctx.set_tables(self.gamma_lo, self.gamma_hi, self.log_n)
+        return ctx
+
+    def _kind_params(self):
+        return TABULATED, [0.0]
+
+    def _calc(self, gamma, cos_xi):
+        self._install(self.ctx or default_context())
+        return super()._calc(gamma, cos_xi)
+
+    def full_calculation(self, ctx=None):
+        return _TabulatedCalculator(self, ctx)
+
+
+class _TabulatedCalculator(FullSynchrotronCalculator):
+    def __init__(self, dist, ctx=None):
+        super().__init__(TABULATED, [0.0], ctx)
+        self.dist = dist
+
+    def _run(self, s, theta, mask):
+        self.dist._install(self.ctx)
+        return super()._run(s, theta, mask)

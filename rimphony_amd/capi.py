@@ -20,6 +20,7 @@ SYMBOLS = [
     "rimphony_hey_element_batch_device", "rimphony_hey_outer_batch_device", "rimphony_last_tail", "rimphony_deriv_probe_batch_device",
     "rimphony_ctx_device", "rimphony_batch_compute_multi_device", "rimphony_rccl_available", "rimphony_rccl_unique_id",
     "rimphony_rccl_comm_create", "rimphony_rccl_comm_destroy", "rimphony_rccl_gather_table",
+    "rimphony_ctx_set_tables",
 ]
 
 
@@ -151,6 +152,9 @@ def load():
         lib.rimphony_rccl_gather_table.restype = c_int
         lib.rimphony_rccl_gather_table.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_size_t, c_void_p, c_void_p,
                                                    c_void_p, c_void_p]
+    if hasattr(lib, "rimphony_ctx_set_tables"):
+        lib.rimphony_ctx_set_tables.restype = c_int
+        lib.rimphony_ctx_set_tables.argtypes = [c_void_p, c_size_t, c_size_t, c_double, c_double, dp]
     _lib = lib
     return lib
 

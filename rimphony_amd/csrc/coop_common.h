@@ -17,6 +17,14 @@ struct AssistSlot;
 template <int KIND>
 __device__ inline void load_params(const ParamPtrs &pp, size_t i, DistParams &d)
 {
+    if (KIND == DIST_TABULATED) {
+        // one parameter, the table index; p[1] is not a parameter array but the context's table set (dev_symphony.h,
+        // dist_prepare: its address travels in par[1])
+        d.par[0] = pp.p[0][i];
+        d.par[1] = rim_frombits((uint64_t) (uintptr_t) pp.p[1]);
+        d.par[2] = 0.; d.par[3] = 0.; d.par[4] = 0.;
+        return;
+    }
     constexpr int NP = (KIND == DIST_POWER_LAW) ? 4 : (KIND == DIST_THERMAL_JUETTNER) ? 1 : (KIND == DIST_PITCHY_PL) ? 5 : 4;
 #pragma unroll
     for (int k = 0; k < 5; k++) d.par[k] = (k < NP) ? pp.p[k][i] : 0.;

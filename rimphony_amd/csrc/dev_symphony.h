@@ -1,5 +1,5 @@
 // dev_symphony.h -- per-sample device functions of the Symphony path:
-// the four distribution functions and gamma_integrand.
+// the distribution functions (four analytic ones and the tabulated one) and gamma_integrand.
 //
 //   DistributionFunction::calc_f / calc_f_derivatives
 //       power_law.rs:36-62, thermal_juettner.rs:29-39, pitchy_pl.rs:32-64,
@@ -13,17 +13,18 @@
 #ifndef RIM_DEV_SYMPHONY_H
 #define RIM_DEV_SYMPHONY_H
 
+#include <stddef.h>
 #include "dev_bessel.h"
 
 namespace rim {
 
-enum { DIST_POWER_LAW = 0, DIST_THERMAL_JUETTNER = 1, DIST_PITCHY_PL = 2, DIST_PITCHY_KAPPA = 3 };
+enum { DIST_POWER_LAW = 0, DIST_THERMAL_JUETTNER = 1, DIST_PITCHY_PL = 2, DIST_PITCHY_KAPPA = 3, DIST_TABULATED = 4 };
 enum { STOKES_I = 0, STOKES_Q = 1, STOKES_V = 2 };
 enum { COEFF_EMISSION = 0, COEFF_ABSORPTION = 1, COEFF_FARADAY = 2 };
 
 // Distribution parameters of one point (wave-uniform).  par[] follows the C ABI:
 //   power_law {p, gmin, gmax, gcut}; thermal {T}; pitchy_pl {p, k, gmin, gmax, gcut};
-//   pitchy_kappa {kappa, width, k, gcut}.
+//   pitchy_kappa {kappa, width, k, gcut}; tabulated {table index} (the other fields: dist_prepare<DIST_TABULATED>).
 struct DistParams {
     double par[5];
     double inv_gamma_cutoff;
@@ -32,9 +33,41 @@ struct DistParams {
     double norm;
 };
 
+// ---- tabulated distribution: a table set in memory (rim_tab_build of tab_spline.h lays it out) ----
+// TAB_HDR_DOUBLES header words, then [n_tables][n_nodes][2] = {y_j = ln n(gamma_j), m_j = dy/du at the node} of the natural
+// cubic spline in u = ln gamma; the nodes are uniform in u.
+enum { TAB_HDR_NTABLES = 0, TAB_HDR_NNODES = 1, TAB_HDR_GLO = 2, TAB_HDR_GHI = 3, TAB_HDR_ULO = 4, TAB_HDR_INVH = 5, TAB_HDR_H = 6,
+       TAB_HDR_DOUBLES = 8 };
+
+// is `idx` (par[0] of a row) the index of a table of the set?
+RIM_DEV bool tab_row_ok(const double *hdr, double idx)
+{
+    return idx >= 0. && idx < hdr[TAB_HDR_NTABLES] && (double) (long long) idx == idx;
+}
+
 template <int KIND>
 RIM_DEV void dist_prepare(DistParams &d, double norm)
 {
+    if (KIND == DIST_TABULATED) {
+        // In: par[0] the table index, par[1] the bit pattern of the table set's address.  The kind has one parameter, so the
+        // fields the others use carry what a sample needs (DistParams does not grow): par[1] the bit pattern of the row's
+        // address, par[2] u_lo, par[3] 1 / h, par[4] the index of the last interval; inv_gamma_cutoff h, inv_kappa_width
+        // gamma_lo, neg_inverse_t gamma_hi.  A row whose index names no table keeps table 0 (every read stays inside the
+        // set) and gets a NaN normalisation.
+        const double *hdr = (const double *) (uintptr_t) rim_bits(d.par[1]);
+        const bool ok = tab_row_ok(hdr, d.par[0]);
+        const size_t nn = (size_t) hdr[TAB_HDR_NNODES];
+        const size_t row = ok ? (size_t) d.par[0] : 0;
+        d.par[1] = rim_frombits((uint64_t) (uintptr_t) (hdr + TAB_HDR_DOUBLES + row * nn * 2));
+        d.par[2] = hdr[TAB_HDR_ULO];
+        d.par[3] = hdr[TAB_HDR_INVH];
+        d.par[4] = (double) (nn - 2);
+        d.inv_gamma_cutoff = hdr[TAB_HDR_H];
+        d.inv_kappa_width = hdr[TAB_HDR_GLO];
+        d.neg_inverse_t = hdr[TAB_HDR_GHI];
+        d.norm = ok ? norm : RIM_NAN;
+        return;
+    }
     d.inv_gamma_cutoff = 0.;
     d.inv_kappa_width = 0.;
     d.neg_inverse_t = 0.;
@@ -64,10 +97,58 @@ RIM_DEV double kappa_gamma_term(const DistParams &d, double gamma)
     return rim_pow(base, y) * RimMath<PREC>::exp(-gamma * d.inv_gamma_cutoff);
 }
 
+// The spline H(u) of a tabulated distribution and dH/du at u = ln gamma: cubic Hermite on the interval of the node values
+// and slopes, which a lane reads as four consecutive doubles.  gamma outside the table only ever gets here as a NaN (the
+// callers return 0 there first): the interval index is formed from a clamped copy, so every read stays inside the row.
+RIM_DEV void tab_spline(const DistParams &d, double gamma, double &hval, double &dhdu)
+{
+    const double *row = (const double *) (uintptr_t) rim_bits(d.par[1]);
+    const double x = (rim_log(gamma) - d.par[2]) * d.par[3];
+    double xc = x;
+    if (!(xc >= 0.)) xc = 0.;
+    if (xc > d.par[4]) xc = d.par[4];
+    const long long j = (long long) xc;
+    const double t = x - (double) j;
+    const double *q = row + 2 * j;
+    const double y0 = q[0], m0 = q[1], y1 = q[2], m1 = q[3];
+    const double h = d.inv_gamma_cutoff;
+    const double b0 = h * m0, b1 = h * m1, dy = y1 - y0;
+    const double c2 = 3. * dy - 2. * b0 - b1;
+    const double c3 = b0 + b1 - 2. * dy;
+    hval = rim_fma(t, rim_fma(t, rim_fma(t, c3, c2), b0), y0);
+    dhdu = rim_fma(t, rim_fma(t, 3. * c3, 2. * c2), b0) * d.par[3];
+}
+
+// n(gamma) = exp(H(ln gamma)) of the table: the integrand of the normalisation (power_law.rs:95-96 for a table)
+RIM_DEV double tab_norm_integrand(const DistParams &d, double g)
+{
+    double hval, dhdu;
+    tab_spline(d, g, hval, dhdu);
+    return rim_exp(hval);
+}
+
+// calc_f and calc_f_derivatives of the tabulated distribution (isotropic: d f / d cos xi = 0), one body for all three
+// entries below: f = norm n(gamma) / (gamma^2 beta), 0 outside the table (the rule of power_law.rs:38,49).
+RIM_DEV void tab_calc_f_both(const DistParams &d, double gamma, double &f, double &dfdg)
+{
+    f = 0.; dfdg = 0.;
+    if (gamma < d.inv_kappa_width || gamma > d.neg_inverse_t) return;
+    double hval, dhdu;
+    tab_spline(d, gamma, hval, dhdu);
+    const double beta = rim_sqrt(1. - rim_div_moderate(1., gamma * gamma));
+    f = d.norm * rim_exp(hval) / (gamma * gamma * beta);
+    dfdg = f * (dhdu / gamma - 1. / gamma - gamma / (gamma * gamma - 1.));
+}
+
 template <int KIND, int PREC = 0>
 RIM_DEV double calc_f(const DistParams &d, double gamma, double cos_xi)
 {
     typedef RimMath<PREC> M;
+    if (KIND == DIST_TABULATED) {
+        double f, dfdg;
+        tab_calc_f_both(d, gamma, f, dfdg);
+        return f;
+    }
     if (KIND == DIST_POWER_LAW) {
         if (gamma < d.par[1] || gamma > d.par[2]) return 0.;
         RIM_HIT(19);
@@ -94,6 +175,12 @@ template <int KIND, int PREC = 0>
 RIM_DEV void calc_f_derivatives(const DistParams &d, double gamma, double cos_xi, double &dfdg, double &dfdcx)
 {
     typedef RimMath<PREC> M;
+    if (KIND == DIST_TABULATED) {
+        double f;
+        tab_calc_f_both(d, gamma, f, dfdg);
+        dfdcx = 0.;
+        return;
+    }
     if (KIND == DIST_POWER_LAW) {
         if (gamma < d.par[1] || gamma > d.par[2]) { dfdg = 0.; dfdcx = 0.; return; }
         RIM_HIT(20);
@@ -285,7 +372,7 @@ RIM_DEV double gamma_integrand_f_term(int coeff, const DistParams &d, double cos
     double dfdg, dfdcx;
     RIM_HIT(25);
     calc_f_derivatives<KIND, PREC>(d, gamma, cos_xi, dfdg, dfdcx);
-    if (KIND == DIST_POWER_LAW || KIND == DIST_THERMAL_JUETTNER) {
+    if (KIND == DIST_POWER_LAW || KIND == DIST_THERMAL_JUETTNER || KIND == DIST_TABULATED) {
         // dfdcx is the constant +0 (isotropic distributions): dfdcx_factor * dfdcx is a zero with the sign of the
         // factor (a NaN only where the sample is a NaN through cos_xi anyway), and for gamma > 0 the factor
         // (beta cos_th - cos_xi) / (gamma - 1 / gamma) has the sign of (beta cos_th - cos_xi) (gamma - 1): the
@@ -304,6 +391,11 @@ RIM_DEV double gamma_integrand_f_term(int coeff, const DistParams &d, double cos
 template <int KIND>
 RIM_DEV void calc_f_both(const DistParams &d, double gamma, double cos_xi, double &f, double &dfdg, double &dfdcx)
 {
+    if (KIND == DIST_TABULATED) {
+        tab_calc_f_both(d, gamma, f, dfdg);
+        dfdcx = 0.;
+        return;
+    }
     if (KIND == DIST_POWER_LAW) {
         f = 0.; dfdg = 0.; dfdcx = 0.;
         if (gamma < d.par[1] || gamma > d.par[2]) return;
@@ -351,7 +443,7 @@ RIM_DEV void gamma_integrand_f_terms(const DistParams &d, double cos_th, const G
     double dfdg, dfdcx;
     RIM_HIT(24); RIM_HIT(25);
     calc_f_both<KIND>(d, gamma, cos_xi, f_em, dfdg, dfdcx);
-    if (KIND == DIST_POWER_LAW || KIND == DIST_THERMAL_JUETTNER) {
+    if (KIND == DIST_POWER_LAW || KIND == DIST_THERMAL_JUETTNER || KIND == DIST_TABULATED) {
         f_ab = dfdg + ((beta * cos_th - cos_xi) * dfdcx) * (gamma - 1.);       // (gamma_integrand_f_term says why)
     } else {
         const double dfdcx_factor = (beta * cos_th - cos_xi) / (gamma - 1. / gamma);

@@ -95,7 +95,8 @@ const double *rim_ctx_norm(const rimphony_ctx *c);
 double *rim_ctx_spill(const rimphony_ctx *c);
 
 // The one place where a run-time distribution kind picks a template instantiation: f(std::integral_constant<int, K>{}).
-// Every entry has validated `kind` before, so anything else is kind 3.
+// Every entry has validated `kind` before, so anything else is kind 3 (kind 4, the tabulated distribution, never gets here:
+// rim_with_kind5, and rimphony_tab.hip for the kernels of coop_kernel.h).
 template <class F>
 auto rim_with_kind(int kind, F &&f)
 {
@@ -105,6 +106,15 @@ auto rim_with_kind(int kind, F &&f)
     case 2: return f(std::integral_constant<int, 2>{});
     default: return f(std::integral_constant<int, 3>{});
     }
+}
+
+// The same for the translation units that also serve the tabulated distribution (kind 4).  rimphony_group.hip keeps
+// the four-way form: its kernels exist for the four analytic kinds only.
+template <class F>
+auto rim_with_kind5(int kind, F &&f)
+{
+    if (kind == 4) return f(std::integral_constant<int, 4>{});
+    return rim_with_kind(kind, f);
 }
 
 // Leaves the calling thread on the device it came with, whichever way the scope ends.

@@ -10,6 +10,7 @@
 //   ThermalJuettnerDistribution::new(t).full_calculation(..)             thermal_juettner.rs:45-72
 //   PitchyPowerLawDistribution::new(p,k).gamma_limits(..)...             pitchy_pl.rs:73-115
 //   PitchyKappaDistribution::new(kappa,width,k).gamma_cutoff(..)...      pitchy_kappa.rs:70-125
+//   TabulatedDistribution(gamma_lo, gamma_hi, log_n)                     the open trait of lib.rs:111-146, as a table
 //   trait DistributionFunction { calc_f, calc_f_derivatives }            lib.rs:111-146
 //
 // plus the batched entry the GPU path exists for: BatchCalculator::compute().
@@ -62,6 +63,14 @@ public:
     // true when another context (this process or another) already owned the device at creation: the persistent grids are
     // then a quarter of the device and the cooperative tail is off (include/rimphony_hip.h, "context")
     bool shared_mode() const { return rimphony_ctx_shared_mode(ctx_) != 0; }
+    // The context's table set for RIMPHONY_TABULATED (include/rimphony_hip.h): log_n = ln n(gamma), [n_tables][n_nodes]
+    // row-major, at nodes uniform in ln gamma from gamma_lo to gamma_hi.  Replaces the previous set; n_tables = 0 clears it.
+    void set_tables(size_t n_tables, size_t n_nodes, double gamma_lo, double gamma_hi, const std::vector<double> &log_n) const
+    {
+        if (log_n.size() != n_tables * n_nodes) throw std::runtime_error("set_tables: log_n must hold n_tables * n_nodes values");
+        check(rimphony_ctx_set_tables(ctx_, n_tables, n_nodes, gamma_lo, gamma_hi, n_tables ? log_n.data() : nullptr),
+              "rimphony_ctx_set_tables");
+    }
 private:
     rimphony_ctx *ctx_ = nullptr;
 };
@@ -280,6 +289,33 @@ public:
     { return FullSynchrotronCalculator(std::move(ctx), RIMPHONY_PITCHY_KAPPA, {kappa_, width_, k_, gcut_}); }
 private:
     double kappa_, width_, k_, gcut_ = 1e10;
+};
+
+// An isotropic distribution given as a table of ln n(gamma) at nodes uniform in ln gamma (n = dN/dgamma up to a factor;
+// the library interpolates with the natural cubic spline in (ln gamma, ln n); f = 0 outside the table, so let n roll off
+// to a negligible value at both ends).  A context holds ONE table set at a time: calc_f, calc_f_derivatives and
+// full_calculation install this object's table in the context they are given, and the calculator computes with whatever
+// set the context holds when it is used -- call install() again after another table has used the context.
+class TabulatedDistribution : public DistributionFunction {
+protected:
+    int abi_kind() const override { return RIMPHONY_TABULATED; }
+    std::vector<double> abi_params() const override { return {0.}; }      // the table index
+public:
+    TabulatedDistribution(double gamma_lo, double gamma_hi, std::vector<double> log_n)
+        : glo_(gamma_lo), ghi_(gamma_hi), log_n_(std::move(log_n)) {}
+    void install(const Context &ctx) const { ctx.set_tables(1, log_n_.size(), glo_, ghi_, log_n_); }
+    double calc_f(const Context &ctx, double gamma, double cos_xi) const
+    { install(ctx); return DistributionFunction::calc_f(ctx, gamma, cos_xi); }
+    std::array<double, 2> calc_f_derivatives(const Context &ctx, double gamma, double cos_xi) const
+    { install(ctx); return DistributionFunction::calc_f_derivatives(ctx, gamma, cos_xi); }
+    FullSynchrotronCalculator full_calculation(std::shared_ptr<Context> ctx) const
+    {
+        install(*ctx);
+        return FullSynchrotronCalculator(std::move(ctx), RIMPHONY_TABULATED, {0.});
+    }
+private:
+    double glo_, ghi_;
+    std::vector<double> log_n_;
 };
 
 }  // namespace rimphony

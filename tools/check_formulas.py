@@ -477,7 +477,7 @@ def main():
 
     # ================= normalisation integrands and norm = 1 / (4 pi [pa] int) =================
     g = pos("g")
-    hip = read(ROOT, "rimphony_amd", "csrc", "rimphony_hip.hip")
+    hip = read(ROOT, "rimphony_amd", "csrc", "coop_kernel.h")      # (norm_kernel and its integrands: instantiated by rimphony_hip.hip)
     nenv = base_env({"g": g, "p": p, "par0": p, "inv_gamma_cutoff": gcut_inv, "inv_kappa_width": ikw, "kappa": kappa, "TWO_PI": 2 * sp.pi,
                      "RIM_TWO_PI": 2 * sp.pi})
     def closure(src, start):
