@@ -307,6 +307,19 @@ RIM_DEV void sym_bessel_pair(const SymOrder &so, double z, double &jn, double &d
     djn = n * jn / z - jnp1;
 }
 
+// The same pair from the complete functions of the Bessel seam (bessel_j / bessel_dj: any z, as the reference's
+// pkgw_bessel_j / pkgw_bessel_dj).  sym_bessel_pair above covers what the kinematics allow, z <= n (and z <= 5e4 below
+// order 30), and answers NaN beyond; where both are defined they return the same bits.  Selected by the type of the
+// order record, so that gamma_integrand_shared is one text for both.
+struct SymOrderFull { double n; };
+
+template <int PREC = 0>
+RIM_DEV void sym_bessel_pair(const SymOrderFull &so, double z, double &jn, double &djn)
+{
+    jn = bessel_j(so.n, z);
+    djn = bessel_dj(so.n, z);
+}
+
 // gamma_integrand (symphony.rs:398-479) in three pieces, so that the coefficients of one parameter point can share
 // the part that depends on (s, theta, n, gamma) only -- the kinematics and the Bessel pair, symphony.rs:406-442 -- and
 // differ in the polarisation term (:444-448) and the distribution term (:455-463): symphony_group.h.
@@ -315,8 +328,9 @@ struct GiShared {
     double mj, njp;             // M J_n(z), N J'_n(z)
 };
 
-template <int PREC = 0>
-RIM_DEV GiShared gamma_integrand_shared(double s, double cos_th, double sin_th, const SymOrder &so, double gamma)
+// ORDER: SymOrder, or SymOrderFull for the complete functions of the Bessel seam (sym_bessel_pair above).
+template <int PREC = 0, class ORDER = SymOrder>
+RIM_DEV GiShared gamma_integrand_shared(double s, double cos_th, double sin_th, const ORDER &so, double gamma)
 {
     const double n = so.n;
 
@@ -451,10 +465,10 @@ RIM_DEV void gamma_integrand_f_terms(const DistParams &d, double cos_th, const G
     }
 }
 
-template <int KIND, int PREC = 0>
-RIM_DEV double gamma_integrand(const SymPoint &pt, const DistParams &d, const SymOrder &so, double gamma)
+template <int KIND, int PREC = 0, class ORDER = SymOrder>
+RIM_DEV double gamma_integrand(const SymPoint &pt, const DistParams &d, const ORDER &so, double gamma)
 {
-    const GiShared sh = gamma_integrand_shared<PREC>(pt.s, pt.cos_th, pt.sin_th, so, gamma);
+    const GiShared sh = gamma_integrand_shared<PREC, ORDER>(pt.s, pt.cos_th, pt.sin_th, so, gamma);
     RIM_PROF_T(t_f);
     const double pol_term = gamma_integrand_pol_term(pt.stokes, sh.mj, sh.njp);
     const double f_term = gamma_integrand_f_term<KIND, PREC>(pt.coeff, d, pt.cos_th, sh);

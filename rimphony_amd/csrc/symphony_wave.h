@@ -287,6 +287,7 @@ __device__ __forceinline__ void sym_eval_pair(const SymPoint &pt, const DistPara
     const GammaLimits L = gamma_limits(pt, n_l, second ? lobe1 : lobe0);
     wv_sync();                       // nobody is still reading the previous requests' records
     if ((lane & 30) == 0) qpark->ord[(lane >> 4) | (lane & 1)] = ord_mine;          // lanes 0, 1, 32, 33 -> records 0, 1, 2, 3
+    if (lane == 0) { qpark->nan_sample = 0; qpark->ctr_save = qpark->ctr; }
     wv_sync();
     const double a0 = readlane_d(L.g0, 0), b0 = readlane_d(L.g1, 0);
     const double a1 = readlane_d(L.g0, 32), b1 = readlane_d(L.g1, 32);
@@ -301,10 +302,28 @@ __device__ __forceinline__ void sym_eval_pair(const SymPoint &pt, const DistPara
         so.n = second ? n1 : n0;
         so.small = (fl & 1) != 0; so.np1_small = (fl & 2) != 0; so.dj_nan = (fl & 4) != 0;
         so.o = qpark->ord + (second ? 2 : 0);
-        return active ? gamma_integrand<KIND, PREC>(pt, dist, so, x) : 0.;
+        const double v = active ? gamma_integrand<KIND, PREC>(pt, dist, so, x) : 0.;
+        if (v != v) qpark->nan_sample = 1;
+        return v;
     };
     int qs0, qs1;
     wave_qag_pair(f, g, inner, a0, b0, a1, b1, have1, false, 0., 1e-3, 5000, qpark, val0, qs0, val1, qs1);
+    wv_sync();
+    if (uni(qpark->nan_sample)) {
+        // A NaN sample.  The kinematics keep z below n, and sym_bessel_pair only covers that; but at |cos theta| ~ 1e-16
+        // gamma sin xi is the difference of two numbers of 1e33 -- rounding noise, z = 1e9 at n = 11 -- and there the
+        // reference still gets a number from pkgw_bessel_j where sym_bessel_pair has none.  Off the hot path: the
+        // request is evaluated again, every sample through the complete functions (the same bits wherever both are
+        // defined, so a NaN that is the reference's own comes back as it was), and the counters forget the first attempt.
+        if (lane == 0) qpark->ctr = qpark->ctr_save;
+        wv_sync();
+        auto f_full = [&](double x, bool active, bool second) __attribute__((always_inline)) -> double {
+            SymOrderFull so;
+            so.n = second ? n1 : n0;
+            return active ? gamma_integrand<KIND, PREC, SymOrderFull>(pt, dist, so, x) : 0.;
+        };
+        wave_qag_pair(f_full, g, inner, a0, b0, a1, b1, have1, false, 0., 1e-3, 5000, qpark, val0, qs0, val1, qs1);
+    }
     if (qs0 != QAG_SUCCESS) {
         val0 = RIM_NAN;
         st0 |= ST_INNER_FAIL;

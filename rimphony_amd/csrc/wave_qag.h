@@ -494,6 +494,8 @@ struct QagParkBase {
 // (SymOrder); the Heyvaerts kernel spends that LDS on the head of its series divisor table instead
 struct QagPark : QagParkBase {
     LeungOrder ord[4];
+    WaveCounters ctr_save;    // the counters before the gamma-integrals in flight, and whether one of their samples was a NaN
+    int nan_sample;           // (sym_eval_pair evaluates such a request again with the complete Bessel functions)
 };
 
 // Diagnostics: make a word visible to the host while the kernel is still running.

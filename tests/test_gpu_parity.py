@@ -12,6 +12,7 @@ import pytest
 
 import oracle_bind
 from rimphony_amd import workload
+from seam_inputs import harmonic_samples, hey_outer_abscissae, hey_seam_inputs
 
 pytestmark = pytest.mark.gpu
 
@@ -115,15 +116,7 @@ def test_gamma_integrand_bit_exact(gpu_ctx, oracle, kind):
         s = float(np.exp(rng.uniform(math.log(.1), math.log(1e6))))
         th = float(rng.uniform(0.01, 1.55))
         coeff, stokes = int(rng.integers(0, 2)), int(rng.integers(0, 3))
-        M = 3000
-        nmin = s * abs(math.sin(th))
-        n = nmin + 1 + np.exp(rng.uniform(-3, 12, M))
-        n = np.where(rng.random(M) < 0.5, np.floor(n), n)
-        nos = n / s
-        root = np.sqrt(np.maximum(nos * nos - math.sin(th) ** 2, 0))
-        gm = (nos - abs(math.cos(th)) * root) / math.sin(th) ** 2
-        gp = (nos + abs(math.cos(th)) * root) / math.sin(th) ** 2
-        g = gm + (gp - gm) * rng.random(M)
+        n, g = harmonic_samples(rng, s, th, 3000)
         got = gpu_ctx.gamma_integrand_batch(kind, par, coeff, stokes, s, th, n, g)
         ref = np.array([oracle.rimo_gamma_integrand(d, coeff, stokes, s, th, a, b) for a, b in zip(n, g)])
         report_mismatch("gamma_integrand kind %d" % kind, got, ref, lambda i: (par, s, th, coeff, stokes, n[i], g[i]))
@@ -647,27 +640,6 @@ HEY_SEAM_POINTS = [   # (kind, params, s, theta): sigma0 = s sin(theta) spans th
 ]
 
 
-def _hey_qr_start(sigma0):
-    """Where the quasi-resonant region begins: both pomega_max expressions of heyvaerts.rs:262-296 are real."""
-    return max(sigma0, 3 ** -0.5 * sigma0 ** 1.5)
-
-
-def _hey_seam_inputs(rng, s, th, qr, n):
-    """(fixed, v) inside the integration domains of heyvaerts.rs:213-296: non-resonant -- fixed = pomega, v = sigma in
-    [sigma_min, sigma_max]; quasi-resonant -- fixed = sigma >= sigma0, v = pomega in [-pomega_max, pomega_max]."""
-    sigma0 = s * math.sin(th)
-    if not qr:
-        pomega = rng.uniform(-1., 1., n) * np.exp(rng.uniform(math.log(3.), math.log(3e3), n)) * max(sigma0, 1.)
-        smin = np.sqrt(pomega ** 2 + sigma0 ** 2)
-        smax = np.maximum(3 ** -0.5 * smin ** 1.5, smin)
-        return pomega, smin + (smax - smin) * rng.random(n)
-    sigma = _hey_qr_start(sigma0) * (1. + np.exp(rng.uniform(math.log(1e-3), math.log(3e2), n)))
-    with np.errstate(invalid="ignore"):
-        pmax = np.fmin(np.sqrt(3 ** (2. / 3.) * sigma ** (4. / 3.) - sigma0 ** 2), np.sqrt(sigma ** 2 - sigma0 ** 2))
-    pmax = np.nan_to_num(pmax, nan=0.)
-    return sigma, pmax * rng.uniform(-1., 1., n)
-
-
 @pytest.mark.parametrize("case", range(len(HEY_SEAM_POINTS)))
 def test_heyvaerts_elements_bit_exact(gpu_ctx, oracle, case):
     """h_qr / h_nr / f_qr / f_nr_element (heyvaerts.rs:302-468), the inner integrands of the Faraday double integral,
@@ -678,7 +650,7 @@ def test_heyvaerts_elements_bit_exact(gpu_ctx, oracle, case):
     assert st == 0
     for stokes in (1, 2):
         for qr in (0, 1):
-            fixed, v = _hey_seam_inputs(rng, s, th, qr, 1536)
+            fixed, v = hey_seam_inputs(rng, s, th, qr, 1536)
             got = gpu_ctx.hey_element_batch(kind, par, stokes, s, th, qr, fixed, v)
             ref = np.array([oracle.rimo_hey_element(ctypes.byref(d), stokes, s, th, qr, float(a), float(b)) for a, b in zip(fixed, v)])
             report_mismatch("hey_element case %d stokes %d qr %d" % (case, stokes, qr), got, ref, lambda i: (fixed[i], v[i]))
@@ -694,14 +666,10 @@ def test_heyvaerts_outer_integrands_bit_exact(gpu_ctx, oracle, case):
     rng = np.random.default_rng(800 + case)
     d, st = oracle_bind.mkdist(oracle, kind, par)
     assert st == 0
-    sigma0 = s * math.sin(th)
     n = 40
     for stokes in (1, 2):
         for qr in (0, 1):
-            if qr:
-                u = _hey_qr_start(sigma0) * (1. + np.exp(rng.uniform(math.log(1e-3), math.log(1e2), n)))
-            else:
-                u = rng.uniform(-1., 1., n) * np.exp(rng.uniform(math.log(0.3), math.log(1e3), n)) * max(sigma0, 1.)
+            u = hey_outer_abscissae(rng, s, th, qr, n)
             got = gpu_ctx.hey_outer_batch(kind, par, stokes, s, th, qr, u)
             ref = np.array([oracle.rimo_hey_outer_integrand(ctypes.byref(d), stokes, s, th, qr, float(x)) for x in u])
             report_mismatch("hey_outer case %d stokes %d qr %d" % (case, stokes, qr), got, ref, lambda i: u[i])
