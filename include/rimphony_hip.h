@@ -158,6 +158,26 @@ const char *rimphony_version(void);
 int rimphony_ctx_set_tables(rimphony_ctx *ctx, size_t n_tables, size_t n_nodes, double gamma_lo, double gamma_hi,
                             const double *log_n);
 
+/* Tabulated distributions with a pitch-angle factor per table (the entry above is the isotropic case):
+ * f(gamma, mu) = norm n(gamma) g(mu) / (gamma^2 beta), mu = cos xi, separable, norm = 1 / (4 pi P int n dgamma) with
+ * P = 1/2 int_{-1}^{+1} g dmu (pitchy_pl.rs:98-111), df/dmu = f G'(mu), G = ln g.
+ *   log_g   HOST, [n_tables][n_mu]: ln g at nodes uniform in mu from -1 to +1, end points included; 8 <= n_mu <= 65536,
+ *           every value finite -- else RIMPHONY_EINVAL.  Only the shape of a row matters: P absorbs an added constant.
+ * log_g == NULL with n_mu == 0 is rimphony_ctx_set_tables exactly (isotropic; the same bits); exactly one of the two given
+ * is RIMPHONY_EINVAL.  Between the nodes the library evaluates the natural cubic spline in (mu, ln g): g > 0 everywhere and
+ * a straight line G = a mu -- an exponential beam -- is reproduced exactly, the counterpart of the power law in gamma.  P is
+ * the integral of that spline, computed on the host once per table.  A mu a rounding beyond +-1 extrapolates the end
+ * cubic; a NaN mu gives NaN.
+ * A ln g that DIVERGES at mu = +-1 (sin^k xi: ln g = (k/2) ln(1 - mu^2)) is hostile to the spline.  Floored as
+ * (k/2) ln(1 - mu^2 + 1e-6) with k = 2, 257 nodes give g to 5e-6 for |mu| < 0.9 but ring by order one at |mu| = 0.99, and
+ * 1025 nodes still leave 3e-3 there: floor such shapes and use many nodes, or use RIMPHONY_PITCHY_PL / _KAPPA, which have
+ * the factor in closed form.
+ * The results are the reference's algorithms applied to the f given: its DistributionFunction trait accepts any
+ * f(gamma, cos xi), one that is asymmetric in mu included; whether that is physically meaningful is the caller's matter.
+ * Everything else -- rows and their index, the refusals, the kernels used -- is as for rimphony_ctx_set_tables. */
+int rimphony_ctx_set_tables_pitch(rimphony_ctx *ctx, size_t n_tables, size_t n_nodes, double gamma_lo, double gamma_hi,
+                                  const double *log_n, size_t n_mu, const double *log_g);
+
 /* Work counters of the most recent batch call on this context (device-side
  * counts, read back synchronously): integrand samples, wave-wide evaluation
  * passes, inner QAG calls. */

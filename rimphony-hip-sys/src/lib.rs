@@ -95,6 +95,16 @@ extern "C" {
         gamma_hi: c_double,
         log_n: *const c_double,
     ) -> c_int;
+    pub fn rimphony_ctx_set_tables_pitch(
+        ctx: *mut rimphony_ctx,
+        n_tables: usize,
+        n_nodes: usize,
+        gamma_lo: c_double,
+        gamma_hi: c_double,
+        log_n: *const c_double,
+        n_mu: usize,
+        log_g: *const c_double,
+    ) -> c_int;
 
     pub fn rimphony_last_work(ctx: *mut rimphony_ctx, out: *mut rimphony_work) -> c_int;
     pub fn rimphony_last_tail(ctx: *mut rimphony_ctx, out: *mut u64) -> c_int;
@@ -215,6 +225,25 @@ impl HipContext {
         }
         let rc = unsafe {
             rimphony_ctx_set_tables(self.raw, log_n.len() / n_nodes, n_nodes, gamma_lo, gamma_hi, log_n.as_ptr())
+        };
+        if rc != RIMPHONY_OK {
+            return Err(error_text(rc));
+        }
+        Ok(())
+    }
+
+    /// The same with a pitch-angle factor per table: `log_g` holds n_tables rows of n_mu values ln g(mu) at nodes uniform
+    /// in mu = cos xi from -1 to +1 (include/rimphony_hip.h: rimphony_ctx_set_tables_pitch).
+    pub fn set_tables_pitch(
+        &self, n_nodes: usize, gamma_lo: f64, gamma_hi: f64, log_n: &[f64], n_mu: usize, log_g: &[f64],
+    ) -> Result<(), String> {
+        if n_nodes == 0 || log_n.len() % n_nodes != 0 || n_mu == 0 || log_g.len() != log_n.len() / n_nodes * n_mu {
+            return Err(error_text(RIMPHONY_EINVAL));
+        }
+        let rc = unsafe {
+            rimphony_ctx_set_tables_pitch(
+                self.raw, log_n.len() / n_nodes, n_nodes, gamma_lo, gamma_hi, log_n.as_ptr(), n_mu, log_g.as_ptr(),
+            )
         };
         if rc != RIMPHONY_OK {
             return Err(error_text(rc));

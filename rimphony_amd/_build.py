@@ -102,12 +102,11 @@ TAB_ORACLE_C = ["rimo_quad.c", "rimo_bessel.c", "rimo_symphony.c", "rimo_heyvaer
 ORACLE_CFLAGS = ["-O2", "-fPIC", "-ffp-contract=off", "-fno-math-errno", "-mfma", "-msse4.1", "-fopenmp"]
 
 
-def build_tab_oracle():
-    """The CPU oracle of the tabulated distribution (tests only): tests/support/tab_oracle.cpp supplies the three
-    distribution symbols the oracle's calculators call, on top of the host build of the device functions."""
+def _build_dist_oracle(src_name, out_name):
+    """One distribution file under tests/support linked with the oracle's unchanged calculators."""
     import tempfile
-    src = os.path.join(ROOT, "tests", "support", "tab_oracle.cpp")
-    out = os.path.join(ROOT, "tests", "support", "liboracle_tab.so")
+    src = os.path.join(ROOT, "tests", "support", src_name)
+    out = os.path.join(ROOT, "tests", "support", out_name)
     csrcs = [os.path.join(ORACLE_DIR, f) for f in TAB_ORACLE_C]
     deps = [src] + csrcs + [os.path.join(ORACLE_DIR, f) for f in ("rimo.h", "rimo_math.h")] + \
         [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
@@ -119,8 +118,25 @@ def build_tab_oracle():
             o = os.path.join(tmp, os.path.basename(c)[:-2] + ".o")
             subprocess.run(["gcc"] + ORACLE_CFLAGS + ["-std=gnu11", "-c", c, "-o", o], check=True)
             objs.append(o)
-        o = os.path.join(tmp, "tab_oracle.o")
+        o = os.path.join(tmp, src_name[:-4] + ".o")
         subprocess.run(["g++"] + ORACLE_CFLAGS + ["-std=c++17", "-c", src, "-o", o], check=True)
         objs.append(o)
         subprocess.run(["g++", "-shared", "-fopenmp", "-Wl,-z,defs"] + objs + ["-o", out, "-lm"], check=True)
     return out
+
+
+def build_tab_oracle():
+    """The CPU oracle of the tabulated distribution (tests only): tests/support/tab_oracle.cpp supplies the three
+    distribution symbols the oracle's calculators call, on top of the host build of the device functions."""
+    return _build_dist_oracle("tab_oracle.cpp", "liboracle_tab.so")
+
+
+def build_tab_pitch_oracle():
+    """The same for table sets with a pitch-angle factor (tests/support/tab_pitch_oracle.cpp)."""
+    return _build_dist_oracle("tab_pitch_oracle.cpp", "liboracle_tabpitch.so")
+
+
+def build_beam_oracle():
+    """The CPU oracle of an analytic power law times an exponential beam in cos xi (tests/support/beam_oracle.cpp): what the
+    pitch tables are compared with.  Tests only."""
+    return _build_dist_oracle("beam_oracle.cpp", "liboracle_beam.so")

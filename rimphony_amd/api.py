@@ -93,6 +93,28 @@ def check_tables(gamma_lo, gamma_hi, log_n):
     return t
 
 
+def check_pitch_tables(gamma_lo, gamma_hi, log_n, log_g=None, n_mu=None):
+    """A table set as rimphony_ctx_set_tables_pitch accepts it -> (log_n, log_g), contiguous float64 [n_tables][n_nodes] and
+    [n_tables][n_mu] (log_g None: an isotropic set, check_tables alone); ValueError for what the library refuses with
+    RIMPHONY_EINVAL.  n_mu, if given, is the node count the caller means to state: it must be the row length of log_g, 0
+    without one."""
+    t = check_tables(gamma_lo, gamma_hi, log_n)
+    if log_g is None:
+        if n_mu:
+            raise ValueError("n_mu = %d without log_g" % n_mu)
+        return t, None
+    g = np.ascontiguousarray(np.atleast_2d(np.asarray(log_g, dtype=np.float64)))
+    if n_mu is not None and n_mu != g.shape[1]:
+        raise ValueError("n_mu = %d, but log_g has %d nodes per row" % (n_mu, g.shape[1]))
+    if g.ndim != 2 or g.shape[0] != t.shape[0]:
+        raise ValueError("log_g: expected one row of ln g per table (%d), got shape %r" % (t.shape[0], g.shape))
+    if not TAB_MIN_NODES <= g.shape[1] <= TAB_MAX_NODES:
+        raise ValueError("log_g: %d nodes, expected %d .. %d" % (g.shape[1], TAB_MIN_NODES, TAB_MAX_NODES))
+    if not np.isfinite(g).all():
+        raise ValueError("log_g: every value must be finite (g = 0 cannot be held: floor ln g instead)")
+    return t, g
+
+
 class Context:
     """Owns a rimphony_ctx bound to one GPU."""
 
@@ -128,13 +150,23 @@ class Context:
         return t.to(self._dev()).contiguous()
 
     # -- tabulated distributions ---------------------------------------------------
-    def set_tables(self, gamma_lo, gamma_hi, log_n):
+    def set_tables(self, gamma_lo, gamma_hi, log_n, log_g=None):
         """The context's table set for kind TABULATED: log_n [n_tables][n_nodes] (or [n_nodes]) = ln n(gamma) at nodes
         uniform in ln gamma from gamma_lo to gamma_hi, n = dN/dgamma up to a factor.  Replaces the previous set; None
         clears it.  Synchronous.  Let n roll off to a negligible value at both ends: a table that ends at a sizeable n is a
-        step in f, like the power law's gamma limits (include/rimphony_hip.h)."""
+        step in f, like the power law's gamma limits (include/rimphony_hip.h).
+        log_g [n_tables][n_mu] (or [n_mu]) gives each table a pitch-angle factor g(mu), mu = cos xi: ln g at nodes uniform in
+        mu from -1 to +1, f = norm n g / (gamma^2 beta).  Only the shape of a row matters.  A ln g that diverges at the
+        ends (sin^k xi) must be floored and needs many nodes, or use PITCHY_PL / PITCHY_KAPPA (include/rimphony_hip.h)."""
         if log_n is None:
             capi.check(self.lib.rimphony_ctx_set_tables(self.handle, 0, 0, 1.0, 2.0, None), "rimphony_ctx_set_tables")
+            return
+        if log_g is not None:
+            t, g = check_pitch_tables(gamma_lo, gamma_hi, log_n, log_g)
+            dp = ctypes.POINTER(ctypes.c_double)
+            capi.check(self.lib.rimphony_ctx_set_tables_pitch(self.handle, t.shape[0], t.shape[1], float(gamma_lo), float(gamma_hi),
+                                                              t.ctypes.data_as(dp), g.shape[1], g.ctypes.data_as(dp)),
+                       "rimphony_ctx_set_tables_pitch")
             return
         t = check_tables(gamma_lo, gamma_hi, log_n)
         capi.check(self.lib.rimphony_ctx_set_tables(self.handle, t.shape[0], t.shape[1], float(gamma_lo), float(gamma_hi),
@@ -676,25 +708,33 @@ class PitchyKappaDistribution(_DistributionFunction):
 
 
 class TabulatedDistribution(_DistributionFunction):
-    """An isotropic distribution given as a table: log_n [n_nodes] = ln n(gamma) at nodes uniform in ln gamma from gamma_lo
+    """A distribution given as a table: log_n [n_nodes] = ln n(gamma) at nodes uniform in ln gamma from gamma_lo
     to gamma_hi (n = dN/dgamma up to a factor; f = norm n / (gamma^2 beta) inside the table, 0 outside).  The library
-    interpolates with the natural cubic spline in (ln gamma, ln n).  The object installs its table as the context's table
+    interpolates with the natural cubic spline in (ln gamma, ln n).  Isotropic, unless log_g [n_mu] = ln g(mu) at nodes
+    uniform in mu = cos xi from -1 to +1 gives it a pitch-angle factor: f = norm n g / (gamma^2 beta), the natural cubic
+    spline in (mu, ln g) (Context.set_tables).  The object installs its table as the context's table
     set whenever it computes, so two of them can share a context in turn; a batch over several tables uses
     Context.set_tables and kind TABULATED directly."""
 
-    def __init__(self, gamma_lo, gamma_hi, log_n):
+    def __init__(self, gamma_lo, gamma_hi, log_n, log_g=None):
         self.gamma_lo, self.gamma_hi = float(gamma_lo), float(gamma_hi)
-        self.log_n = check_tables(self.gamma_lo, self.gamma_hi, np.asarray(log_n, dtype=np.float64).reshape(1, -1))
+        self.log_n, self.log_g = check_pitch_tables(
+            self.gamma_lo, self.gamma_hi, np.asarray(log_n, dtype=np.float64).reshape(1, -1),
+            None if log_g is None else np.asarray(log_g, dtype=np.float64).reshape(1, -1))
 
     @classmethod
-    def from_function(cls, fn, gamma_lo, gamma_hi, n_nodes=4096):
-        """Tabulate n(gamma) = fn(gamma) (vectorised, positive) on n_nodes nodes uniform in ln gamma."""
+    def from_function(cls, fn, gamma_lo, gamma_hi, n_nodes=4096, pitch_fn=None, n_mu=257):
+        """Tabulate n(gamma) = fn(gamma) (vectorised, positive) on n_nodes nodes uniform in ln gamma and, if given,
+        g(mu) = pitch_fn(mu) (vectorised, positive) on n_mu nodes uniform in mu from -1 to +1."""
         gamma = np.exp(np.linspace(math.log(gamma_lo), math.log(gamma_hi), int(n_nodes)))
         gamma[0], gamma[-1] = gamma_lo, gamma_hi
-        return cls(gamma_lo, gamma_hi, np.log(np.asarray(fn(gamma), dtype=np.float64)))
+        log_g = None
+        if pitch_fn is not None:
+            log_g = np.log(np.asarray(pitch_fn(np.linspace(-1.0, 1.0, int(n_mu))), dtype=np.float64))
+        return cls(gamma_lo, gamma_hi, np.log(np.asarray(fn(gamma), dtype=np.float64)), log_g)
 
     def _install(self, ctx):
-        ctx.set_tables(self.gamma_lo, self.gamma_hi, self.log_n)
+        ctx.set_tables(self.gamma_lo, self.gamma_hi, self.log_n, self.log_g)
         return ctx
 
     def _kind_params(self):

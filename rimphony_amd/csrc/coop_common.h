@@ -17,7 +17,7 @@ struct AssistSlot;
 template <int KIND>
 __device__ inline void load_params(const ParamPtrs &pp, size_t i, DistParams &d)
 {
-    if (KIND == DIST_TABULATED) {
+    if (dist_is_tab(KIND)) {
         // one parameter, the table index; p[1] is not a parameter array but the context's table set (dev_symphony.h,
         // dist_prepare: its address travels in par[1])
         d.par[0] = pp.p[0][i];

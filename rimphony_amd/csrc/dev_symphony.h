@@ -18,13 +18,19 @@
 
 namespace rim {
 
-enum { DIST_POWER_LAW = 0, DIST_THERMAL_JUETTNER = 1, DIST_PITCHY_PL = 2, DIST_PITCHY_KAPPA = 3, DIST_TABULATED = 4 };
+enum { DIST_POWER_LAW = 0, DIST_THERMAL_JUETTNER = 1, DIST_PITCHY_PL = 2, DIST_PITCHY_KAPPA = 3, DIST_TABULATED = 4,
+       // not a kind of the C ABI: the tabulated kind where the table set is KNOWN to have no pitch rows, so that the test for
+       // one and everything behind it leave the code.  Same values as DIST_TABULATED on such a set, bit for bit; the two
+       // persistent kernels are instantiated for it (rimphony_tab.hip), so that isotropic tables run the code they always ran.
+       DIST_TABULATED_ISO = 5 };
+constexpr bool dist_is_tab(int kind) { return kind == DIST_TABULATED || kind == DIST_TABULATED_ISO; }
 enum { STOKES_I = 0, STOKES_Q = 1, STOKES_V = 2 };
 enum { COEFF_EMISSION = 0, COEFF_ABSORPTION = 1, COEFF_FARADAY = 2 };
 
 // Distribution parameters of one point (wave-uniform).  par[] follows the C ABI:
 //   power_law {p, gmin, gmax, gcut}; thermal {T}; pitchy_pl {p, k, gmin, gmax, gcut};
-//   pitchy_kappa {kappa, width, k, gcut}; tabulated {table index} (the other fields: dist_prepare<DIST_TABULATED>).
+//   pitchy_kappa {kappa, width, k, gcut}; tabulated {table index} (the other fields: dist_prepare<DIST_TABULATED>, which
+//   also replaces the index by the address of the table's pitch row).
 struct DistParams {
     double par[5];
     double inv_gamma_cutoff;
@@ -35,9 +41,13 @@ struct DistParams {
 
 // ---- tabulated distribution: a table set in memory (rim_tab_build of tab_spline.h lays it out) ----
 // TAB_HDR_DOUBLES header words, then [n_tables][n_nodes][2] = {y_j = ln n(gamma_j), m_j = dy/du at the node} of the natural
-// cubic spline in u = ln gamma; the nodes are uniform in u.
+// cubic spline in u = ln gamma; the nodes are uniform in u.  A set with a pitch-angle factor g(mu), mu = cos xi, says so in
+// TAB_HDR_NMU (0: isotropic, nothing follows) and appends one pitch row per table: TAB_PITCH_HDR words {n_mu - 2, 1 / h_mu,
+// h_mu, P = 1/2 int g dmu}, then [n_mu][2] = {G_j = ln g(mu_j), M_j = dG/dmu at the node} of the natural cubic spline in mu;
+// the nodes are uniform in mu from -1 to +1.
 enum { TAB_HDR_NTABLES = 0, TAB_HDR_NNODES = 1, TAB_HDR_GLO = 2, TAB_HDR_GHI = 3, TAB_HDR_ULO = 4, TAB_HDR_INVH = 5, TAB_HDR_H = 6,
-       TAB_HDR_DOUBLES = 8 };
+       TAB_HDR_NMU = 7, TAB_HDR_DOUBLES = 8 };
+enum { TAB_PITCH_LAST = 0, TAB_PITCH_INVH = 1, TAB_PITCH_H = 2, TAB_PITCH_P = 3, TAB_PITCH_HDR = 4 };
 
 // is `idx` (par[0] of a row) the index of a table of the set?
 RIM_DEV bool tab_row_ok(const double *hdr, double idx)
@@ -48,16 +58,23 @@ RIM_DEV bool tab_row_ok(const double *hdr, double idx)
 template <int KIND>
 RIM_DEV void dist_prepare(DistParams &d, double norm)
 {
-    if (KIND == DIST_TABULATED) {
+    if (dist_is_tab(KIND)) {
         // In: par[0] the table index, par[1] the bit pattern of the table set's address.  The kind has one parameter, so the
         // fields the others use carry what a sample needs (DistParams does not grow): par[1] the bit pattern of the row's
         // address, par[2] u_lo, par[3] 1 / h, par[4] the index of the last interval; inv_gamma_cutoff h, inv_kappa_width
         // gamma_lo, neg_inverse_t gamma_hi.  A row whose index names no table keeps table 0 (every read stays inside the
-        // set) and gets a NaN normalisation.
+        // set) and gets a NaN normalisation.  Out: par[0], no longer needed once the row is found, is the bit pattern of
+        // the address of the table's pitch row, or +0 for a set without pitch rows (isotropic).
         const double *hdr = (const double *) (uintptr_t) rim_bits(d.par[1]);
         const bool ok = tab_row_ok(hdr, d.par[0]);
         const size_t nn = (size_t) hdr[TAB_HDR_NNODES];
         const size_t row = ok ? (size_t) d.par[0] : 0;
+        const size_t nmu = KIND == DIST_TABULATED_ISO ? 0 : (size_t) hdr[TAB_HDR_NMU];
+        d.par[0] = 0.;
+        if (nmu) {
+            const size_t nt = (size_t) hdr[TAB_HDR_NTABLES];
+            d.par[0] = rim_frombits((uint64_t) (uintptr_t) (hdr + TAB_HDR_DOUBLES + nt * nn * 2 + row * (TAB_PITCH_HDR + nmu * 2)));
+        }
         d.par[1] = rim_frombits((uint64_t) (uintptr_t) (hdr + TAB_HDR_DOUBLES + row * nn * 2));
         d.par[2] = hdr[TAB_HDR_ULO];
         d.par[3] = hdr[TAB_HDR_INVH];
@@ -97,9 +114,21 @@ RIM_DEV double kappa_gamma_term(const DistParams &d, double gamma)
     return rim_pow(base, y) * RimMath<PREC>::exp(-gamma * d.inv_gamma_cutoff);
 }
 
-// The spline H(u) of a tabulated distribution and dH/du at u = ln gamma: cubic Hermite on the interval of the node values
-// and slopes, which a lane reads as four consecutive doubles.  gamma outside the table only ever gets here as a NaN (the
-// callers return 0 there first): the interval index is formed from a clamped copy, so every read stays inside the row.
+// Cubic Hermite on one interval of width h: q = {y0, m0, y1, m1}, the node values and slopes a lane reads as four
+// consecutive doubles, t in [0, 1) the position in it.  The value and the derivative with respect to t.
+RIM_DEV void tab_hermite(const double *q, double h, double t, double &val, double &dvaldt)
+{
+    const double y0 = q[0], m0 = q[1], y1 = q[2], m1 = q[3];
+    const double b0 = h * m0, b1 = h * m1, dy = y1 - y0;
+    const double c2 = 3. * dy - 2. * b0 - b1;
+    const double c3 = b0 + b1 - 2. * dy;
+    val = rim_fma(t, rim_fma(t, rim_fma(t, c3, c2), b0), y0);
+    dvaldt = rim_fma(t, rim_fma(t, 3. * c3, 2. * c2), b0);
+}
+
+// The spline H(u) of a tabulated distribution and dH/du at u = ln gamma.  gamma outside the table only ever gets here as
+// a NaN (the callers return 0 there first): the interval index is formed from a clamped copy, so every read stays inside
+// the row.
 RIM_DEV void tab_spline(const DistParams &d, double gamma, double &hval, double &dhdu)
 {
     const double *row = (const double *) (uintptr_t) rim_bits(d.par[1]);
@@ -109,14 +138,32 @@ RIM_DEV void tab_spline(const DistParams &d, double gamma, double &hval, double 
     if (xc > d.par[4]) xc = d.par[4];
     const long long j = (long long) xc;
     const double t = x - (double) j;
-    const double *q = row + 2 * j;
-    const double y0 = q[0], m0 = q[1], y1 = q[2], m1 = q[3];
-    const double h = d.inv_gamma_cutoff;
-    const double b0 = h * m0, b1 = h * m1, dy = y1 - y0;
-    const double c2 = 3. * dy - 2. * b0 - b1;
-    const double c3 = b0 + b1 - 2. * dy;
-    hval = rim_fma(t, rim_fma(t, rim_fma(t, c3, c2), b0), y0);
-    dhdu = rim_fma(t, rim_fma(t, 3. * c3, 2. * c2), b0) * d.par[3];
+    double dhdt;
+    tab_hermite(row + 2 * j, d.inv_gamma_cutoff, t, hval, dhdt);
+    dhdu = dhdt * d.par[3];
+}
+
+// does the row have a pitch-angle factor?  (wave-uniform; DIST_TABULATED_ISO: known not to at compile time)
+RIM_DEV bool tab_has_pitch(const DistParams &d) { return rim_bits(d.par[0]) != 0; }
+template <int KIND>
+RIM_DEV bool tab_kind_has_pitch(const DistParams &d) { return KIND != DIST_TABULATED_ISO && tab_has_pitch(d); }
+
+// The spline G(mu) = ln g of a pitch row (tab_has_pitch) and dG/dmu at mu = cos xi.  The interval index is formed from a
+// clamped copy, as in tab_spline: a mu a rounding beyond +-1 extrapolates the end cubic, a NaN mu gives NaN, and every
+// read stays inside the row.
+RIM_DEV void tab_pitch_spline(const DistParams &d, double mu, double &gval, double &dgdmu)
+{
+    const double *ph = (const double *) (uintptr_t) rim_bits(d.par[0]);
+    const double last = ph[TAB_PITCH_LAST], invh = ph[TAB_PITCH_INVH];
+    const double x = (mu + 1.) * invh;
+    double xc = x;
+    if (!(xc >= 0.)) xc = 0.;
+    if (xc > last) xc = last;
+    const long long j = (long long) xc;
+    const double t = x - (double) j;
+    double dgdt;
+    tab_hermite(ph + TAB_PITCH_HDR + 2 * j, ph[TAB_PITCH_H], t, gval, dgdt);
+    dgdmu = dgdt * invh;
 }
 
 // n(gamma) = exp(H(ln gamma)) of the table: the integrand of the normalisation (power_law.rs:95-96 for a table)
@@ -127,16 +174,25 @@ RIM_DEV double tab_norm_integrand(const DistParams &d, double g)
     return rim_exp(hval);
 }
 
-// calc_f and calc_f_derivatives of the tabulated distribution (isotropic: d f / d cos xi = 0), one body for all three
-// entries below: f = norm n(gamma) / (gamma^2 beta), 0 outside the table (the rule of power_law.rs:38,49).
-RIM_DEV void tab_calc_f_both(const DistParams &d, double gamma, double &f, double &dfdg)
+// calc_f and calc_f_derivatives of the tabulated distribution, one body for all three entries below:
+// f = norm n(gamma) g(mu) / (gamma^2 beta), 0 outside the table (the rule of power_law.rs:38,49), d f / d mu = f G'(mu).
+// A row without a pitch factor is isotropic: no further load, the arithmetic of n(gamma) alone, d f / d mu = +0.
+template <int KIND = DIST_TABULATED>
+RIM_DEV void tab_calc_f_both(const DistParams &d, double gamma, double cos_xi, double &f, double &dfdg, double &dfdcx)
 {
-    f = 0.; dfdg = 0.;
+    f = 0.; dfdg = 0.; dfdcx = 0.;
     if (gamma < d.inv_kappa_width || gamma > d.neg_inverse_t) return;
     double hval, dhdu;
     tab_spline(d, gamma, hval, dhdu);
     const double beta = rim_sqrt(1. - rim_div_moderate(1., gamma * gamma));
-    f = d.norm * rim_exp(hval) / (gamma * gamma * beta);
+    if (tab_kind_has_pitch<KIND>(d)) {
+        double gval, dgdmu;
+        tab_pitch_spline(d, cos_xi, gval, dgdmu);
+        f = d.norm * rim_exp(hval + gval) / (gamma * gamma * beta);
+        dfdcx = f * dgdmu;
+    } else {
+        f = d.norm * rim_exp(hval) / (gamma * gamma * beta);
+    }
     dfdg = f * (dhdu / gamma - 1. / gamma - gamma / (gamma * gamma - 1.));
 }
 
@@ -144,9 +200,9 @@ template <int KIND, int PREC = 0>
 RIM_DEV double calc_f(const DistParams &d, double gamma, double cos_xi)
 {
     typedef RimMath<PREC> M;
-    if (KIND == DIST_TABULATED) {
-        double f, dfdg;
-        tab_calc_f_both(d, gamma, f, dfdg);
+    if (dist_is_tab(KIND)) {
+        double f, dfdg, dfdcx;
+        tab_calc_f_both<KIND>(d, gamma, cos_xi, f, dfdg, dfdcx);
         return f;
     }
     if (KIND == DIST_POWER_LAW) {
@@ -175,10 +231,9 @@ template <int KIND, int PREC = 0>
 RIM_DEV void calc_f_derivatives(const DistParams &d, double gamma, double cos_xi, double &dfdg, double &dfdcx)
 {
     typedef RimMath<PREC> M;
-    if (KIND == DIST_TABULATED) {
+    if (dist_is_tab(KIND)) {
         double f;
-        tab_calc_f_both(d, gamma, f, dfdg);
-        dfdcx = 0.;
+        tab_calc_f_both<KIND>(d, gamma, cos_xi, f, dfdg, dfdcx);
         return;
     }
     if (KIND == DIST_POWER_LAW) {
@@ -386,11 +441,11 @@ RIM_DEV double gamma_integrand_f_term(int coeff, const DistParams &d, double cos
     double dfdg, dfdcx;
     RIM_HIT(25);
     calc_f_derivatives<KIND, PREC>(d, gamma, cos_xi, dfdg, dfdcx);
-    if (KIND == DIST_POWER_LAW || KIND == DIST_THERMAL_JUETTNER || KIND == DIST_TABULATED) {
-        // dfdcx is the constant +0 (isotropic distributions): dfdcx_factor * dfdcx is a zero with the sign of the
-        // factor (a NaN only where the sample is a NaN through cos_xi anyway), and for gamma > 0 the factor
-        // (beta cos_th - cos_xi) / (gamma - 1 / gamma) has the sign of (beta cos_th - cos_xi) (gamma - 1): the
-        // same bits -- signed zeros of f_term included -- without the two divisions.
+    if (KIND == DIST_POWER_LAW || KIND == DIST_THERMAL_JUETTNER || (dist_is_tab(KIND) && !tab_kind_has_pitch<KIND>(d))) {
+        // dfdcx is the constant +0 (isotropic distributions; a table with a pitch row takes the general form below):
+        // dfdcx_factor * dfdcx is a zero with the sign of the factor (a NaN only where the sample is a NaN through cos_xi
+        // anyway), and for gamma > 0 the factor (beta cos_th - cos_xi) / (gamma - 1 / gamma) has the sign of
+        // (beta cos_th - cos_xi) (gamma - 1): the same bits -- signed zeros of f_term included -- without the two divisions.
         return dfdg + ((beta * cos_th - cos_xi) * dfdcx) * (gamma - 1.);
     }
     const double dfdcx_factor = (beta * cos_th - cos_xi) / (gamma - 1. / gamma);
@@ -405,9 +460,8 @@ RIM_DEV double gamma_integrand_f_term(int coeff, const DistParams &d, double cos
 template <int KIND>
 RIM_DEV void calc_f_both(const DistParams &d, double gamma, double cos_xi, double &f, double &dfdg, double &dfdcx)
 {
-    if (KIND == DIST_TABULATED) {
-        tab_calc_f_both(d, gamma, f, dfdg);
-        dfdcx = 0.;
+    if (dist_is_tab(KIND)) {
+        tab_calc_f_both<KIND>(d, gamma, cos_xi, f, dfdg, dfdcx);
         return;
     }
     if (KIND == DIST_POWER_LAW) {
@@ -457,7 +511,7 @@ RIM_DEV void gamma_integrand_f_terms(const DistParams &d, double cos_th, const G
     double dfdg, dfdcx;
     RIM_HIT(24); RIM_HIT(25);
     calc_f_both<KIND>(d, gamma, cos_xi, f_em, dfdg, dfdcx);
-    if (KIND == DIST_POWER_LAW || KIND == DIST_THERMAL_JUETTNER || KIND == DIST_TABULATED) {
+    if (KIND == DIST_POWER_LAW || KIND == DIST_THERMAL_JUETTNER || (dist_is_tab(KIND) && !tab_kind_has_pitch<KIND>(d))) {
         f_ab = dfdg + ((beta * cos_th - cos_xi) * dfdcx) * (gamma - 1.);       // (gamma_integrand_f_term says why)
     } else {
         const double dfdcx_factor = (beta * cos_th - cos_xi) / (gamma - 1. / gamma);

@@ -331,7 +331,7 @@ struct rimphony_ctx {
     unsigned long long hb_task;
     // what hipOccupancyMaxActiveBlocksPerMultiprocessor answered (-1: the query failed), asked once per context
     // (= per device) and instantiation: coop_kernel<P> by problem (0 Symphony, 1 Heyvaerts) and distribution kind,
-    int resident[2][5];
+    int resident[2][6];             // (kind 4 twice: [4] a table set with pitch rows, [5] one without)
     int resident_f32[4];            // ... the Symphony kernels' fp32-integrand variants,
     int resident_group[2][4];       // ... group_kernel<P> [Symphony groups / Faraday pair][kind]
     // 0: this context has the GPU to itself (it holds the device's lock file); 1: another context or process had
@@ -351,6 +351,7 @@ struct rimphony_ctx {
     RimDevBuf<char> d_gboard;       // [cap] GroupSlot + flag words behind
     // the table set of the tabulated distribution (rimphony_ctx_set_tables; dev_symphony.h has the layout), or empty
     RimDevBuf<double> d_tab;
+    bool tab_pitch = false;         // the set has pitch rows: which instantiation of the kind's persistent kernels runs
 };
 
 // ---- last error (thread-local text; the codes are in rimphony_hip.h) ---------------------------
@@ -561,14 +562,14 @@ static int check_tables(const rimphony_ctx *c, int kind)
     return (kind == RIMPHONY_TABULATED && !c->d_tab.p) ? RIMPHONY_EINVAL : RIMPHONY_OK;
 }
 
-extern "C" int rimphony_ctx_set_tables(rimphony_ctx *c, size_t n_tables, size_t n_nodes, double gamma_lo, double gamma_hi,
-                                       const double *log_n)
+static int set_tables(rimphony_ctx *c, size_t n_tables, size_t n_nodes, double gamma_lo, double gamma_hi, const double *log_n,
+                      size_t n_mu, const double *log_g)
 {
     if (!c) return RIMPHONY_EINVAL;
     std::vector<double> blob;
     if (n_tables) {
-        if (rim_tab_check(n_tables, n_nodes, gamma_lo, gamma_hi, log_n)) return RIMPHONY_EINVAL;
-        try { rim_tab_build(n_tables, n_nodes, gamma_lo, gamma_hi, log_n, blob); }
+        if (rim_tab_check_pitch(n_tables, n_nodes, gamma_lo, gamma_hi, log_n, n_mu, log_g)) return RIMPHONY_EINVAL;
+        try { rim_tab_build_pitch(n_tables, n_nodes, gamma_lo, gamma_hi, log_n, n_mu, log_g, blob); }
         catch (const std::bad_alloc &) { return RIMPHONY_ENOMEM; }
     }
     RimCtxScope scope(c, nullptr);
@@ -577,6 +578,7 @@ extern "C" int rimphony_ctx_set_tables(rimphony_ctx *c, size_t n_tables, size_t 
     // the previous set may still be read by the context's earlier work
     if (c->ev_batch_valid) HIP_TRY(hipEventSynchronize(c->ev_batch));
     c->d_tab.release();
+    c->tab_pitch = false;
     if (!n_tables) return RIMPHONY_OK;
     rc = c->d_tab.grow(blob.size(), blob.size() * sizeof(double), "the distribution tables");
     if (rc) return rc;
@@ -585,7 +587,20 @@ extern "C" int rimphony_ctx_set_tables(rimphony_ctx *c, size_t n_tables, size_t 
         c->d_tab.release();
         return RIMPHONY_EHIP;
     }
+    c->tab_pitch = log_g != nullptr;
     return RIMPHONY_OK;
+}
+
+extern "C" int rimphony_ctx_set_tables(rimphony_ctx *c, size_t n_tables, size_t n_nodes, double gamma_lo, double gamma_hi,
+                                       const double *log_n)
+{
+    return set_tables(c, n_tables, n_nodes, gamma_lo, gamma_hi, log_n, 0, nullptr);
+}
+
+extern "C" int rimphony_ctx_set_tables_pitch(rimphony_ctx *c, size_t n_tables, size_t n_nodes, double gamma_lo, double gamma_hi,
+                                             const double *log_n, size_t n_mu, const double *log_g)
+{
+    return set_tables(c, n_tables, n_nodes, gamma_lo, gamma_hi, log_n, n_mu, log_g);
 }
 
 static int rim_precision_check(const rimphony_ctx *c, int kind, int precision);
@@ -665,10 +680,10 @@ static PersistentKernel coop_kernel_of()
     k.early_squad = (unsigned) P::EARLY_SQUAD;
     return k;
 }
-static PersistentKernel rim_coop_kernel(int problem, int kind, int prec)
+static PersistentKernel rim_coop_kernel(int problem, int kind, int prec, bool tab_pitch)
 {
     if (kind == RIMPHONY_TABULATED) {       // (its kernels live in rimphony_tab.hip; no fp32 variant: refused at the entry)
-        const RimCoopKernelInfo t = rim_tab_coop_kernel(problem);
+        const RimCoopKernelInfo t = rim_tab_coop_kernel(problem, tab_pitch);
         PersistentKernel k = {};
         k.fn = t.fn; k.waves = t.waves; k.early_help = t.early_help; k.early_squad = t.early_squad;
         return k;
@@ -748,9 +763,10 @@ static int launch_persistent(rimphony_ctx *c, const PersistentKernel &k, unsigne
 // One wave per (point, coefficient): coop_kernel<SymphonyProblem> (problem 0) or coop_kernel<HeyvaertsProblem> (1).
 static int launch_coop(rimphony_ctx *c, int problem, int kind, int prec, const SymArgs &a, hipStream_t st)
 {
-    PersistentKernel k = rim_coop_kernel(problem, kind, prec);
+    PersistentKernel k = rim_coop_kernel(problem, kind, prec, c->tab_pitch);
     k.faraday = problem != 0;
-    k.resident = prec ? &c->resident_f32[kind] : &c->resident[problem][kind];
+    const int cell = (kind == RIMPHONY_TABULATED && !c->tab_pitch) ? kind + 1 : kind;
+    k.resident = prec ? &c->resident_f32[kind] : &c->resident[problem][cell];
     k.spill = &c->d_spill;
     k.spill_doubles = SPILL_DOUBLES_PER_WAVE;
     k.board = &c->d_board;

@@ -14,8 +14,9 @@ struct RimCoopKernelInfo {
     unsigned early_squad;
 };
 
-// coop_kernel<SymphonyProblem<DIST_TABULATED>> (problem 0) or coop_kernel<HeyvaertsProblem<DIST_TABULATED>> (1)
-RimCoopKernelInfo rim_tab_coop_kernel(int problem);
+// coop_kernel<SymphonyProblem<K>> (problem 0) or coop_kernel<HeyvaertsProblem<K>> (1); K = DIST_TABULATED for a table set with
+// pitch rows, DIST_TABULATED_ISO (dev_symphony.h) for one without
+RimCoopKernelInfo rim_tab_coop_kernel(int problem, bool pitch);
 // norm_kernel, integrand_kernel_n and gamma_integral_kernel of the kind: enqueue only, the caller asks hipGetLastError()
 void rim_tab_launch_norm(unsigned grid, hipStream_t st, const ParamPtrs &pp, size_t n, double *d_norm, unsigned long long *queue,
                          double *spill);

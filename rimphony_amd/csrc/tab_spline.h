@@ -4,6 +4,11 @@
 // fp64: m_{j-1} + 4 m_j + m_{j+1} = 3 (y_{j+1} - y_{j-1}) / h inside, 2 m_0 + m_1 = 3 (y_1 - y_0) / h and its mirror at the
 // ends (second derivative 0 there).  A straight line in (u, y) -- a pure power law -- comes back as itself.
 //
+// A set may carry a pitch-angle factor g(mu), mu = cos xi, per table (rim_tab_check_pitch, rim_tab_build_pitch): G = ln g
+// at n_mu nodes uniform in mu from -1 to +1, the same natural spline in (mu, G) -- a straight line, an exponential beam,
+// comes back as itself -- and P = 1/2 int g dmu of the spline, which the normalisation divides by.  The pitch rows follow
+// the gamma rows; an isotropic set is laid out as it always was.
+//
 // Plain C++ with the elementary functions of detmath.h, so that the library (hipcc's host pass) and the tests' table
 // oracle (g++) produce the same bits from the same table.
 #ifndef RIM_TAB_SPLINE_H
@@ -12,6 +17,7 @@
 #include <cstddef>
 #include <vector>
 #include "dev_symphony.h"
+#include "gk31_table.h"
 
 #define RIM_TAB_MIN_NODES 8
 #define RIM_TAB_MAX_NODES 65536
@@ -25,6 +31,25 @@ inline int rim_tab_check(size_t n_tables, size_t n_nodes, double gamma_lo, doubl
     for (size_t i = 0; i < n_tables * n_nodes; i++)
         if (!rim_isfinite(log_n[i])) return -1;
     return 0;
+}
+
+// The slopes of the natural cubic spline through y[0 .. n-1] at nodes h apart, written with the values as {y_j, m_j} pairs
+// to row[2 j], row[2 j + 1].  cp, dp: n doubles each, the swept upper diagonal and right-hand side of the Thomas algorithm.
+inline void rim_tab_spline_row(const double *y, size_t n, double h, double *row, double *cp, double *dp)
+{
+    const size_t last = n - 1;
+    cp[0] = 0.5;
+    dp[0] = 3. * (y[1] - y[0]) / h / 2.;
+    for (size_t j = 1; j <= last; j++) {
+        const double diag = j < last ? 4. : 2.;
+        const double rhs = j < last ? 3. * (y[j + 1] - y[j - 1]) / h : 3. * (y[last] - y[last - 1]) / h;
+        const double den = diag - cp[j - 1];
+        cp[j] = 1. / den;
+        dp[j] = (rhs - dp[j - 1]) / den;
+    }
+    row[2 * last + 1] = dp[last];
+    for (size_t j = last; j-- > 0;) row[2 * j + 1] = dp[j] - cp[j] * row[2 * (j + 1) + 1];
+    for (size_t j = 0; j <= last; j++) row[2 * j] = y[j];
 }
 
 // the table set as one block of doubles; rim_tab_check() has passed
@@ -42,23 +67,60 @@ inline void rim_tab_build(size_t n_tables, size_t n_nodes, double gamma_lo, doub
     blob[TAB_HDR_ULO] = u_lo;
     blob[TAB_HDR_INVH] = 1. / h;
     blob[TAB_HDR_H] = h;
-    std::vector<double> cp(n_nodes), dp(n_nodes);       // Thomas algorithm: the swept upper diagonal and right-hand side
+    std::vector<double> cp(n_nodes), dp(n_nodes);
+    for (size_t t = 0; t < n_tables; t++)
+        rim_tab_spline_row(log_n + t * n_nodes, n_nodes, h, blob.data() + TAB_HDR_DOUBLES + t * n_nodes * 2, cp.data(), dp.data());
+}
+
+// rim_tab_check() for a set with an optional pitch-angle factor: log_g [n_tables][n_mu] = ln g at nodes uniform in mu, or
+// null with n_mu = 0 for an isotropic set
+inline int rim_tab_check_pitch(size_t n_tables, size_t n_nodes, double gamma_lo, double gamma_hi, const double *log_n,
+                               size_t n_mu, const double *log_g)
+{
+    if (rim_tab_check(n_tables, n_nodes, gamma_lo, gamma_hi, log_n)) return -1;
+    if (!log_g && n_mu == 0) return 0;
+    if (!log_g || n_mu < RIM_TAB_MIN_NODES || n_mu > RIM_TAB_MAX_NODES) return -1;
+    if (n_tables > ((size_t) 1 << 40) / n_mu) return -1;
+    for (size_t i = 0; i < n_tables * n_mu; i++)
+        if (!rim_isfinite(log_g[i])) return -1;
+    return 0;
+}
+
+// rim_tab_build() for such a set; rim_tab_check_pitch() has passed.  Without log_g the blob is rim_tab_build()'s.
+inline void rim_tab_build_pitch(size_t n_tables, size_t n_nodes, double gamma_lo, double gamma_hi, const double *log_n,
+                                size_t n_mu, const double *log_g, std::vector<double> &blob)
+{
+    using namespace rim;
+    rim_tab_build(n_tables, n_nodes, gamma_lo, gamma_hi, log_n, blob);
+    if (!log_g) return;
+    static const double xgk[32] = RIM_GK31_X, wgk[32] = RIM_GK31_WK;
+    const size_t base = blob.size(), stride = (size_t) TAB_PITCH_HDR + n_mu * 2;
+    blob.resize(base + n_tables * stride, 0.);
+    blob[TAB_HDR_NMU] = (double) n_mu;
+    const double h = 2. / (double) (n_mu - 1);
+    std::vector<double> cp(n_mu), dp(n_mu);
     for (size_t t = 0; t < n_tables; t++) {
-        const double *y = log_n + t * n_nodes;
-        double *row = blob.data() + TAB_HDR_DOUBLES + t * n_nodes * 2;
-        const size_t last = n_nodes - 1;
-        cp[0] = 0.5;
-        dp[0] = 3. * (y[1] - y[0]) / h / 2.;
-        for (size_t j = 1; j <= last; j++) {
-            const double diag = j < last ? 4. : 2.;
-            const double rhs = j < last ? 3. * (y[j + 1] - y[j - 1]) / h : 3. * (y[last] - y[last - 1]) / h;
-            const double den = diag - cp[j - 1];
-            cp[j] = 1. / den;
-            dp[j] = (rhs - dp[j - 1]) / den;
+        double *ph = blob.data() + base + t * stride;
+        ph[TAB_PITCH_LAST] = (double) (n_mu - 2);
+        ph[TAB_PITCH_INVH] = 1. / h;
+        ph[TAB_PITCH_H] = h;
+        rim_tab_spline_row(log_g + t * n_mu, n_mu, h, ph + TAB_PITCH_HDR, cp.data(), dp.data());
+        // P = 1/2 int g dmu of the spline as the kernels evaluate it: the 31-point Kronrod rule on each node interval,
+        // summed in node order
+        DistParams d;
+        d.par[0] = rim_frombits((uint64_t) (uintptr_t) ph);
+        double sum = 0.;
+        for (size_t j = 0; j + 1 < n_mu; j++) {
+            const double half = 0.5 * h, centre = -1. + ((double) j + 0.5) * h;
+            double acc = 0.;
+            for (int k = 0; k < 31; k++) {
+                double gval, dgdmu;
+                tab_pitch_spline(d, centre + half * xgk[k], gval, dgdmu);
+                acc += wgk[k] * rim_exp(gval);
+            }
+            sum += half * acc;
         }
-        row[2 * last + 1] = dp[last];
-        for (size_t j = last; j-- > 0;) row[2 * j + 1] = dp[j] - cp[j] * row[2 * (j + 1) + 1];
-        for (size_t j = 0; j <= last; j++) row[2 * j] = y[j];
+        ph[TAB_PITCH_P] = 0.5 * sum;
     }
 }
 

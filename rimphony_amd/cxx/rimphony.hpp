@@ -71,6 +71,17 @@ public:
         check(rimphony_ctx_set_tables(ctx_, n_tables, n_nodes, gamma_lo, gamma_hi, n_tables ? log_n.data() : nullptr),
               "rimphony_ctx_set_tables");
     }
+    // The same with a pitch-angle factor per table: log_g = ln g(mu), [n_tables][n_mu] row-major, at nodes uniform in
+    // mu = cos xi from -1 to +1 (rimphony_ctx_set_tables_pitch); an empty log_g with n_mu = 0 is the isotropic set.
+    void set_tables(size_t n_tables, size_t n_nodes, double gamma_lo, double gamma_hi, const std::vector<double> &log_n,
+                    size_t n_mu, const std::vector<double> &log_g) const
+    {
+        if (log_n.size() != n_tables * n_nodes) throw std::runtime_error("set_tables: log_n must hold n_tables * n_nodes values");
+        if (log_g.size() != n_tables * n_mu) throw std::runtime_error("set_tables: log_g must hold n_tables * n_mu values");
+        check(rimphony_ctx_set_tables_pitch(ctx_, n_tables, n_nodes, gamma_lo, gamma_hi, n_tables ? log_n.data() : nullptr, n_mu,
+                                            log_g.empty() ? nullptr : log_g.data()),
+              "rimphony_ctx_set_tables_pitch");
+    }
 private:
     rimphony_ctx *ctx_ = nullptr;
 };
@@ -291,9 +302,10 @@ private:
     double kappa_, width_, k_, gcut_ = 1e10;
 };
 
-// An isotropic distribution given as a table of ln n(gamma) at nodes uniform in ln gamma (n = dN/dgamma up to a factor;
+// A distribution given as a table of ln n(gamma) at nodes uniform in ln gamma (n = dN/dgamma up to a factor;
 // the library interpolates with the natural cubic spline in (ln gamma, ln n); f = 0 outside the table, so let n roll off
-// to a negligible value at both ends).  A context holds ONE table set at a time: calc_f, calc_f_derivatives and
+// to a negligible value at both ends).  Isotropic, unless log_g = ln g(mu) at nodes uniform in mu = cos xi from -1 to +1
+// gives it a pitch-angle factor: f = norm n g / (gamma^2 beta) (include/rimphony_hip.h).  A context holds ONE table set at a time: calc_f, calc_f_derivatives and
 // full_calculation install this object's table in the context they are given, and the calculator computes with whatever
 // set the context holds when it is used -- call install() again after another table has used the context.
 class TabulatedDistribution : public DistributionFunction {
@@ -303,7 +315,9 @@ protected:
 public:
     TabulatedDistribution(double gamma_lo, double gamma_hi, std::vector<double> log_n)
         : glo_(gamma_lo), ghi_(gamma_hi), log_n_(std::move(log_n)) {}
-    void install(const Context &ctx) const { ctx.set_tables(1, log_n_.size(), glo_, ghi_, log_n_); }
+    TabulatedDistribution(double gamma_lo, double gamma_hi, std::vector<double> log_n, std::vector<double> log_g)
+        : glo_(gamma_lo), ghi_(gamma_hi), log_n_(std::move(log_n)), log_g_(std::move(log_g)) {}
+    void install(const Context &ctx) const { ctx.set_tables(1, log_n_.size(), glo_, ghi_, log_n_, log_g_.size(), log_g_); }
     double calc_f(const Context &ctx, double gamma, double cos_xi) const
     { install(ctx); return DistributionFunction::calc_f(ctx, gamma, cos_xi); }
     std::array<double, 2> calc_f_derivatives(const Context &ctx, double gamma, double cos_xi) const
@@ -315,7 +329,7 @@ public:
     }
 private:
     double glo_, ghi_;
-    std::vector<double> log_n_;
+    std::vector<double> log_n_, log_g_;
 };
 
 }  // namespace rimphony
