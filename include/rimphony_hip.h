@@ -178,6 +178,34 @@ int rimphony_ctx_set_tables(rimphony_ctx *ctx, size_t n_tables, size_t n_nodes, 
 int rimphony_ctx_set_tables_pitch(rimphony_ctx *ctx, size_t n_tables, size_t n_nodes, double gamma_lo, double gamma_hi,
                                   const double *log_n, size_t n_mu, const double *log_g);
 
+/* Tabulated distributions given as a SURFACE, ln n(gamma, mu) on a grid: any f(gamma, cos xi), one that is not a product
+ * n(gamma) g(mu) included -- an anisotropy that grows with energy, a beam on an isotropic core, a loss cone above some gamma.
+ * f(gamma, mu) = norm exp(S(ln gamma, mu)) / (gamma^2 beta) inside [gamma_lo, gamma_hi], 0 outside;
+ * df/dgamma = f (S_u / gamma - 1 / gamma - gamma / (gamma^2 - 1)), df/dmu = f S_mu;
+ * norm = 1 / (4 pi int nbar dgamma), nbar(gamma) = 1/2 int_{-1}^{+1} exp(S(ln gamma, mu)) dmu.
+ *   log_n   HOST, [n_tables][n_nodes][n_mu], mu fastest: ln n at nodes uniform in ln gamma from ln gamma_lo to ln gamma_hi
+ *           and uniform in mu from -1 to +1, end points included; 8 <= n_nodes <= 65536, 8 <= n_mu <= 1024,
+ *           n_nodes n_mu <= 2^20 (32 MiB per table on the device), 1 <= gamma_lo < gamma_hi, every value finite -- else
+ *           RIMPHONY_EINVAL, checked on the host, and the previous set stays.
+ * S is the tensor-product natural cubic spline through the nodes, evaluated as a bicubic on the cell.  A surface bilinear
+ * in (ln gamma, mu), ln n = c - p u + a mu + q u mu -- a power law whose index depends on the pitch angle, times an exponential
+ * beam -- is reproduced exactly; a sum H(ln gamma) + G(mu) gives the function rimphony_ctx_set_tables_pitch makes of (H, G),
+ * in other arithmetic (agreement to rounding, not to the bit).  A mu a rounding beyond +-1 extrapolates the end cell; a NaN
+ * gives NaN.  The natural end condition (second derivative 0 across every edge of the grid) costs accuracy where the surface
+ * is curved at an edge: there the error falls with the fourth power of the spacing only in the interior.  g -> 0 at mu = +-1
+ * cannot be held in ln n: floor it, as for a pitch row.  A table that ends at a non-negligible n behaves like gamma limits.
+ * The normalisation is a property of a table, not of a row: the call integrates it once per table on the device (the
+ * 31-point Kronrod rule on every mu cell inside an adaptive quadrature over gamma, eps_rel 1e-8) and keeps it beside the
+ * table; rimphony_batch_norm* and the coefficient entries read it.  A table whose quadrature fails has a NaN
+ * normalisation: its rows are NaN with RIMPHONY_ST_NORM_FAIL, the other tables are unaffected.  The call therefore takes
+ * from about 20 ms (512 x 64 nodes) to a third of a second (1024 x 1024) per table.
+ * A context holds one set at a time, of one form: installing a 2-D set replaces an isotropic or pitch set and the other way
+ * round; n_tables = 0 clears the set.  A device allocation that fails is RIMPHONY_ENOMEM and the previous set stays.
+ * Everything else -- rows and their index, a bad index, the precisions and closed forms refused, the _multi entries, one wave
+ * per coefficient -- is as for rimphony_ctx_set_tables_pitch. */
+int rimphony_ctx_set_tables_2d(rimphony_ctx *ctx, size_t n_tables, size_t n_nodes, double gamma_lo, double gamma_hi,
+                               size_t n_mu, const double *log_n);
+
 /* Work counters of the most recent batch call on this context (device-side
  * counts, read back synchronously): integrand samples, wave-wide evaluation
  * passes, inner QAG calls. */

@@ -105,6 +105,15 @@ extern "C" {
         n_mu: usize,
         log_g: *const c_double,
     ) -> c_int;
+    pub fn rimphony_ctx_set_tables_2d(
+        ctx: *mut rimphony_ctx,
+        n_tables: usize,
+        n_nodes: usize,
+        gamma_lo: c_double,
+        gamma_hi: c_double,
+        n_mu: usize,
+        log_n: *const c_double,
+    ) -> c_int;
 
     pub fn rimphony_last_work(ctx: *mut rimphony_ctx, out: *mut rimphony_work) -> c_int;
     pub fn rimphony_last_tail(ctx: *mut rimphony_ctx, out: *mut u64) -> c_int;
@@ -243,6 +252,26 @@ impl HipContext {
         let rc = unsafe {
             rimphony_ctx_set_tables_pitch(
                 self.raw, log_n.len() / n_nodes, n_nodes, gamma_lo, gamma_hi, log_n.as_ptr(), n_mu, log_g.as_ptr(),
+            )
+        };
+        if rc != RIMPHONY_OK {
+            return Err(error_text(rc));
+        }
+        Ok(())
+    }
+
+    /// A 2-D table set: `log_n` holds n_tables surfaces of n_nodes x n_mu values ln n(gamma, mu), mu fastest, at nodes
+    /// uniform in ln gamma and in mu = cos xi from -1 to +1 (include/rimphony_hip.h: rimphony_ctx_set_tables_2d).  Any
+    /// f(gamma, cos xi), a non-separable one included.
+    pub fn set_tables_2d(
+        &self, n_nodes: usize, gamma_lo: f64, gamma_hi: f64, n_mu: usize, log_n: &[f64],
+    ) -> Result<(), String> {
+        if n_nodes == 0 || n_mu == 0 || log_n.len() % (n_nodes * n_mu) != 0 {
+            return Err(error_text(RIMPHONY_EINVAL));
+        }
+        let rc = unsafe {
+            rimphony_ctx_set_tables_2d(
+                self.raw, log_n.len() / (n_nodes * n_mu), n_nodes, gamma_lo, gamma_hi, n_mu, log_n.as_ptr(),
             )
         };
         if rc != RIMPHONY_OK {

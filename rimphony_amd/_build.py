@@ -140,3 +140,14 @@ def build_beam_oracle():
     """The CPU oracle of an analytic power law times an exponential beam in cos xi (tests/support/beam_oracle.cpp): what the
     pitch tables are compared with.  Tests only."""
     return _build_dist_oracle("beam_oracle.cpp", "liboracle_beam.so")
+
+
+def build_tab2d_oracle():
+    """The same for 2-D table sets, ln n(gamma, mu) on a grid (tests/support/tab2d_oracle.cpp)."""
+    return _build_dist_oracle("tab2d_oracle.cpp", "liboracle_tab2d.so")
+
+
+def build_tilt_oracle():
+    """The CPU oracle of an analytic non-separable distribution, a power law whose index depends on the pitch angle
+    (tests/support/tilt_oracle.cpp): what the 2-D tables are compared with.  Tests only."""
+    return _build_dist_oracle("tilt_oracle.cpp", "liboracle_tilt.so")

@@ -115,6 +115,31 @@ def check_pitch_tables(gamma_lo, gamma_hi, log_n, log_g=None, n_mu=None):
     return t, g
 
 
+TAB_2D_MIN_MU, TAB_2D_MAX_MU, TAB_2D_MAX_CELLS = 8, 1024, 1 << 20
+
+
+def check_tables_2d(gamma_lo, gamma_hi, log_n):
+    """A 2-D table set as rimphony_ctx_set_tables_2d accepts it -> contiguous float64 [n_tables][n_nodes][n_mu] (a 2-D
+    array is one table); ValueError for what the library refuses with RIMPHONY_EINVAL (include/rimphony_hip.h)."""
+    t = np.asarray(log_n, dtype=np.float64)
+    if t.ndim == 2:
+        t = t[None]
+    if t.ndim != 3 or t.shape[0] < 1:
+        raise ValueError("log_n: expected [n_nodes][n_mu] or [n_tables][n_nodes][n_mu]")
+    t = np.ascontiguousarray(t)
+    if not TAB_MIN_NODES <= t.shape[1] <= TAB_MAX_NODES:
+        raise ValueError("log_n: %d gamma nodes, expected %d .. %d" % (t.shape[1], TAB_MIN_NODES, TAB_MAX_NODES))
+    if not TAB_2D_MIN_MU <= t.shape[2] <= TAB_2D_MAX_MU:
+        raise ValueError("log_n: %d mu nodes, expected %d .. %d" % (t.shape[2], TAB_2D_MIN_MU, TAB_2D_MAX_MU))
+    if t.shape[1] * t.shape[2] > TAB_2D_MAX_CELLS:
+        raise ValueError("log_n: %d x %d nodes per table, at most %d" % (t.shape[1], t.shape[2], TAB_2D_MAX_CELLS))
+    if not (math.isfinite(gamma_lo) and math.isfinite(gamma_hi) and 1.0 <= gamma_lo < gamma_hi):
+        raise ValueError("expected 1 <= gamma_lo < gamma_hi, got %r, %r" % (gamma_lo, gamma_hi))
+    if not np.isfinite(t).all():
+        raise ValueError("log_n: every value must be finite (a table cannot hold n = 0: floor ln n instead)")
+    return t
+
+
 class Context:
     """Owns a rimphony_ctx bound to one GPU."""
 
@@ -172,6 +197,20 @@ class Context:
         capi.check(self.lib.rimphony_ctx_set_tables(self.handle, t.shape[0], t.shape[1], float(gamma_lo), float(gamma_hi),
                                                     t.ctypes.data_as(ctypes.POINTER(ctypes.c_double))),
                    "rimphony_ctx_set_tables")
+
+    def set_tables_2d(self, gamma_lo, gamma_hi, log_n):
+        """The context's table set for kind TABULATED as surfaces: log_n [n_tables][n_nodes][n_mu] (a 2-D array is one
+        table) = ln n(gamma, mu) at nodes uniform in ln gamma from gamma_lo to gamma_hi and uniform in mu = cos xi from -1
+        to +1; f = norm exp(S) / (gamma^2 beta) with S the tensor-product natural cubic spline.  Replaces the previous set of
+        any form; None clears it.  Synchronous: the normalisation of every table is integrated here, once
+        (include/rimphony_hip.h: rimphony_ctx_set_tables_2d)."""
+        if log_n is None:
+            capi.check(self.lib.rimphony_ctx_set_tables_2d(self.handle, 0, 0, 1.0, 2.0, 0, None), "rimphony_ctx_set_tables_2d")
+            return
+        t = check_tables_2d(gamma_lo, gamma_hi, log_n)
+        capi.check(self.lib.rimphony_ctx_set_tables_2d(self.handle, t.shape[0], t.shape[1], float(gamma_lo), float(gamma_hi),
+                                                       t.shape[2], t.ctypes.data_as(ctypes.POINTER(ctypes.c_double))),
+                   "rimphony_ctx_set_tables_2d")
 
     # -- batched compute() -------------------------------------------------------
     def _check_input(self, name, t, n):
@@ -746,6 +785,34 @@ class TabulatedDistribution(_DistributionFunction):
 
     def full_calculation(self, ctx=None):
         return _TabulatedCalculator(self, ctx)
+
+
+class TabulatedDistribution2D(TabulatedDistribution):
+    """A distribution given as a surface: log_n [n_nodes][n_mu] = ln n(gamma, mu) at nodes uniform in ln gamma from
+    gamma_lo to gamma_hi and uniform in mu = cos xi from -1 to +1; f = norm exp(S(ln gamma, mu)) / (gamma^2 beta) inside
+    the table, 0 outside, S the tensor-product natural cubic spline (Context.set_tables_2d).  It need not be a product
+    n(gamma) g(mu).  Installs its table whenever it computes, as TabulatedDistribution does."""
+
+    def __init__(self, gamma_lo, gamma_hi, log_n):
+        self.gamma_lo, self.gamma_hi = float(gamma_lo), float(gamma_hi)
+        log_n = np.asarray(log_n, dtype=np.float64)
+        if log_n.ndim != 2:
+            raise ValueError("log_n: expected one table, [n_nodes][n_mu]")
+        self.log_n = check_tables_2d(self.gamma_lo, self.gamma_hi, log_n)
+
+    @classmethod
+    def from_function(cls, fn, gamma_lo, gamma_hi, n_nodes=512, n_mu=65):
+        """Tabulate n(gamma, mu) = fn(gamma[:, None], mu[None, :]) (vectorised, positive) on n_nodes nodes uniform in
+        ln gamma and n_mu nodes uniform in mu from -1 to +1."""
+        gamma = np.exp(np.linspace(math.log(gamma_lo), math.log(gamma_hi), int(n_nodes)))
+        gamma[0], gamma[-1] = gamma_lo, gamma_hi
+        mu = np.linspace(-1.0, 1.0, int(n_mu))
+        n = np.broadcast_to(np.asarray(fn(gamma[:, None], mu[None, :]), dtype=np.float64), (int(n_nodes), int(n_mu)))
+        return cls(gamma_lo, gamma_hi, np.log(n))
+
+    def _install(self, ctx):
+        ctx.set_tables_2d(self.gamma_lo, self.gamma_hi, self.log_n)
+        return ctx
 
 
 class _TabulatedCalculator(FullSynchrotronCalculator):

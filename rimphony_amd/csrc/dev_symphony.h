@@ -22,8 +22,11 @@ enum { DIST_POWER_LAW = 0, DIST_THERMAL_JUETTNER = 1, DIST_PITCHY_PL = 2, DIST_P
        // not a kind of the C ABI: the tabulated kind where the table set is KNOWN to have no pitch rows, so that the test for
        // one and everything behind it leave the code.  Same values as DIST_TABULATED on such a set, bit for bit; the two
        // persistent kernels are instantiated for it (rimphony_tab.hip), so that isotropic tables run the code they always ran.
-       DIST_TABULATED_ISO = 5 };
-constexpr bool dist_is_tab(int kind) { return kind == DIST_TABULATED || kind == DIST_TABULATED_ISO; }
+       DIST_TABULATED_ISO = 5,
+       // nor is this one: the tabulated kind where the set is a 2-D one, ln n(gamma, mu) on a grid (rim_tab_build_2d).  The host
+       // chooses it by the form of the installed set; a row is still RIMPHONY_TABULATED with a table index.
+       DIST_TABULATED_2D = 6 };
+constexpr bool dist_is_tab(int kind) { return kind == DIST_TABULATED || kind == DIST_TABULATED_ISO || kind == DIST_TABULATED_2D; }
 enum { STOKES_I = 0, STOKES_Q = 1, STOKES_V = 2 };
 enum { COEFF_EMISSION = 0, COEFF_ABSORPTION = 1, COEFF_FARADAY = 2 };
 
@@ -48,6 +51,13 @@ struct DistParams {
 enum { TAB_HDR_NTABLES = 0, TAB_HDR_NNODES = 1, TAB_HDR_GLO = 2, TAB_HDR_GHI = 3, TAB_HDR_ULO = 4, TAB_HDR_INVH = 5, TAB_HDR_H = 6,
        TAB_HDR_NMU = 7, TAB_HDR_DOUBLES = 8 };
 enum { TAB_PITCH_LAST = 0, TAB_PITCH_INVH = 1, TAB_PITCH_H = 2, TAB_PITCH_P = 3, TAB_PITCH_HDR = 4 };
+// A 2-D set, ln n(gamma, mu) on a grid (rim_tab_build_2d), marks itself by a NEGATIVE TAB_HDR_NMU, -n_mu.  After the header
+// come n_tables table headers of TAB_2D_HDR words {n_mu - 2, 1 / h_mu, h_mu, the table's normalisation, four spare words: a
+// table header is one 64-byte line and the node data stay aligned to one}, then [n_tables][n_nodes][n_mu][4] =
+// {S, S_u, S_mu, S_umu} of the tensor-product natural cubic spline S(u, mu) at the node, mu fastest: the nodes (i, j) and
+// (i, j + 1) are 64 contiguous bytes and a sample reads two such runs.
+enum { TAB_2D_LAST = 0, TAB_2D_INVH = 1, TAB_2D_H = 2, TAB_2D_NORM = 3, TAB_2D_HDR = 8 };
+RIM_DEV bool tab_set_is_2d(const double *hdr) { return hdr[TAB_HDR_NMU] < 0.; }
 
 // is `idx` (par[0] of a row) the index of a table of the set?
 RIM_DEV bool tab_row_ok(const double *hdr, double idx)
@@ -69,6 +79,21 @@ RIM_DEV void dist_prepare(DistParams &d, double norm)
         const bool ok = tab_row_ok(hdr, d.par[0]);
         const size_t nn = (size_t) hdr[TAB_HDR_NNODES];
         const size_t row = ok ? (size_t) d.par[0] : 0;
+        if (KIND == DIST_TABULATED_2D) {
+            // a 2-D set: par[0] the address of the table's header (the mu geometry, as a pitch row's), par[1] that of its
+            // node data; the rest as for the other two forms
+            const size_t nt = (size_t) hdr[TAB_HDR_NTABLES], nmu2 = (size_t) -hdr[TAB_HDR_NMU];
+            d.par[0] = rim_frombits((uint64_t) (uintptr_t) (hdr + TAB_HDR_DOUBLES + row * TAB_2D_HDR));
+            d.par[1] = rim_frombits((uint64_t) (uintptr_t) (hdr + TAB_HDR_DOUBLES + nt * TAB_2D_HDR + row * nn * nmu2 * 4));
+            d.par[2] = hdr[TAB_HDR_ULO];
+            d.par[3] = hdr[TAB_HDR_INVH];
+            d.par[4] = hdr[TAB_HDR_NNODES] - 2.;        // the index of the last interval in u
+            d.inv_gamma_cutoff = hdr[TAB_HDR_H];
+            d.inv_kappa_width = hdr[TAB_HDR_GLO];
+            d.neg_inverse_t = hdr[TAB_HDR_GHI];
+            d.norm = ok ? norm : RIM_NAN;
+            return;
+        }
         const size_t nmu = KIND == DIST_TABULATED_ISO ? 0 : (size_t) hdr[TAB_HDR_NMU];
         d.par[0] = 0.;
         if (nmu) {
@@ -146,7 +171,11 @@ RIM_DEV void tab_spline(const DistParams &d, double gamma, double &hval, double 
 // does the row have a pitch-angle factor?  (wave-uniform; DIST_TABULATED_ISO: known not to at compile time)
 RIM_DEV bool tab_has_pitch(const DistParams &d) { return rim_bits(d.par[0]) != 0; }
 template <int KIND>
-RIM_DEV bool tab_kind_has_pitch(const DistParams &d) { return KIND != DIST_TABULATED_ISO && tab_has_pitch(d); }
+RIM_DEV bool tab_kind_has_pitch(const DistParams &d)
+{
+    // (a 2-D table always has a live d f / d mu: it takes the general forms, as a pitch row does)
+    return KIND == DIST_TABULATED_2D || (KIND != DIST_TABULATED_ISO && tab_has_pitch(d));
+}
 
 // The spline G(mu) = ln g of a pitch row (tab_has_pitch) and dG/dmu at mu = cos xi.  The interval index is formed from a
 // clamped copy, as in tab_spline: a mu a rounding beyond +-1 extrapolates the end cubic, a NaN mu gives NaN, and every
@@ -174,6 +203,77 @@ RIM_DEV double tab_norm_integrand(const DistParams &d, double g)
     return rim_exp(hval);
 }
 
+// The same Hermite cubic from four values that do not sit side by side: the value and the derivative with respect to t.
+RIM_DEV void tab_hermite4(double y0, double m0, double y1, double m1, double h, double t, double &val, double &dvaldt)
+{
+    const double b0 = h * m0, b1 = h * m1, dy = y1 - y0;
+    const double c2 = 3. * dy - 2. * b0 - b1;
+    const double c3 = b0 + b1 - 2. * dy;
+    val = rim_fma(t, rim_fma(t, rim_fma(t, c3, c2), b0), y0);
+    dvaldt = rim_fma(t, rim_fma(t, 3. * c3, 2. * c2), b0);
+}
+
+// The surface S(u, mu) = ln n of a 2-D table at u = ln gamma, mu = cos xi, with dS/du and dS/dmu: bicubic Hermite on the
+// cell, the tensor-product natural spline whose node data {S, S_u, S_mu, S_umu} rim_tab_build_2d solved.  Along mu first,
+// on the cell's two u edges -- the value and the u slope, each with its mu derivative --, then along u through the two
+// edges.  Both interval indices are formed from clamped copies, as in tab_spline / tab_pitch_spline: a mu a rounding
+// beyond +-1 extrapolates the end cell, a NaN gives NaN, and every read stays inside the table.  Only rim_log, explicit
+// rim_fma and + - * /: gcc and hipcc agree to the bit.
+RIM_DEV void tab_bicubic(const DistParams &d, double gamma, double mu, double &sval, double &dsdu, double &dsdmu)
+{
+    const double *th = (const double *) (uintptr_t) rim_bits(d.par[0]);
+    const double *nodes = (const double *) (uintptr_t) rim_bits(d.par[1]);
+    const double mlast = th[TAB_2D_LAST], minvh = th[TAB_2D_INVH], mh = th[TAB_2D_H];
+    const double x = (rim_log(gamma) - d.par[2]) * d.par[3];
+    double xc = x;
+    if (!(xc >= 0.)) xc = 0.;
+    if (xc > d.par[4]) xc = d.par[4];
+    const long long i = (long long) xc;
+    const double tu = x - (double) i;
+    const double z = (mu + 1.) * minvh;
+    double zc = z;
+    if (!(zc >= 0.)) zc = 0.;
+    if (zc > mlast) zc = mlast;
+    const long long j = (long long) zc;
+    const double tm = z - (double) j;
+    const long long nmu = (long long) mlast + 2;
+    const double *a = nodes + (i * nmu + j) * 4;        // nodes (i, j), (i, j + 1)
+    const double *b = a + nmu * 4;                      // nodes (i + 1, j), (i + 1, j + 1)
+    // along mu on the edge u_i and on the edge u_{i+1}: the value v and the u slope w, d./dt_mu of each
+    double va, dva, wa, dwa, vb, dvb, wb, dwb;
+    tab_hermite4(a[0], a[2], a[4], a[6], mh, tm, va, dva);
+    tab_hermite4(a[1], a[3], a[5], a[7], mh, tm, wa, dwa);
+    tab_hermite4(b[0], b[2], b[4], b[6], mh, tm, vb, dvb);
+    tab_hermite4(b[1], b[3], b[5], b[7], mh, tm, wb, dwb);
+    // along u through the two edges: S and dS/dt_u from (v, w), dS/dt_mu from their mu derivatives
+    double dsdtu, dsdtm, unused;
+    tab_hermite4(va, wa, vb, wb, d.inv_gamma_cutoff, tu, sval, dsdtu);
+    tab_hermite4(dva, dwa, dvb, dwb, d.inv_gamma_cutoff, tu, dsdtm, unused);
+    dsdu = dsdtu * d.par[3];
+    dsdmu = dsdtm * minvh;
+}
+
+// nbar(gamma) = 1/2 int exp(S(ln gamma, mu)) dmu of a 2-D table: the integrand of its normalisation.  The 31-point Kronrod
+// rule (xgk, wgk: gk31_table.h) on every mu cell, summed in node order -- the rule P of a pitch row uses.
+RIM_DEV double tab_2d_norm_integrand(const DistParams &d, double g, const double *xgk, const double *wgk)
+{
+    const double *th = (const double *) (uintptr_t) rim_bits(d.par[0]);
+    const long long cells = (long long) th[TAB_2D_LAST] + 1;
+    const double h = th[TAB_2D_H];
+    double sum = 0.;
+    for (long long j = 0; j < cells; j++) {
+        const double half = 0.5 * h, centre = -1. + ((double) j + 0.5) * h;
+        double acc = 0.;
+        for (int k = 0; k < 31; k++) {
+            double sval, dsdu, dsdmu;
+            tab_bicubic(d, g, centre + half * xgk[k], sval, dsdu, dsdmu);
+            acc += wgk[k] * rim_exp(sval);
+        }
+        sum += half * acc;
+    }
+    return 0.5 * sum;
+}
+
 // calc_f and calc_f_derivatives of the tabulated distribution, one body for all three entries below:
 // f = norm n(gamma) g(mu) / (gamma^2 beta), 0 outside the table (the rule of power_law.rs:38,49), d f / d mu = f G'(mu).
 // A row without a pitch factor is isotropic: no further load, the arithmetic of n(gamma) alone, d f / d mu = +0.
@@ -182,6 +282,16 @@ RIM_DEV void tab_calc_f_both(const DistParams &d, double gamma, double cos_xi, d
 {
     f = 0.; dfdg = 0.; dfdcx = 0.;
     if (gamma < d.inv_kappa_width || gamma > d.neg_inverse_t) return;
+    if (KIND == DIST_TABULATED_2D) {
+        // f = norm exp(S(ln gamma, mu)) / (gamma^2 beta), d f / d mu = f S_mu: one exponential per sample
+        double sval, dsdu, dsdmu;
+        tab_bicubic(d, gamma, cos_xi, sval, dsdu, dsdmu);
+        const double beta2 = rim_sqrt(1. - rim_div_moderate(1., gamma * gamma));
+        f = d.norm * rim_exp(sval) / (gamma * gamma * beta2);
+        dfdg = f * (dsdu / gamma - 1. / gamma - gamma / (gamma * gamma - 1.));
+        dfdcx = f * dsdmu;
+        return;
+    }
     double hval, dhdu;
     tab_spline(d, gamma, hval, dhdu);
     const double beta = rim_sqrt(1. - rim_div_moderate(1., gamma * gamma));

@@ -209,7 +209,7 @@ extern "C" int rimphony_n_integral_batch_device(rimphony_ctx *c, int kind, const
     if (rc) return rc;
     const double *norm = rim_ctx_norm(c);
     double *spill = rim_ctx_spill(c);
-    rim_with_kind5(kind, [&](auto K) { hipLaunchKernelGGL(n_integral_kernel<decltype(K)::value>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pa, norm, count, d_n_lo, d_n_hi, d_out, spill); });
+    rim_with_kind5(rim_ctx_dist_kind(c, kind), [&](auto K) { hipLaunchKernelGGL(n_integral_kernel<decltype(K)::value>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pa, norm, count, d_n_lo, d_n_hi, d_out, spill); });
     HIP_TRY(hipGetLastError());
     return RIMPHONY_OK;
 }
@@ -231,7 +231,7 @@ extern "C" int rimphony_deriv_probe_batch_device(rimphony_ctx *c, int kind, cons
     if (rc) return rc;
     const double *norm = rim_ctx_norm(c);
     double *spill = rim_ctx_spill(c);
-    rim_with_kind5(kind, [&](auto K) { hipLaunchKernelGGL(deriv_probe_kernel<decltype(K)::value>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pa, norm, count, d_n_start, d_out, spill); });
+    rim_with_kind5(rim_ctx_dist_kind(c, kind), [&](auto K) { hipLaunchKernelGGL(deriv_probe_kernel<decltype(K)::value>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pa, norm, count, d_n_start, d_out, spill); });
     HIP_TRY(hipGetLastError());
     return RIMPHONY_OK;
 }
@@ -253,7 +253,7 @@ extern "C" int rimphony_gamma_contribution_batch_device(rimphony_ctx *c, int kin
     if (rc) return rc;
     const double *norm = rim_ctx_norm(c);
     double *spill = rim_ctx_spill(c);
-    rim_with_kind5(kind, [&](auto K) { hipLaunchKernelGGL(gamma_contribution_kernel<decltype(K)::value>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pa, norm, count, d_gamma, d_out, spill); });
+    rim_with_kind5(rim_ctx_dist_kind(c, kind), [&](auto K) { hipLaunchKernelGGL(gamma_contribution_kernel<decltype(K)::value>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pa, norm, count, d_gamma, d_out, spill); });
     HIP_TRY(hipGetLastError());
     return RIMPHONY_OK;
 }
@@ -295,7 +295,7 @@ extern "C" int rimphony_calc_f_batch_device(rimphony_ctx *c, int kind, const dou
     if (count == 0) return RIMPHONY_OK;
     const double *norm = rim_ctx_norm(c);
     const dim3 grid((unsigned) ((count + 63) / 64)), block(64);
-    rim_with_kind5(kind, [&](auto K) { hipLaunchKernelGGL(calc_f_kernel<decltype(K)::value>, grid, block, RIM_DYN_LDS, st, pa, norm, norm_override, count, d_gamma, d_cos_xi, d_f, d_dfdg, d_dfdcx); });
+    rim_with_kind5(rim_ctx_dist_kind(c, kind), [&](auto K) { hipLaunchKernelGGL(calc_f_kernel<decltype(K)::value>, grid, block, RIM_DYN_LDS, st, pa, norm, norm_override, count, d_gamma, d_cos_xi, d_f, d_dfdg, d_dfdcx); });
     HIP_TRY(hipGetLastError());
     return RIMPHONY_OK;
 }
@@ -395,7 +395,7 @@ extern "C" int rimphony_hey_element_batch_device(rimphony_ctx *c, int kind, cons
     if (count == 0) return RIMPHONY_OK;
     const double *norm = rim_ctx_norm(c);
     const dim3 grid((unsigned) ((count + 63) / 64)), block(64);
-    rim_with_kind5(kind, [&](auto K) { hipLaunchKernelGGL(hey_element_kernel<decltype(K)::value>, grid, block, RIM_DYN_LDS, st, pa, norm, qr, count, d_fixed, d_v, d_out); });
+    rim_with_kind5(rim_ctx_dist_kind(c, kind), [&](auto K) { hipLaunchKernelGGL(hey_element_kernel<decltype(K)::value>, grid, block, RIM_DYN_LDS, st, pa, norm, qr, count, d_fixed, d_v, d_out); });
     HIP_TRY(hipGetLastError());
     return RIMPHONY_OK;
 }
@@ -415,7 +415,7 @@ extern "C" int rimphony_hey_outer_batch_device(rimphony_ctx *c, int kind, const 
     rc = rim_wave_grid(c, count, 16, &grid);
     if (rc) return rc;
     const double *norm = rim_ctx_norm(c);
-    rim_with_kind5(kind, [&](auto K) { hipLaunchKernelGGL(hey_outer_kernel<decltype(K)::value>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pa, norm, qr, count, d_u, d_out, rim_ctx_spill(c)); });
+    rim_with_kind5(rim_ctx_dist_kind(c, kind), [&](auto K) { hipLaunchKernelGGL(hey_outer_kernel<decltype(K)::value>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pa, norm, qr, count, d_u, d_out, rim_ctx_spill(c)); });
     HIP_TRY(hipGetLastError());
     return RIMPHONY_OK;
 }

@@ -331,7 +331,7 @@ struct rimphony_ctx {
     unsigned long long hb_task;
     // what hipOccupancyMaxActiveBlocksPerMultiprocessor answered (-1: the query failed), asked once per context
     // (= per device) and instantiation: coop_kernel<P> by problem (0 Symphony, 1 Heyvaerts) and distribution kind,
-    int resident[2][6];             // (kind 4 twice: [4] a table set with pitch rows, [5] one without)
+    int resident[2][7];             // (kind 4 three times: [4] a table set with pitch rows, [5] one without, [6] a 2-D set)
     int resident_f32[4];            // ... the Symphony kernels' fp32-integrand variants,
     int resident_group[2][4];       // ... group_kernel<P> [Symphony groups / Faraday pair][kind]
     // 0: this context has the GPU to itself (it holds the device's lock file); 1: another context or process had
@@ -351,7 +351,7 @@ struct rimphony_ctx {
     RimDevBuf<char> d_gboard;       // [cap] GroupSlot + flag words behind
     // the table set of the tabulated distribution (rimphony_ctx_set_tables; dev_symphony.h has the layout), or empty
     RimDevBuf<double> d_tab;
-    bool tab_pitch = false;         // the set has pitch rows: which instantiation of the kind's persistent kernels runs
+    int tab_form = RIM_TAB_FORM_ISO;    // isotropic, with pitch rows or 2-D (tab_launch.h): which instantiation of the kind's kernels runs
 };
 
 // ---- last error (thread-local text; the codes are in rimphony_hip.h) ---------------------------
@@ -540,7 +540,7 @@ static int launch_norm(rimphony_ctx *c, int kind, size_t n, const ParamPtrs &pp,
     const unsigned grid = persistent_grid(c, n, 16);
     int rc = ensure_spill(c, grid);
     if (rc) return rc;
-    if (kind == RIMPHONY_TABULATED) rim_tab_launch_norm(grid, st, pp, n, d_norm, c->d_queue.p, c->d_spill.p);
+    if (kind == RIMPHONY_TABULATED) rim_tab_launch_norm(c->tab_form, grid, st, pp, n, d_norm, c->d_queue.p, c->d_spill.p);
     else rim_with_kind(kind, [&](auto K) {
         hipLaunchKernelGGL(norm_kernel<decltype(K)::value>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pp, n, d_norm, c->d_queue.p, c->d_spill.p);
     });
@@ -578,7 +578,7 @@ static int set_tables(rimphony_ctx *c, size_t n_tables, size_t n_nodes, double g
     // the previous set may still be read by the context's earlier work
     if (c->ev_batch_valid) HIP_TRY(hipEventSynchronize(c->ev_batch));
     c->d_tab.release();
-    c->tab_pitch = false;
+    c->tab_form = RIM_TAB_FORM_ISO;
     if (!n_tables) return RIMPHONY_OK;
     rc = c->d_tab.grow(blob.size(), blob.size() * sizeof(double), "the distribution tables");
     if (rc) return rc;
@@ -587,7 +587,7 @@ static int set_tables(rimphony_ctx *c, size_t n_tables, size_t n_nodes, double g
         c->d_tab.release();
         return RIMPHONY_EHIP;
     }
-    c->tab_pitch = log_g != nullptr;
+    c->tab_form = log_g ? RIM_TAB_FORM_PITCH : RIM_TAB_FORM_ISO;
     return RIMPHONY_OK;
 }
 
@@ -601,6 +601,45 @@ extern "C" int rimphony_ctx_set_tables_pitch(rimphony_ctx *c, size_t n_tables, s
                                              const double *log_n, size_t n_mu, const double *log_g)
 {
     return set_tables(c, n_tables, n_nodes, gamma_lo, gamma_hi, log_n, n_mu, log_g);
+}
+
+// A 2-D set: ln n(gamma, mu) on a grid.  The normalisation of each table is integrated here, once, on the device (one wave
+// per table: rimphony_tab.hip) and kept in the table's header, where the rows of a batch read it.  The new set is complete
+// on the device before the previous one is let go: a refusal or a failed allocation leaves the previous set in place.
+extern "C" int rimphony_ctx_set_tables_2d(rimphony_ctx *c, size_t n_tables, size_t n_nodes, double gamma_lo, double gamma_hi,
+                                          size_t n_mu, const double *log_n)
+{
+    if (!c) return RIMPHONY_EINVAL;
+    if (!n_tables) return set_tables(c, 0, 0, 0., 0., nullptr, 0, nullptr);
+    if (rim_tab_check_2d(n_tables, n_nodes, gamma_lo, gamma_hi, n_mu, log_n)) return RIMPHONY_EINVAL;
+    std::vector<double> blob;
+    try { rim_tab_build_2d(n_tables, n_nodes, gamma_lo, gamma_hi, n_mu, log_n, blob); }
+    catch (const std::bad_alloc &) { return RIMPHONY_ENOMEM; }
+    RimCtxScope scope(c, nullptr);
+    int rc = scope.enter();
+    if (rc) return rc;
+    if (c->ev_batch_valid) HIP_TRY(hipEventSynchronize(c->ev_batch));
+    RimDevBuf<double> fresh = { nullptr, 0 };
+    rc = fresh.grow(blob.size(), blob.size() * sizeof(double), "the distribution tables");
+    if (rc) return rc;
+    const unsigned grid = persistent_grid(c, n_tables, 16);
+    rc = ensure_spill(c, grid);
+    if (rc) { fresh.release(); return rc; }
+    hipError_t e = hipMemcpy(fresh.p, blob.data(), blob.size() * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        rim_tab_launch_table_norms(grid, nullptr, fresh.p, c->d_spill.p);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+    if (e != hipSuccess) {
+        rim_set_last_error("installing the distribution tables", hipGetErrorString(e));
+        fresh.release();
+        return RIMPHONY_EHIP;
+    }
+    c->d_tab.release();
+    c->d_tab = fresh;
+    c->tab_form = RIM_TAB_FORM_2D;
+    return RIMPHONY_OK;
 }
 
 static int rim_precision_check(const rimphony_ctx *c, int kind, int precision);
@@ -680,10 +719,10 @@ static PersistentKernel coop_kernel_of()
     k.early_squad = (unsigned) P::EARLY_SQUAD;
     return k;
 }
-static PersistentKernel rim_coop_kernel(int problem, int kind, int prec, bool tab_pitch)
+static PersistentKernel rim_coop_kernel(int problem, int kind, int prec, int tab_form)
 {
     if (kind == RIMPHONY_TABULATED) {       // (its kernels live in rimphony_tab.hip; no fp32 variant: refused at the entry)
-        const RimCoopKernelInfo t = rim_tab_coop_kernel(problem, tab_pitch);
+        const RimCoopKernelInfo t = rim_tab_coop_kernel(problem, tab_form);
         PersistentKernel k = {};
         k.fn = t.fn; k.waves = t.waves; k.early_help = t.early_help; k.early_squad = t.early_squad;
         return k;
@@ -763,9 +802,9 @@ static int launch_persistent(rimphony_ctx *c, const PersistentKernel &k, unsigne
 // One wave per (point, coefficient): coop_kernel<SymphonyProblem> (problem 0) or coop_kernel<HeyvaertsProblem> (1).
 static int launch_coop(rimphony_ctx *c, int problem, int kind, int prec, const SymArgs &a, hipStream_t st)
 {
-    PersistentKernel k = rim_coop_kernel(problem, kind, prec, c->tab_pitch);
+    PersistentKernel k = rim_coop_kernel(problem, kind, prec, c->tab_form);
     k.faraday = problem != 0;
-    const int cell = (kind == RIMPHONY_TABULATED && !c->tab_pitch) ? kind + 1 : kind;
+    const int cell = kind != RIMPHONY_TABULATED ? kind : c->tab_form == RIM_TAB_FORM_PITCH ? 4 : c->tab_form == RIM_TAB_FORM_ISO ? 5 : 6;
     k.resident = prec ? &c->resident_f32[kind] : &c->resident[problem][cell];
     k.spill = &c->d_spill;
     k.spill_doubles = SPILL_DOUBLES_PER_WAVE;
@@ -1349,7 +1388,7 @@ extern "C" int rimphony_gamma_integrand_batch_device(rimphony_ctx *c, int kind, 
     rc = single_point_norm(c, kind, params, st);
     if (rc) return rc;
     const dim3 grid((unsigned) ((count + 63) / 64)), block(64);
-    if (kind == RIMPHONY_TABULATED) rim_tab_launch_integrand(grid.x, st, pa, c->d_norm.p, count, d_n, d_gamma, d_out);
+    if (kind == RIMPHONY_TABULATED) rim_tab_launch_integrand(c->tab_form, grid.x, st, pa, c->d_norm.p, count, d_n, d_gamma, d_out);
     else rim_with_kind(kind, [&](auto K) { hipLaunchKernelGGL(integrand_kernel_n<decltype(K)::value>, grid, block, RIM_DYN_LDS, st, pa, c->d_norm.p, count, d_n, d_gamma, d_out); });
     HIP_TRY(hipGetLastError());
     return RIMPHONY_OK;
@@ -1370,6 +1409,10 @@ int rim_wave_grid(rimphony_ctx *c, size_t count, int waves_per_cu, unsigned *gri
     return ensure_spill(c, *grid);
 }
 const double *rim_ctx_norm(const rimphony_ctx *c) { return c->d_norm.p; }
+int rim_ctx_dist_kind(const rimphony_ctx *c, int kind)
+{
+    return (kind == RIMPHONY_TABULATED && c->tab_form == RIM_TAB_FORM_2D) ? (int) DIST_TABULATED_2D : kind;
+}
 double *rim_ctx_spill(const rimphony_ctx *c) { return c->d_spill.p; }
 
 extern "C" int rimphony_gamma_integral_batch_device(rimphony_ctx *c, int kind, const double *params,
@@ -1390,7 +1433,7 @@ extern "C" int rimphony_gamma_integral_batch_device(rimphony_ctx *c, int kind, c
     const unsigned grid = persistent_grid(c, count, 16);
     rc = ensure_spill(c, grid);
     if (rc) return rc;
-    if (kind == RIMPHONY_TABULATED) rim_tab_launch_gamma_integral(grid, st, pa, c->d_norm.p, count, d_n, d_out, c->d_spill.p);
+    if (kind == RIMPHONY_TABULATED) rim_tab_launch_gamma_integral(c->tab_form, grid, st, pa, c->d_norm.p, count, d_n, d_out, c->d_spill.p);
     else rim_with_kind(kind, [&](auto K) { hipLaunchKernelGGL(gamma_integral_kernel<decltype(K)::value>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pa, c->d_norm.p, count, d_n, d_out, c->d_spill.p); });
     HIP_TRY(hipGetLastError());
     return RIMPHONY_OK;

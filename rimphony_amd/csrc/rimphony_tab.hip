@@ -4,9 +4,62 @@
 // global loads -- a 4096-node table is 64 KB and stays in cache.  A table with a pitch-angle factor g(cos xi) reads four more
 // from its pitch row, whose address travels in par[0] (dev_symphony.h: dist_prepare<DIST_TABULATED>, tab_pitch_spline).
 // The two persistent kernels exist twice: for sets with pitch rows and, "no pitch row" known at compile time, for sets without.
+// A 2-D set, ln n(gamma, mu) on a grid, runs a third family (DIST_TABULATED_2D): a sample reads two runs of 64 bytes, the
+// nodes (i, j), (i, j + 1) and (i + 1, j), (i + 1, j + 1), and evaluates one bicubic (tab_bicubic).  Its normalisation is a
+// property of the table: tab2d_table_norm_kernel integrates it once, when the set is installed, and a row's normalisation
+// is a load (tab2d_row_norm_kernel).
 #include <hip/hip_runtime.h>
 #include "coop_kernel.h"
 #include "tab_launch.h"
+#include "gk31_table.h"
+
+static __device__ const double c_tab_xgk[32] = RIM_GK31_X;
+static __device__ const double c_tab_wgk[32] = RIM_GK31_WK;
+
+// The normalisation of every table of a 2-D set, one wave per table: norm = 1 / (4 pi int nbar dgamma) over the table's
+// range with the settings of norm_kernel (eps_rel 1e-8, 1000 subintervals), nbar(gamma) = 1/2 int exp(S) dmu by the Kronrod
+// rule on every mu cell (tab_2d_norm_integrand).  Written into the table's header; a quadrature that fails leaves NaN
+// there, for that table only.
+__global__ __launch_bounds__(64) void tab2d_table_norm_kernel(double *set, double *spill_base)
+{
+    __shared__ double s_tab[96];
+    __shared__ double s_store[RIM_ISTORE_DOUBLES(CAP_NORM)];
+    const GKLane g = gk_lane_init(s_tab);
+    const IStore st = istore_carve(s_store, CAP_NORM, spill_base + (size_t) blockIdx.x * SPILL_DOUBLES_PER_WAVE, SPILL_INNER);
+    __shared__ QagPark s_qpark;
+    if (threadIdx.x == 0) { s_qpark.ctr = WaveCounters{0, 0, 0}; s_qpark.hb = nullptr; }
+    const size_t n_tables = (size_t) set[TAB_HDR_NTABLES];
+    for (size_t t = blockIdx.x; t < n_tables; t += gridDim.x) {
+        DistParams d;
+        d.par[0] = (double) t;
+        d.par[1] = rim_frombits((uint64_t) (uintptr_t) set);
+        d.par[2] = 0.; d.par[3] = 0.; d.par[4] = 0.;
+        dist_prepare<DIST_TABULATED_2D>(d, RIM_NAN);
+        auto f = [&](double x, bool active) -> double {
+            return active ? tab_2d_norm_integrand(d, x, c_tab_xgk, c_tab_wgk) : 0.;
+        };
+        QagState q;
+        wave_qag(f, g, st, d.inv_kappa_width, d.neg_inverse_t, 0., 1e-8, 1000, q, &s_qpark);
+        double v = RIM_NAN;
+        if (q.status == QAG_SUCCESS) v = 1. / (2. * RIM_TWO_PI * q.result);
+        if (g.lane == 0) set[TAB_HDR_DOUBLES + t * TAB_2D_HDR + TAB_2D_NORM] = v;
+    }
+}
+
+// the normalisation of the rows of a batch on a 2-D set: the table's, or NaN for an index that names no table
+__global__ void tab2d_row_norm_kernel(ParamPtrs pp, size_t n, double *norm)
+{
+    const size_t i = (size_t) blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const double *set = pp.p[1];
+    const double idx = pp.p[0][i];
+    norm[i] = tab_row_ok(set, idx) ? set[TAB_HDR_DOUBLES + (size_t) idx * TAB_2D_HDR + TAB_2D_NORM] : RIM_NAN;
+}
+
+void rim_tab_launch_table_norms(unsigned grid, hipStream_t st, double *d_set, double *spill)
+{
+    hipLaunchKernelGGL(tab2d_table_norm_kernel, dim3(grid), dim3(64), RIM_DYN_LDS, st, d_set, spill);
+}
 
 template <class P>
 static RimCoopKernelInfo coop_info()
@@ -19,26 +72,41 @@ static RimCoopKernelInfo coop_info()
 
 // A set without pitch rows runs the instantiations that know so at compile time (DIST_TABULATED_ISO): the code isotropic
 // tables had before the pitch factor existed.  Same bits either way.
-RimCoopKernelInfo rim_tab_coop_kernel(int problem, bool pitch)
+RimCoopKernelInfo rim_tab_coop_kernel(int problem, int form)
 {
+    if (form == RIM_TAB_FORM_2D)
+        return problem ? coop_info<HeyvaertsProblem<DIST_TABULATED_2D>>() : coop_info<SymphonyProblem<DIST_TABULATED_2D>>();
+    const bool pitch = form == RIM_TAB_FORM_PITCH;
     if (problem) return pitch ? coop_info<HeyvaertsProblem<DIST_TABULATED>>() : coop_info<HeyvaertsProblem<DIST_TABULATED_ISO>>();
     return pitch ? coop_info<SymphonyProblem<DIST_TABULATED>>() : coop_info<SymphonyProblem<DIST_TABULATED_ISO>>();
 }
 
-void rim_tab_launch_norm(unsigned grid, hipStream_t st, const ParamPtrs &pp, size_t n, double *d_norm, unsigned long long *queue,
-                         double *spill)
+void rim_tab_launch_norm(int form, unsigned grid, hipStream_t st, const ParamPtrs &pp, size_t n, double *d_norm,
+                         unsigned long long *queue, double *spill)
 {
+    if (form == RIM_TAB_FORM_2D) {
+        hipLaunchKernelGGL(tab2d_row_norm_kernel, dim3((unsigned) ((n + 255) / 256)), dim3(256), RIM_DYN_LDS, st, pp, n, d_norm);
+        return;
+    }
     hipLaunchKernelGGL(norm_kernel<DIST_TABULATED>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pp, n, d_norm, queue, spill);
 }
 
-void rim_tab_launch_integrand(unsigned grid, hipStream_t st, const PointArgs &pa, const double *d_norm, size_t count,
+void rim_tab_launch_integrand(int form, unsigned grid, hipStream_t st, const PointArgs &pa, const double *d_norm, size_t count,
                               const double *d_n, const double *d_gamma, double *d_out)
 {
+    if (form == RIM_TAB_FORM_2D) {
+        hipLaunchKernelGGL(integrand_kernel_n<DIST_TABULATED_2D>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pa, d_norm, count, d_n, d_gamma, d_out);
+        return;
+    }
     hipLaunchKernelGGL(integrand_kernel_n<DIST_TABULATED>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pa, d_norm, count, d_n, d_gamma, d_out);
 }
 
-void rim_tab_launch_gamma_integral(unsigned grid, hipStream_t st, const PointArgs &pa, const double *d_norm, size_t count,
+void rim_tab_launch_gamma_integral(int form, unsigned grid, hipStream_t st, const PointArgs &pa, const double *d_norm, size_t count,
                                    const double *d_n, double *d_out, double *spill)
 {
+    if (form == RIM_TAB_FORM_2D) {
+        hipLaunchKernelGGL(gamma_integral_kernel<DIST_TABULATED_2D>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pa, d_norm, count, d_n, d_out, spill);
+        return;
+    }
     hipLaunchKernelGGL(gamma_integral_kernel<DIST_TABULATED>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pa, d_norm, count, d_n, d_out, spill);
 }

@@ -14,15 +14,21 @@ struct RimCoopKernelInfo {
     unsigned early_squad;
 };
 
+// the form of the installed table set, which chooses the instantiation: isotropic, with pitch rows, two-dimensional
+enum { RIM_TAB_FORM_ISO = 0, RIM_TAB_FORM_PITCH = 1, RIM_TAB_FORM_2D = 2 };
+
 // coop_kernel<SymphonyProblem<K>> (problem 0) or coop_kernel<HeyvaertsProblem<K>> (1); K = DIST_TABULATED for a table set with
-// pitch rows, DIST_TABULATED_ISO (dev_symphony.h) for one without
-RimCoopKernelInfo rim_tab_coop_kernel(int problem, bool pitch);
-// norm_kernel, integrand_kernel_n and gamma_integral_kernel of the kind: enqueue only, the caller asks hipGetLastError()
-void rim_tab_launch_norm(unsigned grid, hipStream_t st, const ParamPtrs &pp, size_t n, double *d_norm, unsigned long long *queue,
-                         double *spill);
-void rim_tab_launch_integrand(unsigned grid, hipStream_t st, const PointArgs &pa, const double *d_norm, size_t count,
+// pitch rows, DIST_TABULATED_ISO (dev_symphony.h) for one without, DIST_TABULATED_2D for a 2-D set
+RimCoopKernelInfo rim_tab_coop_kernel(int problem, int form);
+// norm_kernel, integrand_kernel_n and gamma_integral_kernel of the kind: enqueue only, the caller asks hipGetLastError().
+// (The rows of a 2-D set read their table's normalisation, which rim_tab_launch_table_norms computed when the set came in:
+// one wave per table, `grid` waves, each with its region of `spill`.)
+void rim_tab_launch_norm(int form, unsigned grid, hipStream_t st, const ParamPtrs &pp, size_t n, double *d_norm,
+                         unsigned long long *queue, double *spill);
+void rim_tab_launch_integrand(int form, unsigned grid, hipStream_t st, const PointArgs &pa, const double *d_norm, size_t count,
                               const double *d_n, const double *d_gamma, double *d_out);
-void rim_tab_launch_gamma_integral(unsigned grid, hipStream_t st, const PointArgs &pa, const double *d_norm, size_t count,
+void rim_tab_launch_gamma_integral(int form, unsigned grid, hipStream_t st, const PointArgs &pa, const double *d_norm, size_t count,
                                    const double *d_n, double *d_out, double *spill);
+void rim_tab_launch_table_norms(unsigned grid, hipStream_t st, double *d_set, double *spill);
 
 #endif

@@ -9,6 +9,12 @@
 // comes back as itself -- and P = 1/2 int g dmu of the spline, which the normalisation divides by.  The pitch rows follow
 // the gamma rows; an isotropic set is laid out as it always was.
 //
+// A set may instead be two-dimensional (rim_tab_check_2d, rim_tab_build_2d): ln n(gamma, mu) on a grid uniform in u and in
+// mu, interpolated by the tensor-product natural cubic spline S(u, mu).  Per node the four words {S, S_u, S_mu, S_umu} of
+// the bicubic Hermite form, all from the same Thomas sweep; a surface bilinear in (u, mu) comes back as itself, a sum
+// H(u) + G(mu) as the two 1-D splines.  The normalisation of a 2-D table is a word of its header, which the caller fills
+// (the library on the device, the tests' oracle with its own QAG): 0 as built.
+//
 // Plain C++ with the elementary functions of detmath.h, so that the library (hipcc's host pass) and the tests' table
 // oracle (g++) produce the same bits from the same table.
 #ifndef RIM_TAB_SPLINE_H
@@ -121,6 +127,71 @@ inline void rim_tab_build_pitch(size_t n_tables, size_t n_nodes, double gamma_lo
             sum += half * acc;
         }
         ph[TAB_PITCH_P] = 0.5 * sum;
+    }
+}
+
+#define RIM_TAB_2D_MIN_MU 8
+#define RIM_TAB_2D_MAX_MU 1024
+#define RIM_TAB_2D_MAX_CELLS ((size_t) 1 << 20)
+
+// a 2-D set: log_n [n_tables][n_nodes][n_mu], mu fastest.  0, or -1 for bad geometry or a non-finite value
+inline int rim_tab_check_2d(size_t n_tables, size_t n_nodes, double gamma_lo, double gamma_hi, size_t n_mu, const double *log_n)
+{
+    if (n_tables < 1 || n_nodes < RIM_TAB_MIN_NODES || n_nodes > RIM_TAB_MAX_NODES || !log_n) return -1;
+    if (n_mu < RIM_TAB_2D_MIN_MU || n_mu > RIM_TAB_2D_MAX_MU || n_nodes * n_mu > RIM_TAB_2D_MAX_CELLS) return -1;
+    if (n_tables > ((size_t) 1 << 40) / (n_nodes * n_mu)) return -1;
+    if (!rim_isfinite(gamma_lo) || !rim_isfinite(gamma_hi) || !(gamma_lo >= 1.) || !(gamma_lo < gamma_hi)) return -1;
+    for (size_t i = 0; i < n_tables * n_nodes * n_mu; i++)
+        if (!rim_isfinite(log_n[i])) return -1;
+    return 0;
+}
+
+// the 2-D set as one block of doubles (dev_symphony.h: TAB_2D_*); rim_tab_check_2d() has passed.  The order of the three
+// families of sweeps is fixed, because the bits depend on it: S_u along u for each mu column, S_mu along mu for each u row,
+// S_umu along u through the S_mu values of a column.
+inline void rim_tab_build_2d(size_t n_tables, size_t n_nodes, double gamma_lo, double gamma_hi, size_t n_mu, const double *log_n,
+                             std::vector<double> &blob)
+{
+    using namespace rim;
+    const double u_lo = rim_log(gamma_lo), u_hi = rim_log(gamma_hi);
+    const double h = (u_hi - u_lo) / (double) (n_nodes - 1);
+    const double hm = 2. / (double) (n_mu - 1);
+    const size_t per_table = n_nodes * n_mu * 4;
+    blob.assign((size_t) TAB_HDR_DOUBLES + n_tables * TAB_2D_HDR + n_tables * per_table, 0.);
+    blob[TAB_HDR_NTABLES] = (double) n_tables;
+    blob[TAB_HDR_NNODES] = (double) n_nodes;
+    blob[TAB_HDR_GLO] = gamma_lo;
+    blob[TAB_HDR_GHI] = gamma_hi;
+    blob[TAB_HDR_ULO] = u_lo;
+    blob[TAB_HDR_INVH] = 1. / h;
+    blob[TAB_HDR_H] = h;
+    blob[TAB_HDR_NMU] = -(double) n_mu;
+    const size_t longest = n_nodes > n_mu ? n_nodes : n_mu;
+    std::vector<double> y(longest), pairs(2 * longest), cp(longest), dp(longest);
+    for (size_t t = 0; t < n_tables; t++) {
+        double *th = blob.data() + TAB_HDR_DOUBLES + t * TAB_2D_HDR;
+        th[TAB_2D_LAST] = (double) (n_mu - 2);
+        th[TAB_2D_INVH] = 1. / hm;
+        th[TAB_2D_H] = hm;
+        const double *src = log_n + t * n_nodes * n_mu;
+        double *nodes = blob.data() + TAB_HDR_DOUBLES + n_tables * TAB_2D_HDR + t * per_table;
+        for (size_t j = 0; j < n_mu; j++) {
+            for (size_t i = 0; i < n_nodes; i++) y[i] = src[i * n_mu + j];
+            rim_tab_spline_row(y.data(), n_nodes, h, pairs.data(), cp.data(), dp.data());
+            for (size_t i = 0; i < n_nodes; i++) {
+                nodes[(i * n_mu + j) * 4] = pairs[2 * i];
+                nodes[(i * n_mu + j) * 4 + 1] = pairs[2 * i + 1];
+            }
+        }
+        for (size_t i = 0; i < n_nodes; i++) {
+            rim_tab_spline_row(src + i * n_mu, n_mu, hm, pairs.data(), cp.data(), dp.data());
+            for (size_t j = 0; j < n_mu; j++) nodes[(i * n_mu + j) * 4 + 2] = pairs[2 * j + 1];
+        }
+        for (size_t j = 0; j < n_mu; j++) {
+            for (size_t i = 0; i < n_nodes; i++) y[i] = nodes[(i * n_mu + j) * 4 + 2];
+            rim_tab_spline_row(y.data(), n_nodes, h, pairs.data(), cp.data(), dp.data());
+            for (size_t i = 0; i < n_nodes; i++) nodes[(i * n_mu + j) * 4 + 3] = pairs[2 * i + 1];
+        }
     }
 }
 

@@ -82,6 +82,16 @@ public:
                                             log_g.empty() ? nullptr : log_g.data()),
               "rimphony_ctx_set_tables_pitch");
     }
+    // A 2-D set: log_n [n_tables][n_nodes][n_mu], mu fastest, = ln n(gamma, mu) at nodes uniform in ln gamma and in mu from -1
+    // to +1 (rimphony_ctx_set_tables_2d): any f(gamma, cos xi), a non-separable one included.
+    void set_tables_2d(size_t n_tables, size_t n_nodes, double gamma_lo, double gamma_hi, size_t n_mu,
+                       const std::vector<double> &log_n) const
+    {
+        if (log_n.size() != n_tables * n_nodes * n_mu)
+            throw std::runtime_error("set_tables_2d: log_n must hold n_tables * n_nodes * n_mu values");
+        check(rimphony_ctx_set_tables_2d(ctx_, n_tables, n_nodes, gamma_lo, gamma_hi, n_mu, n_tables ? log_n.data() : nullptr),
+              "rimphony_ctx_set_tables_2d");
+    }
 private:
     rimphony_ctx *ctx_ = nullptr;
 };
@@ -330,6 +340,32 @@ public:
 private:
     double glo_, ghi_;
     std::vector<double> log_n_, log_g_;
+};
+
+// A distribution given as a surface: log_n [n_nodes][n_mu], mu fastest, = ln n(gamma, mu) at nodes uniform in ln gamma and
+// in mu = cos xi from -1 to +1; f = norm exp(S) / (gamma^2 beta) with S the tensor-product natural cubic spline, 0 outside
+// the table (include/rimphony_hip.h: rimphony_ctx_set_tables_2d).  Used as TabulatedDistribution is.
+class TabulatedDistribution2D : public DistributionFunction {
+protected:
+    int abi_kind() const override { return RIMPHONY_TABULATED; }
+    std::vector<double> abi_params() const override { return {0.}; }      // the table index
+public:
+    TabulatedDistribution2D(double gamma_lo, double gamma_hi, size_t n_nodes, size_t n_mu, std::vector<double> log_n)
+        : glo_(gamma_lo), ghi_(gamma_hi), n_nodes_(n_nodes), n_mu_(n_mu), log_n_(std::move(log_n)) {}
+    void install(const Context &ctx) const { ctx.set_tables_2d(1, n_nodes_, glo_, ghi_, n_mu_, log_n_); }
+    double calc_f(const Context &ctx, double gamma, double cos_xi) const
+    { install(ctx); return DistributionFunction::calc_f(ctx, gamma, cos_xi); }
+    std::array<double, 2> calc_f_derivatives(const Context &ctx, double gamma, double cos_xi) const
+    { install(ctx); return DistributionFunction::calc_f_derivatives(ctx, gamma, cos_xi); }
+    FullSynchrotronCalculator full_calculation(std::shared_ptr<Context> ctx) const
+    {
+        install(*ctx);
+        return FullSynchrotronCalculator(std::move(ctx), RIMPHONY_TABULATED, {0.});
+    }
+private:
+    double glo_, ghi_;
+    size_t n_nodes_, n_mu_;
+    std::vector<double> log_n_;
 };
 
 }  // namespace rimphony
