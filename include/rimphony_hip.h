@@ -170,8 +170,8 @@ int rimphony_ctx_set_tables(rimphony_ctx *ctx, size_t n_tables, size_t n_nodes, 
  * cubic; a NaN mu gives NaN.
  * A ln g that DIVERGES at mu = +-1 (sin^k xi: ln g = (k/2) ln(1 - mu^2)) is hostile to the spline.  Floored as
  * (k/2) ln(1 - mu^2 + 1e-6) with k = 2, 257 nodes give g to 5e-6 for |mu| < 0.9 but ring by order one at |mu| = 0.99, and
- * 1025 nodes still leave 3e-3 there: floor such shapes and use many nodes, or use RIMPHONY_PITCHY_PL / _KAPPA, which have
- * the factor in closed form.
+ * 1025 nodes still leave 3e-3 there: give such a factor as an exponent instead (rimphony_ctx_set_tables_pitchy below),
+ * or use RIMPHONY_PITCHY_PL / _KAPPA where their energy part serves.
  * The results are the reference's algorithms applied to the f given: its DistributionFunction trait accepts any
  * f(gamma, cos xi), one that is asymmetric in mu included; whether that is physically meaningful is the caller's matter.
  * Everything else -- rows and their index, the refusals, the kernels used -- is as for rimphony_ctx_set_tables. */
@@ -205,6 +205,30 @@ int rimphony_ctx_set_tables_pitch(rimphony_ctx *ctx, size_t n_tables, size_t n_n
  * per coefficient -- is as for rimphony_ctx_set_tables_pitch. */
 int rimphony_ctx_set_tables_2d(rimphony_ctx *ctx, size_t n_tables, size_t n_nodes, double gamma_lo, double gamma_hi,
                                size_t n_mu, const double *log_n);
+
+/* Tabulated distributions with a sin^k xi prefactor per table, the anisotropy of RIMPHONY_PITCHY_PL and _KAPPA
+ * (pitchy_pl.rs, pitchy_kappa.rs), which no pitch row can hold because its logarithm diverges at mu = +-1:
+ * f(gamma, mu) = norm n(gamma) sin^k xi g(mu) / (gamma^2 beta) inside the table, 0 outside;
+ * df/dmu = f (G'(mu) - k mu / sin^2 xi), df/dgamma as for the other forms;
+ * norm = 1 / (4 pi P int n dgamma), P = 1/2 int_{-1}^{+1} (1 - mu^2)^(k/2) g(mu) dmu.
+ *   log_n, n_mu, log_g   exactly as for rimphony_ctx_set_tables_pitch; log_g == NULL with n_mu == 0: no g;
+ *   sin_k   HOST, [n_tables]: the exponent k of each table, finite with 0 <= k <= 100 -- else RIMPHONY_EINVAL, checked on
+ *           the host, and the previous set stays.
+ * sin_k == NULL is rimphony_ctx_set_tables_pitch exactly: the same form, the same kernels, the same bits.  n_tables = 0
+ * clears the set.
+ * The factor is formed as the pitchy kinds form it, pow(sqrt(1 - mu^2), k), and df/dmu has the form of pitchy_pl.rs:56-61
+ * with what that form gives at |mu| = 1: f = 0 and df/dmu = NaN (0 x inf) for k > 0; for k = 0 the factor is 1 and the
+ * term 0 mu / 0 is NaN there too.  A mu a rounding beyond +-1 gives NaN (the square root of a negative number), as for
+ * the pitchy kinds.
+ * Without g, P is the closed form of the pitchy kinds, Gamma(3/2) Gamma(1 + k/2) / Gamma(3/2 + k/2) (pitchy_pl.rs:98).
+ * With g the call integrates P once per table on the device, adaptively (eps_rel 1e-8, 1000 subintervals; the integrand's
+ * derivative is singular at both ends for a non-integer k), and keeps it beside the table.  A table whose quadrature
+ * fails has a NaN P: its rows are NaN with RIMPHONY_ST_NORM_FAIL, the other tables are unaffected.
+ * A row is still RIMPHONY_TABULATED with one parameter, the table index.  A context holds one set at a time, of one form:
+ * installing this form replaces any other and the other way round.  Everything else -- a bad index, the precisions and
+ * closed forms refused, the _multi entries, one wave per coefficient -- is as for rimphony_ctx_set_tables_pitch. */
+int rimphony_ctx_set_tables_pitchy(rimphony_ctx *ctx, size_t n_tables, size_t n_nodes, double gamma_lo, double gamma_hi,
+                                   const double *log_n, size_t n_mu, const double *log_g, const double *sin_k);
 
 /* Work counters of the most recent batch call on this context (device-side
  * counts, read back synchronously): integrand samples, wave-wide evaluation

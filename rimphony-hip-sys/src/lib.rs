@@ -105,6 +105,17 @@ extern "C" {
         n_mu: usize,
         log_g: *const c_double,
     ) -> c_int;
+    pub fn rimphony_ctx_set_tables_pitchy(
+        ctx: *mut rimphony_ctx,
+        n_tables: usize,
+        n_nodes: usize,
+        gamma_lo: c_double,
+        gamma_hi: c_double,
+        log_n: *const c_double,
+        n_mu: usize,
+        log_g: *const c_double,
+        sin_k: *const c_double,
+    ) -> c_int;
     pub fn rimphony_ctx_set_tables_2d(
         ctx: *mut rimphony_ctx,
         n_tables: usize,
@@ -252,6 +263,28 @@ impl HipContext {
         let rc = unsafe {
             rimphony_ctx_set_tables_pitch(
                 self.raw, log_n.len() / n_nodes, n_nodes, gamma_lo, gamma_hi, log_n.as_ptr(), n_mu, log_g.as_ptr(),
+            )
+        };
+        if rc != RIMPHONY_OK {
+            return Err(error_text(rc));
+        }
+        Ok(())
+    }
+
+    /// The same with a sin^k xi prefactor per table: `sin_k` holds one exponent in [0, 100] per table; `log_g` may be
+    /// empty with n_mu = 0 (include/rimphony_hip.h: rimphony_ctx_set_tables_pitchy).
+    pub fn set_tables_pitchy(
+        &self, n_nodes: usize, gamma_lo: f64, gamma_hi: f64, log_n: &[f64], n_mu: usize, log_g: &[f64], sin_k: &[f64],
+    ) -> Result<(), String> {
+        if n_nodes == 0 || log_n.len() % n_nodes != 0 || log_g.len() != log_n.len() / n_nodes * n_mu
+            || sin_k.len() != log_n.len() / n_nodes
+        {
+            return Err(error_text(RIMPHONY_EINVAL));
+        }
+        let rc = unsafe {
+            rimphony_ctx_set_tables_pitchy(
+                self.raw, log_n.len() / n_nodes, n_nodes, gamma_lo, gamma_hi, log_n.as_ptr(), n_mu,
+                if log_g.is_empty() { std::ptr::null() } else { log_g.as_ptr() }, sin_k.as_ptr(),
             )
         };
         if rc != RIMPHONY_OK {

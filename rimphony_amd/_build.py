@@ -151,3 +151,14 @@ def build_tilt_oracle():
     """The CPU oracle of an analytic non-separable distribution, a power law whose index depends on the pitch angle
     (tests/support/tilt_oracle.cpp): what the 2-D tables are compared with.  Tests only."""
     return _build_dist_oracle("tilt_oracle.cpp", "liboracle_tilt.so")
+
+
+def build_tab_pitchy_oracle():
+    """The same for table sets with a sin^k xi prefactor per table (tests/support/tab_pitchy_oracle.cpp)."""
+    return _build_dist_oracle("tab_pitchy_oracle.cpp", "liboracle_tabpitchy.so")
+
+
+def build_pitchy_beam_oracle():
+    """The CPU oracle of an analytic power law times sin^k xi times an exponential beam in cos xi
+    (tests/support/pitchy_beam_oracle.cpp): what the tables with a sin^k prefactor are compared with.  Tests only."""
+    return _build_dist_oracle("pitchy_beam_oracle.cpp", "liboracle_pitchy_beam.so")

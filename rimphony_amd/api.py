@@ -115,6 +115,22 @@ def check_pitch_tables(gamma_lo, gamma_hi, log_n, log_g=None, n_mu=None):
     return t, g
 
 
+TAB_MAX_SIN_K = 100.0
+
+
+def check_sin_k(sin_k, n_tables):
+    """The exponents of a set's sin^k xi prefactors as rimphony_ctx_set_tables_pitchy accepts them -> contiguous float64
+    [n_tables] (a scalar serves every table); ValueError for what the library refuses with RIMPHONY_EINVAL."""
+    k = np.asarray(sin_k, dtype=np.float64)
+    if k.ndim == 0:
+        k = np.full(n_tables, float(k))
+    if k.ndim != 1 or k.shape[0] != n_tables:
+        raise ValueError("sin_k: expected a scalar or one value per table (%d), got shape %r" % (n_tables, k.shape))
+    if not (np.isfinite(k) & (k >= 0.0) & (k <= TAB_MAX_SIN_K)).all():
+        raise ValueError("sin_k: every exponent must be finite and in [0, %g]" % TAB_MAX_SIN_K)
+    return np.ascontiguousarray(k)
+
+
 TAB_2D_MIN_MU, TAB_2D_MAX_MU, TAB_2D_MAX_CELLS = 8, 1024, 1 << 20
 
 
@@ -175,16 +191,28 @@ class Context:
         return t.to(self._dev()).contiguous()
 
     # -- tabulated distributions ---------------------------------------------------
-    def set_tables(self, gamma_lo, gamma_hi, log_n, log_g=None):
+    def set_tables(self, gamma_lo, gamma_hi, log_n, log_g=None, sin_k=None):
         """The context's table set for kind TABULATED: log_n [n_tables][n_nodes] (or [n_nodes]) = ln n(gamma) at nodes
         uniform in ln gamma from gamma_lo to gamma_hi, n = dN/dgamma up to a factor.  Replaces the previous set; None
         clears it.  Synchronous.  Let n roll off to a negligible value at both ends: a table that ends at a sizeable n is a
         step in f, like the power law's gamma limits (include/rimphony_hip.h).
         log_g [n_tables][n_mu] (or [n_mu]) gives each table a pitch-angle factor g(mu), mu = cos xi: ln g at nodes uniform in
         mu from -1 to +1, f = norm n g / (gamma^2 beta).  Only the shape of a row matters.  A ln g that diverges at the
-        ends (sin^k xi) must be floored and needs many nodes, or use PITCHY_PL / PITCHY_KAPPA (include/rimphony_hip.h)."""
+        ends (sin^k xi) cannot be held in a row: give the exponent instead.
+        sin_k (a scalar, or one value per table, each in [0, 100]) multiplies each table by sin^k xi, the pitchy kinds'
+        own anisotropy, in closed form: f = norm n sin^k xi g / (gamma^2 beta), with or without log_g
+        (include/rimphony_hip.h: rimphony_ctx_set_tables_pitchy)."""
         if log_n is None:
             capi.check(self.lib.rimphony_ctx_set_tables(self.handle, 0, 0, 1.0, 2.0, None), "rimphony_ctx_set_tables")
+            return
+        if sin_k is not None:
+            t, g = check_pitch_tables(gamma_lo, gamma_hi, log_n, log_g)
+            k = check_sin_k(sin_k, t.shape[0])
+            dp = ctypes.POINTER(ctypes.c_double)
+            capi.check(self.lib.rimphony_ctx_set_tables_pitchy(self.handle, t.shape[0], t.shape[1], float(gamma_lo), float(gamma_hi),
+                                                               t.ctypes.data_as(dp), 0 if g is None else g.shape[1],
+                                                               None if g is None else g.ctypes.data_as(dp), k.ctypes.data_as(dp)),
+                       "rimphony_ctx_set_tables_pitchy")
             return
         if log_g is not None:
             t, g = check_pitch_tables(gamma_lo, gamma_hi, log_n, log_g)
@@ -751,29 +779,31 @@ class TabulatedDistribution(_DistributionFunction):
     to gamma_hi (n = dN/dgamma up to a factor; f = norm n / (gamma^2 beta) inside the table, 0 outside).  The library
     interpolates with the natural cubic spline in (ln gamma, ln n).  Isotropic, unless log_g [n_mu] = ln g(mu) at nodes
     uniform in mu = cos xi from -1 to +1 gives it a pitch-angle factor: f = norm n g / (gamma^2 beta), the natural cubic
-    spline in (mu, ln g) (Context.set_tables).  The object installs its table as the context's table
+    spline in (mu, ln g) (Context.set_tables).  sin_k, a number in [0, 100], multiplies it by sin^k xi in closed form.
+    The object installs its table as the context's table
     set whenever it computes, so two of them can share a context in turn; a batch over several tables uses
     Context.set_tables and kind TABULATED directly."""
 
-    def __init__(self, gamma_lo, gamma_hi, log_n, log_g=None):
+    def __init__(self, gamma_lo, gamma_hi, log_n, log_g=None, sin_k=None):
         self.gamma_lo, self.gamma_hi = float(gamma_lo), float(gamma_hi)
         self.log_n, self.log_g = check_pitch_tables(
             self.gamma_lo, self.gamma_hi, np.asarray(log_n, dtype=np.float64).reshape(1, -1),
             None if log_g is None else np.asarray(log_g, dtype=np.float64).reshape(1, -1))
+        self.sin_k = None if sin_k is None else check_sin_k(sin_k, 1)
 
     @classmethod
-    def from_function(cls, fn, gamma_lo, gamma_hi, n_nodes=4096, pitch_fn=None, n_mu=257):
+    def from_function(cls, fn, gamma_lo, gamma_hi, n_nodes=4096, pitch_fn=None, n_mu=257, sin_k=None):
         """Tabulate n(gamma) = fn(gamma) (vectorised, positive) on n_nodes nodes uniform in ln gamma and, if given,
-        g(mu) = pitch_fn(mu) (vectorised, positive) on n_mu nodes uniform in mu from -1 to +1."""
+        g(mu) = pitch_fn(mu) (vectorised, positive) on n_mu nodes uniform in mu from -1 to +1; sin_k as in the constructor."""
         gamma = np.exp(np.linspace(math.log(gamma_lo), math.log(gamma_hi), int(n_nodes)))
         gamma[0], gamma[-1] = gamma_lo, gamma_hi
         log_g = None
         if pitch_fn is not None:
             log_g = np.log(np.asarray(pitch_fn(np.linspace(-1.0, 1.0, int(n_mu))), dtype=np.float64))
-        return cls(gamma_lo, gamma_hi, np.log(np.asarray(fn(gamma), dtype=np.float64)), log_g)
+        return cls(gamma_lo, gamma_hi, np.log(np.asarray(fn(gamma), dtype=np.float64)), log_g, sin_k)
 
     def _install(self, ctx):
-        ctx.set_tables(self.gamma_lo, self.gamma_hi, self.log_n, self.log_g)
+        ctx.set_tables(self.gamma_lo, self.gamma_hi, self.log_n, self.log_g, self.sin_k)
         return ctx
 
     def _kind_params(self):

@@ -62,15 +62,17 @@ __global__ __launch_bounds__(64) void norm_kernel(ParamPtrs pp, size_t n, double
         DistParams d;
         load_params<KIND>(pp, i, d);
         // (the tabulated kind: dist_prepare replaces the table index in par[0], so the index is judged first)
-        const bool tab_ok = KIND != DIST_TABULATED || tab_row_ok(pp.p[1], d.par[0]);
+        constexpr bool TAB = KIND == DIST_TABULATED || KIND == DIST_TABULATED_PITCHY;
+        const bool tab_ok = !TAB || tab_row_ok(pp.p[1], d.par[0]);
         dist_prepare<KIND>(d, RIM_NAN);
 
         double lo, hi, epsrel, pa = 1.;
-        if (KIND == DIST_TABULATED) {
+        if (TAB) {
             // (a row whose index names no table: NaN, and with it RIMPHONY_ST_NORM_FAIL in every selected slot)
             if (!tab_ok) { if (g.lane == 0) norm[i] = RIM_NAN; continue; }
             lo = d.inv_kappa_width; hi = d.neg_inverse_t; epsrel = 1e-8;
             // a pitch row: P = 1/2 int g dmu of its header takes the place of the pitchy kinds' 2F1 (pitchy_pl.rs:98-111)
+            // (a sin^k set: every table has one, with the factor in it -- NaN where its quadrature failed)
             if (tab_has_pitch(d)) pa = ((const double *) (uintptr_t) rim_bits(d.par[0]))[TAB_PITCH_P];
         } else if (KIND == DIST_POWER_LAW) { lo = d.par[1]; hi = d.par[2]; epsrel = 1e-8; }
         else if (KIND == DIST_PITCHY_PL) { lo = d.par[2]; hi = d.par[3]; epsrel = 1e-8; pa = hyperg_2F1_at_1(0.5, -0.5 * d.par[1], 1.5); }
@@ -81,14 +83,14 @@ __global__ __launch_bounds__(64) void norm_kernel(ParamPtrs pp, size_t n, double
 
         // (the tabulated kind's integrand, n(gamma) of its table, is dev_symphony.h's: the tests' table oracle shares it)
         auto f = [&](double x, bool active) -> double {
-            if (KIND == DIST_TABULATED) return active ? tab_norm_integrand(d, x) : 0.;
+            if (TAB) return active ? tab_norm_integrand(d, x) : 0.;
             return active ? norm_integrand<KIND>(d, x) : 0.;
         };
         QagState q;
         wave_qag(f, g, st, lo, hi, 0., epsrel, 1000, q, &s_qpark);
         double v = RIM_NAN;
         if (q.status == QAG_SUCCESS) {
-            if (KIND == DIST_PITCHY_PL || KIND == DIST_PITCHY_KAPPA || (KIND == DIST_TABULATED && tab_has_pitch(d)))
+            if (KIND == DIST_PITCHY_PL || KIND == DIST_PITCHY_KAPPA || (TAB && tab_has_pitch(d)))
                 v = 1. / (2. * RIM_TWO_PI * pa * q.result);
             else v = 1. / (2. * RIM_TWO_PI * q.result);
         }

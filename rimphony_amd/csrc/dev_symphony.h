@@ -25,8 +25,14 @@ enum { DIST_POWER_LAW = 0, DIST_THERMAL_JUETTNER = 1, DIST_PITCHY_PL = 2, DIST_P
        DIST_TABULATED_ISO = 5,
        // nor is this one: the tabulated kind where the set is a 2-D one, ln n(gamma, mu) on a grid (rim_tab_build_2d).  The host
        // chooses it by the form of the installed set; a row is still RIMPHONY_TABULATED with a table index.
-       DIST_TABULATED_2D = 6 };
-constexpr bool dist_is_tab(int kind) { return kind == DIST_TABULATED || kind == DIST_TABULATED_ISO || kind == DIST_TABULATED_2D; }
+       DIST_TABULATED_2D = 6,
+       // nor this one: the tabulated kind where every table carries a sin^k xi prefactor (rim_tab_build_pitchy), with or
+       // without a pitch row.  Chosen by the host in the same way.
+       DIST_TABULATED_PITCHY = 7 };
+constexpr bool dist_is_tab(int kind)
+{
+    return kind == DIST_TABULATED || kind == DIST_TABULATED_ISO || kind == DIST_TABULATED_2D || kind == DIST_TABULATED_PITCHY;
+}
 enum { STOKES_I = 0, STOKES_Q = 1, STOKES_V = 2 };
 enum { COEFF_EMISSION = 0, COEFF_ABSORPTION = 1, COEFF_FARADAY = 2 };
 
@@ -58,6 +64,12 @@ enum { TAB_PITCH_LAST = 0, TAB_PITCH_INVH = 1, TAB_PITCH_H = 2, TAB_PITCH_P = 3,
 // (i, j + 1) are 64 contiguous bytes and a sample reads two such runs.
 enum { TAB_2D_LAST = 0, TAB_2D_INVH = 1, TAB_2D_H = 2, TAB_2D_NORM = 3, TAB_2D_HDR = 8 };
 RIM_DEV bool tab_set_is_2d(const double *hdr) { return hdr[TAB_HDR_NMU] < 0.; }
+// A set with a sin^k xi prefactor (rim_tab_build_pitchy): header and gamma rows as ever, TAB_HDR_NMU = n_mu (0: no g), then
+// per table TAB_PITCHY_PRE words {k, n_mu, two spare} and, straight behind them, what a pitch row is: TAB_PITCH_HDR words
+// {n_mu - 2, 1 / h_mu, h_mu, P = 1/2 int (1 - mu^2)^(k/2) g dmu} and, where there is a g, [n_mu][2] = {G_j, M_j}.  A row
+// carries the address of the pitch-row part, so tab_pitch_spline serves it as it is; k and n_mu sit at negative offsets
+// from there.  A table header is one 64-byte line.
+enum { TAB_PITCHY_PRE = 4, TAB_PITCHY_K = -4, TAB_PITCHY_NMU = -3 };
 
 // is `idx` (par[0] of a row) the index of a table of the set?
 RIM_DEV bool tab_row_ok(const double *hdr, double idx)
@@ -96,7 +108,12 @@ RIM_DEV void dist_prepare(DistParams &d, double norm)
         }
         const size_t nmu = KIND == DIST_TABULATED_ISO ? 0 : (size_t) hdr[TAB_HDR_NMU];
         d.par[0] = 0.;
-        if (nmu) {
+        if (KIND == DIST_TABULATED_PITCHY) {
+            // a sin^k set: every table has a header, whose pitch-row part par[0] names (k: TAB_PITCHY_K from there)
+            const size_t nt = (size_t) hdr[TAB_HDR_NTABLES];
+            d.par[0] = rim_frombits((uint64_t) (uintptr_t) (hdr + TAB_HDR_DOUBLES + nt * nn * 2 +
+                                                            row * (TAB_PITCHY_PRE + TAB_PITCH_HDR + nmu * 2) + TAB_PITCHY_PRE));
+        } else if (nmu) {
             const size_t nt = (size_t) hdr[TAB_HDR_NTABLES];
             d.par[0] = rim_frombits((uint64_t) (uintptr_t) (hdr + TAB_HDR_DOUBLES + nt * nn * 2 + row * (TAB_PITCH_HDR + nmu * 2)));
         }
@@ -173,8 +190,9 @@ RIM_DEV bool tab_has_pitch(const DistParams &d) { return rim_bits(d.par[0]) != 0
 template <int KIND>
 RIM_DEV bool tab_kind_has_pitch(const DistParams &d)
 {
-    // (a 2-D table always has a live d f / d mu: it takes the general forms, as a pitch row does)
-    return KIND == DIST_TABULATED_2D || (KIND != DIST_TABULATED_ISO && tab_has_pitch(d));
+    // (a 2-D table and one with a sin^k prefactor always have a live d f / d mu: they take the general forms, as a pitch
+    // row does)
+    return KIND == DIST_TABULATED_2D || KIND == DIST_TABULATED_PITCHY || (KIND != DIST_TABULATED_ISO && tab_has_pitch(d));
 }
 
 // The spline G(mu) = ln g of a pitch row (tab_has_pitch) and dG/dmu at mu = cos xi.  The interval index is formed from a
@@ -193,6 +211,16 @@ RIM_DEV void tab_pitch_spline(const DistParams &d, double mu, double &gval, doub
     double dgdt;
     tab_hermite(ph + TAB_PITCH_HDR + 2 * j, ph[TAB_PITCH_H], t, gval, dgdt);
     dgdmu = dgdt * invh;
+}
+
+// The integrand of P of a table with a sin^k prefactor and a pitch row: (1 - mu^2)^(k/2) g(mu), the factor formed as
+// tab_calc_f_both<DIST_TABULATED_PITCHY> forms it.  d: dist_prepare<DIST_TABULATED_PITCHY>'s.
+RIM_DEV double tab_pitchy_p_integrand(const DistParams &d, double mu)
+{
+    const double *ph = (const double *) (uintptr_t) rim_bits(d.par[0]);
+    double gval, dgdmu;
+    tab_pitch_spline(d, mu, gval, dgdmu);
+    return RimMath<0>::pow(rim_sqrt(1. - mu * mu), ph[TAB_PITCHY_K]) * rim_exp(gval);
 }
 
 // n(gamma) = exp(H(ln gamma)) of the table: the integrand of the normalisation (power_law.rs:95-96 for a table)
@@ -295,7 +323,18 @@ RIM_DEV void tab_calc_f_both(const DistParams &d, double gamma, double cos_xi, d
     double hval, dhdu;
     tab_spline(d, gamma, hval, dhdu);
     const double beta = rim_sqrt(1. - rim_div_moderate(1., gamma * gamma));
-    if (tab_kind_has_pitch<KIND>(d)) {
+    if (KIND == DIST_TABULATED_PITCHY) {
+        // f = norm n(gamma) sin^k xi g(mu) / (gamma^2 beta), d f / d mu = f (G' - k mu / sin^2 xi): the factor and its term as
+        // the pitchy kinds form them (pitchy_pl.rs:56-61), k a wave-uniform load; without a pitch row G = G' = 0
+        const double *ph = (const double *) (uintptr_t) rim_bits(d.par[0]);
+        const double k = ph[TAB_PITCHY_K];
+        const double sin_xi = rim_sqrt(1. - cos_xi * cos_xi);
+        const double pa_term = RimMath<0>::pow(sin_xi, k);
+        double gval = 0., dgdmu = 0.;
+        if (ph[TAB_PITCHY_NMU] != 0.) tab_pitch_spline(d, cos_xi, gval, dgdmu);
+        f = d.norm * pa_term * rim_exp(hval + gval) / (gamma * gamma * beta);
+        dfdcx = f * (dgdmu - k * cos_xi / (sin_xi * sin_xi));
+    } else if (tab_kind_has_pitch<KIND>(d)) {
         double gval, dgdmu;
         tab_pitch_spline(d, cos_xi, gval, dgdmu);
         f = d.norm * rim_exp(hval + gval) / (gamma * gamma * beta);

@@ -331,7 +331,7 @@ struct rimphony_ctx {
     unsigned long long hb_task;
     // what hipOccupancyMaxActiveBlocksPerMultiprocessor answered (-1: the query failed), asked once per context
     // (= per device) and instantiation: coop_kernel<P> by problem (0 Symphony, 1 Heyvaerts) and distribution kind,
-    int resident[2][7];             // (kind 4 three times: [4] a table set with pitch rows, [5] one without, [6] a 2-D set)
+    int resident[2][8];             // (kind 4 four times: [4] a table set with pitch rows, [5] one without, [6] a 2-D set, [7] sin^k)
     int resident_f32[4];            // ... the Symphony kernels' fp32-integrand variants,
     int resident_group[2][4];       // ... group_kernel<P> [Symphony groups / Faraday pair][kind]
     // 0: this context has the GPU to itself (it holds the device's lock file); 1: another context or process had
@@ -642,6 +642,45 @@ extern "C" int rimphony_ctx_set_tables_2d(rimphony_ctx *c, size_t n_tables, size
     return RIMPHONY_OK;
 }
 
+// A set with a sin^k xi prefactor per table.  Without g, P is the closed form rim_tab_build_pitchy set on the host; with g
+// it is integrated here, once, on the device (one wave per table: rimphony_tab.hip) into the table's header, where
+// norm_kernel reads it.  As for a 2-D set, the new set is complete on the device before the previous one is let go.
+extern "C" int rimphony_ctx_set_tables_pitchy(rimphony_ctx *c, size_t n_tables, size_t n_nodes, double gamma_lo, double gamma_hi,
+                                              const double *log_n, size_t n_mu, const double *log_g, const double *sin_k)
+{
+    if (!c) return RIMPHONY_EINVAL;
+    if (!sin_k || !n_tables) return set_tables(c, n_tables, n_nodes, gamma_lo, gamma_hi, log_n, n_mu, log_g);
+    if (rim_tab_check_pitchy(n_tables, n_nodes, gamma_lo, gamma_hi, log_n, n_mu, log_g, sin_k)) return RIMPHONY_EINVAL;
+    std::vector<double> blob;
+    try { rim_tab_build_pitchy(n_tables, n_nodes, gamma_lo, gamma_hi, log_n, n_mu, log_g, sin_k, blob); }
+    catch (const std::bad_alloc &) { return RIMPHONY_ENOMEM; }
+    RimCtxScope scope(c, nullptr);
+    int rc = scope.enter();
+    if (rc) return rc;
+    if (c->ev_batch_valid) HIP_TRY(hipEventSynchronize(c->ev_batch));
+    RimDevBuf<double> fresh = { nullptr, 0 };
+    rc = fresh.grow(blob.size(), blob.size() * sizeof(double), "the distribution tables");
+    if (rc) return rc;
+    const unsigned grid = persistent_grid(c, n_tables, 16);
+    rc = ensure_spill(c, grid);
+    if (rc) { fresh.release(); return rc; }
+    hipError_t e = hipMemcpy(fresh.p, blob.data(), blob.size() * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess && log_g) {
+        rim_tab_launch_pitchy_p(grid, nullptr, fresh.p, c->d_spill.p);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+    if (e != hipSuccess) {
+        rim_set_last_error("installing the distribution tables", hipGetErrorString(e));
+        fresh.release();
+        return RIMPHONY_EHIP;
+    }
+    c->d_tab.release();
+    c->d_tab = fresh;
+    c->tab_form = RIM_TAB_FORM_PITCHY;
+    return RIMPHONY_OK;
+}
+
 static int rim_precision_check(const rimphony_ctx *c, int kind, int precision);
 
 // The argument checks of the batch entries, in the order every entry applies them: the kind and the `head` pointers
@@ -804,7 +843,8 @@ static int launch_coop(rimphony_ctx *c, int problem, int kind, int prec, const S
 {
     PersistentKernel k = rim_coop_kernel(problem, kind, prec, c->tab_form);
     k.faraday = problem != 0;
-    const int cell = kind != RIMPHONY_TABULATED ? kind : c->tab_form == RIM_TAB_FORM_PITCH ? 4 : c->tab_form == RIM_TAB_FORM_ISO ? 5 : 6;
+    const int cell = kind != RIMPHONY_TABULATED ? kind : c->tab_form == RIM_TAB_FORM_PITCH ? 4 : c->tab_form == RIM_TAB_FORM_ISO ? 5 :
+                     c->tab_form == RIM_TAB_FORM_2D ? 6 : 7;
     k.resident = prec ? &c->resident_f32[kind] : &c->resident[problem][cell];
     k.spill = &c->d_spill;
     k.spill_doubles = SPILL_DOUBLES_PER_WAVE;
@@ -1411,7 +1451,8 @@ int rim_wave_grid(rimphony_ctx *c, size_t count, int waves_per_cu, unsigned *gri
 const double *rim_ctx_norm(const rimphony_ctx *c) { return c->d_norm.p; }
 int rim_ctx_dist_kind(const rimphony_ctx *c, int kind)
 {
-    return (kind == RIMPHONY_TABULATED && c->tab_form == RIM_TAB_FORM_2D) ? (int) DIST_TABULATED_2D : kind;
+    if (kind != RIMPHONY_TABULATED) return kind;
+    return c->tab_form == RIM_TAB_FORM_2D ? (int) DIST_TABULATED_2D : c->tab_form == RIM_TAB_FORM_PITCHY ? (int) DIST_TABULATED_PITCHY : kind;
 }
 double *rim_ctx_spill(const rimphony_ctx *c) { return c->d_spill.p; }
 

@@ -93,7 +93,8 @@ struct RimCtxScope {
 };
 const double *rim_ctx_norm(const rimphony_ctx *c);
 // the distribution kind whose instantiation serves `kind` on this context: DIST_TABULATED_2D (dev_symphony.h) for
-// RIMPHONY_TABULATED while a 2-D table set is installed, `kind` itself otherwise
+// RIMPHONY_TABULATED while a 2-D table set is installed, DIST_TABULATED_PITCHY while one with a sin^k prefactor is, `kind`
+// itself otherwise
 int rim_ctx_dist_kind(const rimphony_ctx *c, int kind);
 double *rim_ctx_spill(const rimphony_ctx *c);
 
@@ -111,14 +112,15 @@ auto rim_with_kind(int kind, F &&f)
     }
 }
 
-// The same for the translation units that also serve the tabulated distribution (kind 4, and 6 = DIST_TABULATED_2D, its
-// form for a 2-D table set: rim_ctx_dist_kind).  rimphony_group.hip keeps the four-way form: its kernels exist for the
+// The same for the translation units that also serve the tabulated distribution (kind 4, and 6 = DIST_TABULATED_2D and
+// 7 = DIST_TABULATED_PITCHY, its forms for a 2-D table set and for one with a sin^k prefactor: rim_ctx_dist_kind).  rimphony_group.hip keeps the four-way form: its kernels exist for the
 // four analytic kinds only.
 template <class F>
 auto rim_with_kind5(int kind, F &&f)
 {
     if (kind == 4) return f(std::integral_constant<int, 4>{});
     if (kind == 6) return f(std::integral_constant<int, 6>{});
+    if (kind == 7) return f(std::integral_constant<int, 7>{});
     return rim_with_kind(kind, f);
 }
 

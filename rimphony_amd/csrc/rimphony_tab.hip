@@ -8,6 +8,9 @@
 // nodes (i, j), (i, j + 1) and (i + 1, j), (i + 1, j + 1), and evaluates one bicubic (tab_bicubic).  Its normalisation is a
 // property of the table: tab2d_table_norm_kernel integrates it once, when the set is installed, and a row's normalisation
 // is a load (tab2d_row_norm_kernel).
+// A set with a sin^k xi prefactor runs a fourth family (DIST_TABULATED_PITCHY): k is one more wave-uniform load from the
+// table's header.  Where its tables have a g, P = 1/2 int (1 - mu^2)^(k/2) g dmu is integrated adaptively when the set is
+// installed (tab_pitchy_table_p_kernel): the integrand's derivative is singular at both ends for a non-integer k.
 #include <hip/hip_runtime.h>
 #include "coop_kernel.h"
 #include "tab_launch.h"
@@ -61,6 +64,38 @@ void rim_tab_launch_table_norms(unsigned grid, hipStream_t st, double *d_set, do
     hipLaunchKernelGGL(tab2d_table_norm_kernel, dim3(grid), dim3(64), RIM_DYN_LDS, st, d_set, spill);
 }
 
+// P of every table of a sin^k set with pitch rows, one wave per table: 1/2 int_-1^+1 (1 - mu^2)^(k/2) exp(G(mu)) dmu,
+// eps_rel 1e-8, 1000 subintervals.  Written into the table's header; a quadrature that fails leaves NaN there, for that
+// table only, and norm_kernel hands it on to the table's rows.
+__global__ __launch_bounds__(64) void tab_pitchy_table_p_kernel(double *set, double *spill_base)
+{
+    __shared__ double s_tab[96];
+    __shared__ double s_store[RIM_ISTORE_DOUBLES(CAP_NORM)];
+    const GKLane g = gk_lane_init(s_tab);
+    const IStore st = istore_carve(s_store, CAP_NORM, spill_base + (size_t) blockIdx.x * SPILL_DOUBLES_PER_WAVE, SPILL_INNER);
+    __shared__ QagPark s_qpark;
+    if (threadIdx.x == 0) { s_qpark.ctr = WaveCounters{0, 0, 0}; s_qpark.hb = nullptr; }
+    const size_t n_tables = (size_t) set[TAB_HDR_NTABLES];
+    for (size_t t = blockIdx.x; t < n_tables; t += gridDim.x) {
+        DistParams d;
+        d.par[0] = (double) t;
+        d.par[1] = rim_frombits((uint64_t) (uintptr_t) set);
+        d.par[2] = 0.; d.par[3] = 0.; d.par[4] = 0.;
+        dist_prepare<DIST_TABULATED_PITCHY>(d, RIM_NAN);
+        auto f = [&](double x, bool active) -> double { return active ? tab_pitchy_p_integrand(d, x) : 0.; };
+        QagState q;
+        wave_qag(f, g, st, -1., 1., 0., 1e-8, 1000, q, &s_qpark);
+        double v = RIM_NAN;
+        if (q.status == QAG_SUCCESS) v = 0.5 * q.result;
+        if (g.lane == 0) ((double *) (uintptr_t) rim_bits(d.par[0]))[TAB_PITCH_P] = v;
+    }
+}
+
+void rim_tab_launch_pitchy_p(unsigned grid, hipStream_t st, double *d_set, double *spill)
+{
+    hipLaunchKernelGGL(tab_pitchy_table_p_kernel, dim3(grid), dim3(64), RIM_DYN_LDS, st, d_set, spill);
+}
+
 template <class P>
 static RimCoopKernelInfo coop_info()
 {
@@ -76,6 +111,8 @@ RimCoopKernelInfo rim_tab_coop_kernel(int problem, int form)
 {
     if (form == RIM_TAB_FORM_2D)
         return problem ? coop_info<HeyvaertsProblem<DIST_TABULATED_2D>>() : coop_info<SymphonyProblem<DIST_TABULATED_2D>>();
+    if (form == RIM_TAB_FORM_PITCHY)
+        return problem ? coop_info<HeyvaertsProblem<DIST_TABULATED_PITCHY>>() : coop_info<SymphonyProblem<DIST_TABULATED_PITCHY>>();
     const bool pitch = form == RIM_TAB_FORM_PITCH;
     if (problem) return pitch ? coop_info<HeyvaertsProblem<DIST_TABULATED>>() : coop_info<HeyvaertsProblem<DIST_TABULATED_ISO>>();
     return pitch ? coop_info<SymphonyProblem<DIST_TABULATED>>() : coop_info<SymphonyProblem<DIST_TABULATED_ISO>>();
@@ -88,6 +125,10 @@ void rim_tab_launch_norm(int form, unsigned grid, hipStream_t st, const ParamPtr
         hipLaunchKernelGGL(tab2d_row_norm_kernel, dim3((unsigned) ((n + 255) / 256)), dim3(256), RIM_DYN_LDS, st, pp, n, d_norm);
         return;
     }
+    if (form == RIM_TAB_FORM_PITCHY) {
+        hipLaunchKernelGGL(norm_kernel<DIST_TABULATED_PITCHY>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pp, n, d_norm, queue, spill);
+        return;
+    }
     hipLaunchKernelGGL(norm_kernel<DIST_TABULATED>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pp, n, d_norm, queue, spill);
 }
 
@@ -98,6 +139,10 @@ void rim_tab_launch_integrand(int form, unsigned grid, hipStream_t st, const Poi
         hipLaunchKernelGGL(integrand_kernel_n<DIST_TABULATED_2D>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pa, d_norm, count, d_n, d_gamma, d_out);
         return;
     }
+    if (form == RIM_TAB_FORM_PITCHY) {
+        hipLaunchKernelGGL(integrand_kernel_n<DIST_TABULATED_PITCHY>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pa, d_norm, count, d_n, d_gamma, d_out);
+        return;
+    }
     hipLaunchKernelGGL(integrand_kernel_n<DIST_TABULATED>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pa, d_norm, count, d_n, d_gamma, d_out);
 }
 
@@ -106,6 +151,10 @@ void rim_tab_launch_gamma_integral(int form, unsigned grid, hipStream_t st, cons
 {
     if (form == RIM_TAB_FORM_2D) {
         hipLaunchKernelGGL(gamma_integral_kernel<DIST_TABULATED_2D>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pa, d_norm, count, d_n, d_out, spill);
+        return;
+    }
+    if (form == RIM_TAB_FORM_PITCHY) {
+        hipLaunchKernelGGL(gamma_integral_kernel<DIST_TABULATED_PITCHY>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pa, d_norm, count, d_n, d_out, spill);
         return;
     }
     hipLaunchKernelGGL(gamma_integral_kernel<DIST_TABULATED>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pa, d_norm, count, d_n, d_out, spill);

@@ -14,11 +14,12 @@ struct RimCoopKernelInfo {
     unsigned early_squad;
 };
 
-// the form of the installed table set, which chooses the instantiation: isotropic, with pitch rows, two-dimensional
-enum { RIM_TAB_FORM_ISO = 0, RIM_TAB_FORM_PITCH = 1, RIM_TAB_FORM_2D = 2 };
+// the form of the installed table set, which chooses the instantiation: isotropic, with pitch rows, two-dimensional, with a
+// sin^k xi prefactor (and pitch rows or none)
+enum { RIM_TAB_FORM_ISO = 0, RIM_TAB_FORM_PITCH = 1, RIM_TAB_FORM_2D = 2, RIM_TAB_FORM_PITCHY = 3 };
 
 // coop_kernel<SymphonyProblem<K>> (problem 0) or coop_kernel<HeyvaertsProblem<K>> (1); K = DIST_TABULATED for a table set with
-// pitch rows, DIST_TABULATED_ISO (dev_symphony.h) for one without, DIST_TABULATED_2D for a 2-D set
+// pitch rows, DIST_TABULATED_ISO (dev_symphony.h) for one without, DIST_TABULATED_2D for a 2-D set, DIST_TABULATED_PITCHY for one with a sin^k prefactor
 RimCoopKernelInfo rim_tab_coop_kernel(int problem, int form);
 // norm_kernel, integrand_kernel_n and gamma_integral_kernel of the kind: enqueue only, the caller asks hipGetLastError().
 // (The rows of a 2-D set read their table's normalisation, which rim_tab_launch_table_norms computed when the set came in:
@@ -30,5 +31,7 @@ void rim_tab_launch_integrand(int form, unsigned grid, hipStream_t st, const Poi
 void rim_tab_launch_gamma_integral(int form, unsigned grid, hipStream_t st, const PointArgs &pa, const double *d_norm, size_t count,
                                    const double *d_n, double *d_out, double *spill);
 void rim_tab_launch_table_norms(unsigned grid, hipStream_t st, double *d_set, double *spill);
+// P of every table of a sin^k set WITH pitch rows, into the tables' headers: one wave per table, as the line above
+void rim_tab_launch_pitchy_p(unsigned grid, hipStream_t st, double *d_set, double *spill);
 
 #endif

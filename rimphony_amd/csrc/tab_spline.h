@@ -15,6 +15,11 @@
 // H(u) + G(mu) as the two 1-D splines.  The normalisation of a 2-D table is a word of its header, which the caller fills
 // (the library on the device, the tests' oracle with its own QAG): 0 as built.
 //
+// A set may carry a sin^k xi prefactor per table, with or without g (rim_tab_check_pitchy, rim_tab_build_pitchy): the
+// layout of dev_symphony.h's TAB_PITCHY_*.  Without g, P = 1/2 int (1 - mu^2)^(k/2) dmu is the closed form of the pitchy
+// kinds, set here; with g it is 0 as built and the caller fills it (the library on the device, the tests' oracle with its
+// own QAG), as the normalisation of a 2-D table.
+//
 // Plain C++ with the elementary functions of detmath.h, so that the library (hipcc's host pass) and the tests' table
 // oracle (g++) produce the same bits from the same table.
 #ifndef RIM_TAB_SPLINE_H
@@ -127,6 +132,58 @@ inline void rim_tab_build_pitch(size_t n_tables, size_t n_nodes, double gamma_lo
             sum += half * acc;
         }
         ph[TAB_PITCH_P] = 0.5 * sum;
+    }
+}
+
+#define RIM_TAB_MAX_SIN_K 100.
+
+// rim_tab_check_pitch() for a set with a sin^k xi prefactor: sin_k [n_tables], every k finite and in [0, RIM_TAB_MAX_SIN_K]
+inline int rim_tab_check_pitchy(size_t n_tables, size_t n_nodes, double gamma_lo, double gamma_hi, const double *log_n,
+                                size_t n_mu, const double *log_g, const double *sin_k)
+{
+    if (rim_tab_check_pitch(n_tables, n_nodes, gamma_lo, gamma_hi, log_n, n_mu, log_g) || !sin_k) return -1;
+    for (size_t t = 0; t < n_tables; t++)
+        if (!rim_isfinite(sin_k[t]) || !(sin_k[t] >= 0.) || !(sin_k[t] <= RIM_TAB_MAX_SIN_K)) return -1;
+    return 0;
+}
+
+// 1/2 int (1 - mu^2)^(k/2) dmu = Gamma(3/2) Gamma(1 + k/2) / Gamma(3/2 + k/2): hyperg_2F1_at_1(0.5, -0.5 k, 1.5) of
+// coop_kernel.h (pitchy_pl.rs:98), the same operations in the same order, here for the host
+inline double rim_tab_sin_k_integral(double k)
+{
+    using namespace rim;
+    const double a = 0.5, b = -0.5 * k, c = 1.5;
+    const double lc = rim_lgamma_pos(c);
+    const double lcab = rim_lgamma_pos(c - a - b);
+    const double lca = rim_lgamma_pos(c - a);
+    const double lcb = rim_lgamma_pos(c - b);
+    return rim_exp(lc + lcab - lca - lcb);
+}
+
+// the set with a sin^k prefactor as one block of doubles (dev_symphony.h: TAB_PITCHY_*); rim_tab_check_pitchy() has passed
+inline void rim_tab_build_pitchy(size_t n_tables, size_t n_nodes, double gamma_lo, double gamma_hi, const double *log_n,
+                                 size_t n_mu, const double *log_g, const double *sin_k, std::vector<double> &blob)
+{
+    using namespace rim;
+    rim_tab_build(n_tables, n_nodes, gamma_lo, gamma_hi, log_n, blob);
+    if (!log_g) n_mu = 0;
+    const size_t base = blob.size(), stride = (size_t) TAB_PITCHY_PRE + TAB_PITCH_HDR + n_mu * 2;
+    blob.resize(base + n_tables * stride, 0.);
+    blob[TAB_HDR_NMU] = (double) n_mu;
+    const double h = n_mu ? 2. / (double) (n_mu - 1) : 0.;
+    std::vector<double> cp(n_mu), dp(n_mu);
+    for (size_t t = 0; t < n_tables; t++) {
+        double *ph = blob.data() + base + t * stride + TAB_PITCHY_PRE;
+        ph[TAB_PITCHY_K] = sin_k[t];
+        ph[TAB_PITCHY_NMU] = (double) n_mu;
+        if (!n_mu) {
+            ph[TAB_PITCH_P] = rim_tab_sin_k_integral(sin_k[t]);
+            continue;
+        }
+        ph[TAB_PITCH_LAST] = (double) (n_mu - 2);
+        ph[TAB_PITCH_INVH] = 1. / h;
+        ph[TAB_PITCH_H] = h;
+        rim_tab_spline_row(log_g + t * n_mu, n_mu, h, ph + TAB_PITCH_HDR, cp.data(), dp.data());
     }
 }
 

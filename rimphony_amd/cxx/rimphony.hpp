@@ -82,6 +82,18 @@ public:
                                             log_g.empty() ? nullptr : log_g.data()),
               "rimphony_ctx_set_tables_pitch");
     }
+    // The same with a sin^k xi prefactor per table: sin_k [n_tables], each in [0, 100] (rimphony_ctx_set_tables_pitchy);
+    // log_g may be empty with n_mu = 0.  f = norm n sin^k xi g / (gamma^2 beta).
+    void set_tables(size_t n_tables, size_t n_nodes, double gamma_lo, double gamma_hi, const std::vector<double> &log_n,
+                    size_t n_mu, const std::vector<double> &log_g, const std::vector<double> &sin_k) const
+    {
+        if (log_n.size() != n_tables * n_nodes) throw std::runtime_error("set_tables: log_n must hold n_tables * n_nodes values");
+        if (log_g.size() != n_tables * n_mu) throw std::runtime_error("set_tables: log_g must hold n_tables * n_mu values");
+        if (sin_k.size() != n_tables) throw std::runtime_error("set_tables: sin_k must hold n_tables values");
+        check(rimphony_ctx_set_tables_pitchy(ctx_, n_tables, n_nodes, gamma_lo, gamma_hi, n_tables ? log_n.data() : nullptr, n_mu,
+                                             log_g.empty() ? nullptr : log_g.data(), n_tables ? sin_k.data() : nullptr),
+              "rimphony_ctx_set_tables_pitchy");
+    }
     // A 2-D set: log_n [n_tables][n_nodes][n_mu], mu fastest, = ln n(gamma, mu) at nodes uniform in ln gamma and in mu from -1
     // to +1 (rimphony_ctx_set_tables_2d): any f(gamma, cos xi), a non-separable one included.
     void set_tables_2d(size_t n_tables, size_t n_nodes, double gamma_lo, double gamma_hi, size_t n_mu,
@@ -327,7 +339,14 @@ public:
         : glo_(gamma_lo), ghi_(gamma_hi), log_n_(std::move(log_n)) {}
     TabulatedDistribution(double gamma_lo, double gamma_hi, std::vector<double> log_n, std::vector<double> log_g)
         : glo_(gamma_lo), ghi_(gamma_hi), log_n_(std::move(log_n)), log_g_(std::move(log_g)) {}
-    void install(const Context &ctx) const { ctx.set_tables(1, log_n_.size(), glo_, ghi_, log_n_, log_g_.size(), log_g_); }
+    // ... times sin^k xi in closed form, 0 <= sin_k <= 100; log_g may be empty
+    TabulatedDistribution(double gamma_lo, double gamma_hi, std::vector<double> log_n, std::vector<double> log_g, double sin_k)
+        : glo_(gamma_lo), ghi_(gamma_hi), log_n_(std::move(log_n)), log_g_(std::move(log_g)), sin_k_{sin_k} {}
+    void install(const Context &ctx) const
+    {
+        if (sin_k_.empty()) ctx.set_tables(1, log_n_.size(), glo_, ghi_, log_n_, log_g_.size(), log_g_);
+        else ctx.set_tables(1, log_n_.size(), glo_, ghi_, log_n_, log_g_.size(), log_g_, sin_k_);
+    }
     double calc_f(const Context &ctx, double gamma, double cos_xi) const
     { install(ctx); return DistributionFunction::calc_f(ctx, gamma, cos_xi); }
     std::array<double, 2> calc_f_derivatives(const Context &ctx, double gamma, double cos_xi) const
@@ -339,7 +358,7 @@ public:
     }
 private:
     double glo_, ghi_;
-    std::vector<double> log_n_, log_g_;
+    std::vector<double> log_n_, log_g_, sin_k_;
 };
 
 // A distribution given as a surface: log_n [n_nodes][n_mu], mu fastest, = ln n(gamma, mu) at nodes uniform in ln gamma and
