@@ -118,6 +118,9 @@ typedef struct rimphony_ctx rimphony_ctx;
  * RIMPHONY_SYM_SOLO=1 runs the six Symphony coefficients one wave per (point, coefficient) as until round 2 instead of
  * the coefficients of a point in lock-step; RIMPHONY_FARADAY_GROUP=1 runs rho_Q and rho_V of a point in lock-step as well
  * (measured slower than one wave per coefficient, hence off).  Both for A/B measurements: the tables do not change.
+ * RIMPHONY_TAB_GROUP=1 / =0 runs the Symphony coefficients of RIMPHONY_TABULATED in lock-step on the group kernel / one wave
+ * per coefficient whatever the form of the table set (unset or negative: the form's default, at rimphony_ctx_set_tables);
+ * RIMPHONY_SYM_SOLO=1 wins.  The tables do not change either.
  * RIMPHONY_EARLY_SQUAD=<n> sets how many waves of the Faraday kernel's grid serve the longest outer quadratures of a
  * launch from its first cycle instead of fetching tasks (0: none; default 64 for the power-law family, 256 for pitchy kappa,
  * 0 for the other two distributions; only on launches with at least four tasks per wave, never in shared mode),
@@ -152,9 +155,14 @@ const char *rimphony_version(void);
  * the set.  A row of a batch names its table by index (the kind's one parameter, a double); a row whose index is not an
  * integer in [0, n_tables) gets a NaN normalisation: all its selected slots are NaN with RIMPHONY_ST_NORM_FAIL.  With no
  * table set every entry refuses the kind with RIMPHONY_EINVAL.  In the _multi entries each context uses its OWN table
- * set: give every context the same tables.  The kind runs one wave per coefficient (never the lock-step group kernels);
- * RIMPHONY_PRECISION_F32_INTEGRAND is RIMPHONY_ENOTSUP and the high-frequency closed forms RIMPHONY_EINVAL, as for every
- * kind without them. */
+ * set: give every context the same tables.  The six Symphony coefficients of a point run in lock-step on the group kernel,
+ * as for the analytic kinds, where that is the form's default -- every form, until profiles/tabulated_group_times.txt holds a measurement -- and one
+ * wave per coefficient otherwise; RIMPHONY_TAB_GROUP=1 / =0 in the environment of rimphony_ctx_create chooses for every form.  Same
+ * values, status words and work counters either way; rimphony_last_work().passes and the group statistics of
+ * rimphony_last_tail say which ran.  If the group kernel's workspace cannot be allocated (4.4 GB for a full grid) the batch
+ * runs one wave per coefficient instead of failing.  The Faraday pair always runs one wave per coefficient
+ * (RIMPHONY_FARADAY_GROUP does not apply to the kind).  RIMPHONY_PRECISION_F32_INTEGRAND is RIMPHONY_ENOTSUP and the
+ * high-frequency closed forms RIMPHONY_EINVAL, as for every kind without them. */
 int rimphony_ctx_set_tables(rimphony_ctx *ctx, size_t n_tables, size_t n_nodes, double gamma_lo, double gamma_hi,
                             const double *log_n);
 
@@ -174,7 +182,8 @@ int rimphony_ctx_set_tables(rimphony_ctx *ctx, size_t n_tables, size_t n_nodes, 
  * or use RIMPHONY_PITCHY_PL / _KAPPA where their energy part serves.
  * The results are the reference's algorithms applied to the f given: its DistributionFunction trait accepts any
  * f(gamma, cos xi), one that is asymmetric in mu included; whether that is physically meaningful is the caller's matter.
- * Everything else -- rows and their index, the refusals, the kernels used -- is as for rimphony_ctx_set_tables. */
+ * Everything else -- rows and their index, the refusals, the kernels used (the group kernel or one wave per coefficient for
+ * the Symphony coefficients: RIMPHONY_TAB_GROUP) -- is as for rimphony_ctx_set_tables. */
 int rimphony_ctx_set_tables_pitch(rimphony_ctx *ctx, size_t n_tables, size_t n_nodes, double gamma_lo, double gamma_hi,
                                   const double *log_n, size_t n_mu, const double *log_g);
 
@@ -201,8 +210,8 @@ int rimphony_ctx_set_tables_pitch(rimphony_ctx *ctx, size_t n_tables, size_t n_n
  * from about 20 ms (512 x 64 nodes) to a third of a second (1024 x 1024) per table.
  * A context holds one set at a time, of one form: installing a 2-D set replaces an isotropic or pitch set and the other way
  * round; n_tables = 0 clears the set.  A device allocation that fails is RIMPHONY_ENOMEM and the previous set stays.
- * Everything else -- rows and their index, a bad index, the precisions and closed forms refused, the _multi entries, one wave
- * per coefficient -- is as for rimphony_ctx_set_tables_pitch. */
+ * Everything else -- rows and their index, a bad index, the precisions and closed forms refused, the _multi entries, the
+ * choice between the group kernel and one wave per coefficient (RIMPHONY_TAB_GROUP) -- is as for rimphony_ctx_set_tables_pitch. */
 int rimphony_ctx_set_tables_2d(rimphony_ctx *ctx, size_t n_tables, size_t n_nodes, double gamma_lo, double gamma_hi,
                                size_t n_mu, const double *log_n);
 
@@ -226,7 +235,8 @@ int rimphony_ctx_set_tables_2d(rimphony_ctx *ctx, size_t n_tables, size_t n_node
  * fails has a NaN P: its rows are NaN with RIMPHONY_ST_NORM_FAIL, the other tables are unaffected.
  * A row is still RIMPHONY_TABULATED with one parameter, the table index.  A context holds one set at a time, of one form:
  * installing this form replaces any other and the other way round.  Everything else -- a bad index, the precisions and
- * closed forms refused, the _multi entries, one wave per coefficient -- is as for rimphony_ctx_set_tables_pitch. */
+ * closed forms refused, the _multi entries, the choice between the group kernel and one wave per coefficient
+ * (RIMPHONY_TAB_GROUP) -- is as for rimphony_ctx_set_tables_pitch. */
 int rimphony_ctx_set_tables_pitchy(rimphony_ctx *ctx, size_t n_tables, size_t n_nodes, double gamma_lo, double gamma_hi,
                                    const double *log_n, size_t n_mu, const double *log_g, const double *sin_k);
 

@@ -69,7 +69,7 @@ def build_hip(force=False, verbose=False):
         raise RuntimeError("hipcc not found: cannot build librimphony_hip.so")
     cmd = [hipcc] + HIPCC_FLAGS + [os.path.join(CSRC, "rimphony_hip.hip"), os.path.join(CSRC, "rimphony_diag.hip"),
                                     os.path.join(CSRC, "rimphony_group.hip"), os.path.join(CSRC, "rimphony_multi.hip"),
-                                    os.path.join(CSRC, "rimphony_tab.hip"),
+                                    os.path.join(CSRC, "rimphony_tab.hip"), os.path.join(CSRC, "rimphony_tab_group.hip"),
                                     "-ldl", "-o", LIB]
     if verbose:
         print(" ".join(cmd))

@@ -1,7 +1,7 @@
 // coop_common.h -- what the persistent, cooperative kernels of librimphony_hip.so share: the kernel arguments, the task
 // queue, the assist board (cooperative tail) and the per-task context loads.  Included by rimphony_hip.hip
-// (coop_kernel<P>: the Heyvaerts kernel, the solo Symphony kernels) and rimphony_group.hip (group_kernel: the
-// Symphony coefficients of a point in lock-step); they are separate translation units because hipcc's code
+// (coop_kernel<P>: the Heyvaerts kernel, the solo Symphony kernels) and, through group_kernel.h, rimphony_group.hip and
+// rimphony_tab_group.hip (group_kernel<P>: the Symphony coefficients of a point in lock-step); they are separate translation units because hipcc's code
 // generation for one big kernel depends on what else is in the unit (rimphony_internal.h).
 #ifndef RIM_COOP_COMMON_H
 #define RIM_COOP_COMMON_H

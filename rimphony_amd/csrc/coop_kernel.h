@@ -2,7 +2,8 @@
 // problems (SymphonyProblem<KIND>, HeyvaertsProblem<KIND>) and the two unit seams gamma_integral_kernel<KIND> and
 // integrand_kernel_n<KIND>.  rimphony_hip.hip instantiates them for the four analytic distributions, rimphony_tab.hip for
 // the tabulated one: separate translation units, because hipcc's code generation for one big kernel depends on what else
-// is in the unit (rimphony_internal.h) -- a fifth kind must not move the other four.
+// is in the unit (rimphony_internal.h) -- a fifth kind must not move the other four.  (group_kernel.h is the same split for
+// group_kernel<P>: rimphony_group.hip and rimphony_tab_group.hip.)
 #ifndef RIM_COOP_KERNEL_H
 #define RIM_COOP_KERNEL_H
 

@@ -1,4 +1,5 @@
-// group_launch.h -- what rimphony_hip.hip (host side) and rimphony_group.hip (the kernel) agree on.
+// group_launch.h -- what rimphony_hip.hip (host side) and the units of group_kernel<P> (group_kernel.h: rimphony_group.hip,
+// rimphony_tab_group.hip) agree on.
 #ifndef RIM_GROUP_LAUNCH_H
 #define RIM_GROUP_LAUNCH_H
 

@@ -247,7 +247,8 @@ struct RimDevBuf {
 
 // ---- the knobs: environment variables read once, when a context is created (DESIGN.md "Environment variables") ----
 struct RimKnobs {
-    long long no_assist, sym_solo, faraday_symphony_order, rounds, early_squad, early_min, f32_variant, faraday_group, owner_wait_us;
+    long long no_assist, sym_solo, faraday_symphony_order, rounds, early_squad, early_min, f32_variant, faraday_group, owner_wait_us,
+              tab_group;
 };
 enum RimKnobKind {
     KNOB_ON_1,          // on when the value starts with '1'
@@ -282,6 +283,8 @@ static const RimKnobDef RIM_KNOBS[] = {
       "=1: rho_Q and rho_V of a point in lock-step (measured slower: DESIGN.md section 5)" },
     { "RIMPHONY_OWNER_WAIT_US", KNOB_U64, &RimKnobs::owner_wait_us, 120000000, 0, 0,
       "microseconds an owner waits for its helpers before it recomputes a batch itself (test hook; 0 is accepted)" },
+    { "RIMPHONY_TAB_GROUP", KNOB_INT, &RimKnobs::tab_group, -1, INT_MIN, 1,
+      "Symphony slots of the tabulated kind: 1 = in lock-step on the group kernel, 0 = one wave per coefficient, for every form (unset or negative: the form's default)" },
 };
 
 static RimKnobs rim_read_knobs()
@@ -333,7 +336,7 @@ struct rimphony_ctx {
     // (= per device) and instantiation: coop_kernel<P> by problem (0 Symphony, 1 Heyvaerts) and distribution kind,
     int resident[2][8];             // (kind 4 four times: [4] a table set with pitch rows, [5] one without, [6] a 2-D set, [7] sin^k)
     int resident_f32[4];            // ... the Symphony kernels' fp32-integrand variants,
-    int resident_group[2][4];       // ... group_kernel<P> [Symphony groups / Faraday pair][kind]
+    int resident_group[2][8];       // ... group_kernel<P> [Symphony groups / Faraday pair][kind] (kind 4: the cells of `resident`; no Faraday pair)
     // 0: this context has the GPU to itself (it holds the device's lock file); 1: another context or process had
     // the device first -- smaller persistent grids, no cooperative tail (see rimphony_ctx_create)
     int shared_mode;
@@ -731,7 +734,7 @@ extern "C" int rimphony_batch_norm_device(rimphony_ctx *c, int kind, size_t n, c
 
 // ---- the persistent launch ----------------------------------------------------------------------------------------
 // What differs between the kernels that run as a persistent grid with a cooperative tail: coop_kernel<P> (one wave per
-// coefficient) and group_kernel<P> (rimphony_group.hip: the coefficients of a point in lock-step).
+// coefficient) and group_kernel<P> (group_kernel.h: the coefficients of a point in lock-step).
 struct PersistentKernel {
     const void *fn;                 // kernel entry: occupancy and attribute queries, launch
     int waves;                      // waves per SIMD of its launch bounds
@@ -864,7 +867,7 @@ static int launch_coop(rimphony_ctx *c, int problem, int kind, int prec, const S
     });
 }
 
-// The slots of a batch as (point, group) tasks (rimphony_group.hip).  Symphony: group 0 = the selected ones of
+// The slots of a batch as (point, group) tasks (group_kernel.h).  Symphony: group 0 = the selected ones of
 // {j_I, alpha_I, j_Q, alpha_Q}, group 1 = those of {j_V, alpha_V} (symphony_group.h); Faraday: the one group
 // {rho_Q, rho_V} (heyvaerts_group.h).
 static int launch_group(rimphony_ctx *c, int kind, const SymArgs &a, uint32_t coeff_mask, int faraday, hipStream_t st)
@@ -881,10 +884,15 @@ static int launch_group(rimphony_ctx *c, int kind, const SymArgs &a, uint32_t co
     }
     if (ga.ngroups == 0) return RIMPHONY_OK;
     PersistentKernel k = {};
-    k.fn = rim_group_kernel(kind, faraday);
+    // (the tabulated kind: one instantiation and one cell per form of the installed set, as in launch_coop; Symphony groups only)
+    const bool tab = kind == RIMPHONY_TABULATED;
+    if (tab && faraday) return RIMPHONY_ENOTSUP;
+    const int cell = !tab ? kind : c->tab_form == RIM_TAB_FORM_PITCH ? 4 : c->tab_form == RIM_TAB_FORM_ISO ? 5 :
+                     c->tab_form == RIM_TAB_FORM_2D ? 6 : 7;
+    k.fn = tab ? rim_tab_group_kernel(c->tab_form) : rim_group_kernel(kind, faraday);
     k.waves = rim_group_waves(faraday);
     k.faraday = faraday != 0;
-    k.resident = &c->resident_group[faraday ? 1 : 0][kind];
+    k.resident = &c->resident_group[faraday ? 1 : 0][cell];
     k.spill = &c->d_gspill;
     // (never less than the Symphony groups' size)
     k.spill_doubles = faraday && SPILL_HEYGROUP_DOUBLES_PER_WAVE > SPILL_GROUP_DOUBLES_PER_WAVE ? SPILL_HEYGROUP_DOUBLES_PER_WAVE
@@ -904,6 +912,21 @@ static int launch_group(rimphony_ctx *c, int kind, const SymArgs &a, uint32_t co
         (void) plan;
         return RIMPHONY_OK;
     });
+}
+
+// Where the Symphony slots of the tabulated distribution run when RIMPHONY_TAB_GROUP does not say: on the group kernel
+// (rimphony_tab_group.hip) or one wave per coefficient (rimphony_tab.hip), per form of the installed set.
+// NOT MEASURED yet (profiles/tabulated_group_times.txt): every form says "group" until that file has figures.
+static const bool RIM_TAB_GROUP_DEFAULT[4] = {
+    true,       // RIM_TAB_FORM_ISO
+    true,       // RIM_TAB_FORM_PITCH
+    true,       // RIM_TAB_FORM_2D
+    true,       // RIM_TAB_FORM_PITCHY
+};
+static bool rim_tab_runs_group(const rimphony_ctx *c)
+{
+    if (c->knobs.tab_group >= 0) return c->knobs.tab_group != 0;
+    return RIM_TAB_GROUP_DEFAULT[c->tab_form];
 }
 
 // `precision` of the batch entries.  F64 is the product.  F32_INTEGRAND (BASELINE configs[4]'s fp32-core integrand) is
@@ -1028,11 +1051,17 @@ static int batch_compute_locked(rimphony_ctx *c, int kind, size_t n, const doubl
             // the six Symphony coefficients with the fp32-core integrand (detmath.h); the Faraday pair below stays fp64
             // (kinds 2 and 3 were refused at the entry: RIMPHONY_ENOTSUP)
             rc = launch_coop(c, 0, kind, 1, a, st);
-        } else if (!c->knobs.sym_solo && kind != RIMPHONY_TABULATED) {
+        } else if (!c->knobs.sym_solo && (kind != RIMPHONY_TABULATED || rim_tab_runs_group(c))) {
             // the coefficients of a point that share their samples advance in lock-step on one wave
             rc = launch_group(c, kind, a, coeff_mask, 0, st);
+            if (rc == RIMPHONY_ENOMEM && kind == RIMPHONY_TABULATED) {
+                // no room for the group kernel's workspace (its spill region is 4.4 GB for a full grid, launch_persistent;
+                // nothing has been enqueued): the batch runs where the kind ran before it had group kernels, same bits
+                rim_clear_last_error();
+                rc = launch_coop(c, 0, kind, 0, a, st);
+            }
         } else {
-            // (always the tabulated distribution's kernel: the group kernel has the four analytic kinds only)
+            // (RIMPHONY_SYM_SOLO=1, or a form of the tabulated distribution whose Symphony slots are not on the group kernel)
             rc = launch_coop(c, 0, kind, 0, a, st);
         }
         if (rc) return rc;

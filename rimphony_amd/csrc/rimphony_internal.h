@@ -114,7 +114,8 @@ auto rim_with_kind(int kind, F &&f)
 
 // The same for the translation units that also serve the tabulated distribution (kind 4, and 6 = DIST_TABULATED_2D and
 // 7 = DIST_TABULATED_PITCHY, its forms for a 2-D table set and for one with a sin^k prefactor: rim_ctx_dist_kind).  rimphony_group.hip keeps the four-way form: its kernels exist for the
-// four analytic kinds only.
+// four analytic kinds only; the tabulated kind's group kernels are reached by the form of the table set (tab_launch.h:
+// rim_tab_group_kernel, rimphony_tab_group.hip).
 template <class F>
 auto rim_with_kind5(int kind, F &&f)
 {

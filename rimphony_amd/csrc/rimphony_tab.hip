@@ -1,6 +1,8 @@
 // rimphony_tab.hip -- the kernels of the tabulated distribution (RIMPHONY_TABULATED; gfx950 only): its normalisation,
-// the one-wave-per-coefficient Symphony and Faraday kernels and the two unit seams of coop_kernel.h.  The kind never runs
-// on the group kernel (rimphony_group.hip keeps its four instantiations); a sample reads its four spline words with plain
+// the one-wave-per-coefficient Symphony and Faraday kernels and the two unit seams of coop_kernel.h.  The kind's group
+// kernels -- the Symphony coefficients of a point in lock-step -- have a unit of their own, rimphony_tab_group.hip
+// (rimphony_group.hip keeps its four instantiations); which of the two runs the Symphony slots of a form is
+// RIM_TAB_GROUP_DEFAULT's and RIMPHONY_TAB_GROUP's matter (rimphony_hip.hip).  A sample reads its four spline words with plain
 // global loads -- a 4096-node table is 64 KB and stays in cache.  A table with a pitch-angle factor g(cos xi) reads four more
 // from its pitch row, whose address travels in par[0] (dev_symphony.h: dist_prepare<DIST_TABULATED>, tab_pitch_spline).
 // The two persistent kernels exist twice: for sets with pitch rows and, "no pitch row" known at compile time, for sets without.

@@ -1,0 +1,22 @@
+// rimphony_tab_group.hip -- group_kernel<P> (group_kernel.h) for the tabulated distribution (RIMPHONY_TABULATED; gfx950 only):
+// the Symphony coefficients of a parameter point in lock-step, one instantiation per form of the installed table set.  In a
+// group the table lookup of a sample -- the cubic of the energy table, the pitch row's, the bicubic of a 2-D set, the pow of
+// a sin^k prefactor -- is evaluated once for all members that need it (dev_symphony.h: gamma_integrand_f_terms calls
+// calc_f_both once), where one wave per coefficient evaluates it for every member again.
+//
+// A translation unit of its own: hipcc's code generation for a kernel of this size depends on what else is in the unit
+// (rimphony_internal.h), so these four must not move the four of rimphony_group.hip.  They live with the budget of those:
+// RIM_GROUP_WAVES waves per SIMD and the same LDS block.  The kind has no Faraday group (RIMPHONY_FARADAY_GROUP is
+// measured slower for the analytic kinds: DESIGN.md section 5).
+#include "group_kernel.h"
+#include "tab_launch.h"
+
+const void *rim_tab_group_kernel(int form)
+{
+    switch (form) {
+    case RIM_TAB_FORM_PITCH: return reinterpret_cast<const void *>(group_kernel<SymGroupProblem<DIST_TABULATED>>);
+    case RIM_TAB_FORM_2D: return reinterpret_cast<const void *>(group_kernel<SymGroupProblem<DIST_TABULATED_2D>>);
+    case RIM_TAB_FORM_PITCHY: return reinterpret_cast<const void *>(group_kernel<SymGroupProblem<DIST_TABULATED_PITCHY>>);
+    default: return reinterpret_cast<const void *>(group_kernel<SymGroupProblem<DIST_TABULATED_ISO>>);
+    }
+}

@@ -105,6 +105,9 @@ __device__ __forceinline__ IStore group_store(double *lds_base, int cap, double 
                         spill_base ? spill_base + (size_t) m * RIM_ISTORE_DOUBLES(gcap) : nullptr, spill_base ? gcap : 0);
 }
 
+__device__ __forceinline__ unsigned long long uni_u64(unsigned long long v)
+{ return ((unsigned long long) uni((unsigned) (v >> 32)) << 32) | uni((unsigned) v); }
+
 // position of entry idx in member M's stash, or -1
 __device__ __forceinline__ int stash_find(const GroupMember *M, int idx, int lane)
 {
@@ -456,7 +459,9 @@ __device__ __forceinline__ void wave_qag_group(F &f, const GKLane &g, double *in
 }
 
 // ---- gamma_integrand for the members of a group: the shared part once per sample --------------------------------
-template <int KIND>
+// FULL: the Bessel pair from the complete functions of the seam (SymOrderFull, dev_symphony.h) -- the second evaluation of
+// an entry one of whose samples had no value from sym_bessel_pair (sym_eval_group, the tabulated kinds).
+template <int KIND, bool FULL = false>
 struct SymGroupF {
     double s, cos_th, sin_th;       // wave-uniform
     const DistParams *d;
@@ -467,6 +472,7 @@ struct SymGroupF {
     // per lane, valid between shared() and the member() calls of a pass
     GiShared sh;
     double g2, f_em, f_ab;
+    bool nan_seen;                  // per lane: some sample's Bessel pair was a NaN (kept for the tabulated kinds only)
 
     __device__ __forceinline__ void shared(double x, bool active, bool second, unsigned members)
     {
@@ -482,7 +488,14 @@ struct SymGroupF {
         sh.gamma = 0.; sh.beta = 0.; sh.cos_xi = 0.; sh.mj = 0.; sh.njp = 0.;
         g2 = 0.; f_em = 0.; f_ab = 0.;
         if (active) {
-            sh = gamma_integrand_shared<0>(s, cos_th, sin_th, so, x);
+            if (FULL) {
+                SymOrderFull sof;
+                sof.n = so.n;
+                sh = gamma_integrand_shared<0>(s, cos_th, sin_th, sof, x);
+            } else {
+                sh = gamma_integrand_shared<0>(s, cos_th, sin_th, so, x);
+                if (dist_is_tab(KIND) && (sh.mj != sh.mj || sh.njp != sh.njp)) nan_seen = true;
+            }
             RIM_PROF_T(t_f);
             g2 = x * x;
 #if !defined(RIM_NO_FTERM_SHARE)           // (A/B knob of tools/build_variant.sh)
@@ -537,8 +550,38 @@ __device__ __forceinline__ void sym_eval_group(const SymPoint &pt, const DistPar
     f.n0 = uni(n0); f.n1 = uni(n1);
     f.fl0 = wv_readlane(fl_l, 0); f.fl1 = wv_readlane(fl_l, 32);
     f.slots = slots;
+    f.nan_seen = false;
     RIM_PROF_ADD(7, t_setup);
+    if (!dist_is_tab(KIND)) {
+        wave_qag_group(f, g, inner_lds, inner_spill, a0, b0, a1, b1, mask0, mask1, 1e-3, 5000, gp);
+        return;
+    }
+    // The tabulated kinds, whose tests hold this path to the oracle's sample counts on every row: what sym_eval_pair does
+    // (symphony_wave.h).  At |cos theta| ~ 1e-16 the argument of the Bessel pair is rounding noise far above n, where the
+    // reference still gets a number from pkgw_bessel_j and sym_bessel_pair has none.  Off the hot path: an entry that had
+    // such a sample is evaluated again for all its members, every sample through the complete functions (the same bits
+    // wherever both are defined, so a NaN that is the reference's own comes back as it was), and the wave's counters forget
+    // the first attempt (the members' records start afresh with every evaluation).  The counters wait in scalar registers:
+    // the park has no room that would not move the LDS block of the analytic kinds' kernels, which do without all this.
+    const unsigned long long c_samples = uni_u64(gp->ctr.samples), c_steps = uni_u64(gp->ctr.steps), c_qags = uni_u64(gp->ctr.inner_qags);
+    const unsigned long long c_member = uni_u64(gp->member_passes), c_filed = uni_u64(gp->stash_filed), c_used = uni_u64(gp->stash_used);
     wave_qag_group(f, g, inner_lds, inner_spill, a0, b0, a1, b1, mask0, mask1, 1e-3, 5000, gp);
+    if (wv_ballot(f.nan_seen)) {
+        if (lane == 0) {
+            gp->ctr.samples = c_samples; gp->ctr.steps = c_steps; gp->ctr.inner_qags = c_qags;
+            gp->member_passes = c_member; gp->stash_filed = c_filed; gp->stash_used = c_used;
+        }
+        wv_sync();
+        SymGroupF<KIND, true> f_full;
+        f_full.s = f.s; f_full.cos_th = f.cos_th; f_full.sin_th = f.sin_th;
+        f_full.d = &dist;
+        f_full.ord = gp->ord;
+        f_full.n0 = f.n0; f_full.n1 = f.n1;
+        f_full.fl0 = f.fl0; f_full.fl1 = f.fl1;
+        f_full.slots = slots;
+        f_full.nan_seen = false;
+        wave_qag_group(f_full, g, inner_lds, inner_spill, a0, b0, a1, b1, mask0, mask1, 1e-3, 5000, gp);
+    }
 }
 
 // value and status bits of member m's entry e after sym_eval_group (symphony.rs:375-380: an Err is a NaN sample)

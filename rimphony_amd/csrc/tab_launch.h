@@ -1,5 +1,5 @@
-// tab_launch.h -- what rimphony_hip.hip asks of rimphony_tab.hip, the translation unit that holds the kernels of the
-// tabulated distribution (coop_kernel.h says why they have a unit of their own).
+// tab_launch.h -- what rimphony_hip.hip asks of rimphony_tab.hip and rimphony_tab_group.hip, the translation units that hold
+// the kernels of the tabulated distribution (coop_kernel.h and group_kernel.h say why they have units of their own).
 #ifndef RIM_TAB_LAUNCH_H
 #define RIM_TAB_LAUNCH_H
 
@@ -21,6 +21,9 @@ enum { RIM_TAB_FORM_ISO = 0, RIM_TAB_FORM_PITCH = 1, RIM_TAB_FORM_2D = 2, RIM_TA
 // coop_kernel<SymphonyProblem<K>> (problem 0) or coop_kernel<HeyvaertsProblem<K>> (1); K = DIST_TABULATED for a table set with
 // pitch rows, DIST_TABULATED_ISO (dev_symphony.h) for one without, DIST_TABULATED_2D for a 2-D set, DIST_TABULATED_PITCHY for one with a sin^k prefactor
 RimCoopKernelInfo rim_tab_coop_kernel(int problem, int form);
+// group_kernel<SymGroupProblem<K>> of a form, K as above (rimphony_tab_group.hip): the Symphony coefficients of a point in
+// lock-step.  Launched with the grid and the arguments of the analytic kinds' (group_launch.h); the kind has no Faraday group.
+const void *rim_tab_group_kernel(int form);
 // norm_kernel, integrand_kernel_n and gamma_integral_kernel of the kind: enqueue only, the caller asks hipGetLastError().
 // (The rows of a 2-D set read their table's normalisation, which rim_tab_launch_table_norms computed when the set came in:
 // one wave per table, `grid` waves, each with its region of `spill`.)
