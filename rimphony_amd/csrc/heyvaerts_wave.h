@@ -207,6 +207,7 @@ __device__ __forceinline__ bool hey_post(const HeyPoint &pt, const GKLane &g, co
         if (hs) {
             const int hit = uni(hs->used) ? hey_stash_find(hs, T.oq.a1, T.oq.b2, lane) : -1;
             if (hit >= 0) {                                               // booked without a batch
+                T.batches -= 1;         // (nothing is evaluated, nothing waited for: no link of the task's chain, rimphony_last_tail)
                 wv_sync();
                 if (lane == 0) hs->hit = hit;
                 wv_sync();

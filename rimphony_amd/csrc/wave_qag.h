@@ -22,13 +22,20 @@
 //     error estimates, and 1 % of the thermal coefficients were NaN here and numbers in the reference's arithmetic.
 //     With the reference's terms the sums of subnormal samples are exact in any order: DESIGN.md section 2.)
 //   * The subinterval list (alist/blist/rlist/elist of the GSL workspace) lives
-//     in LDS, wave-private.  GSL's sorted `order` list is replaced by a
-//     wave-wide argmax over (error, insertion stamp): GSL inserts a new entry
-//     in front of entries of equal error, so "largest error, latest insertion
-//     wins ties" selects the same interval (exact while the list is shorter
-//     than limit/2 + 2, beyond which GSL stops keeping it fully sorted; the LDS
-//     capacity is far below that).  After the first bisection GSL always takes
-//     slot 0 (qpsrt's `last < 2` shortcut); so do we.
+//     in LDS, wave-private, and continues in the wave's spill region of global
+//     memory up to the GSL limit (IStore below).  GSL's sorted `order` list is
+//     replaced by a wave-wide argmax over (error, insertion stamp): GSL inserts
+//     a new entry in front of entries of equal error, so "largest error, latest
+//     insertion wins ties" selects the same interval.  That is exact while the
+//     list is shorter than limit/2 + 2; beyond, qpsrt keeps only the top
+//     limit + 1 - last entries of its list in order and the argmax is RELIED ON
+//     to pick what qpsrt's truncated list picks.  Lists do get that long (2050
+//     for the Faraday limit of 4096); the tests that hold the argmax to qpsrt
+//     there are test_gpu_parity.py::test_qag_selftest_past_half_the_limit (the
+//     inner store's picks, limits of 200 to 1000) and test_gpu_faraday_long.py
+//     (the outer store: lists of 3739, 3742 and 4096 entries against the
+//     oracle's bits and sample counts).  After the first bisection GSL always
+//     takes slot 0 (qpsrt's `last < 2` shortcut); so do we.
 //
 // All bookkeeping values are wave-uniform; they are computed redundantly by
 // every lane (there is no scalar fp64 unit) so no broadcast is needed.

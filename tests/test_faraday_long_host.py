@@ -1,0 +1,90 @@
+"""The committed fixture of the long Faraday outer quadratures (tests/golden/faraday_long_det.npz) against what it was made
+from: the row generator, the size classes it exists for, and the deterministic oracle's bits and counters.  No GPU: the GPU
+side is tests/test_gpu_faraday_long.py."""
+import os
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+import pytest
+
+import faraday_long as fl
+from rimphony_amd import workload
+
+
+def same_bits(a, b):
+    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    return (a.view(np.uint64) == b.view(np.uint64)) | (np.isnan(a) & np.isnan(b))
+
+
+def test_rows_are_the_generators():
+    """s, theta and the parameters stored with a row are what workload.make_rows gives for it today: a drift of the row
+    generator would leave the stored values describing other points than the tables have."""
+    f = fl.load()
+    assert set(f["config"]) <= set(fl.CONFIGS)
+    for i in range(len(f["row"])):
+        kind, _, s, theta, params = workload.make_rows(str(f["config"][i]), [int(f["row"][i])])
+        assert kind == fl.CONFIGS.index(str(f["config"][i]))
+        assert f["s"][i] == s[0] and f["theta"][i] == theta[0]
+        assert f["nparams"][i] == len(params)
+        assert (f["params"][i, :len(params)] == [p[0] for p in params]).all()
+        assert np.isnan(f["params"][i, len(params):]).all()
+
+
+def test_size_classes():
+    """The stored rows reach every length of the outer list at which the kernels change what they do: exactly 48 (the first
+    size with rounds) on pitchy-kappa, a FINITE value from a list that left LDS, two finite values from lists beyond
+    limit / 2 + 2 and two NaN from lists that ran to the limit -- and a 'mid' row (the ones a shared context runs) has no
+    list beyond limit / 2 + 2."""
+    f = fl.load()
+    size, rho = f["max_outer_size"].astype(np.int64), f["values"][:, 6:]
+    fin = np.isfinite(rho)
+    assert size[fl.index_of("cfg5_pitchykappa_8", 305)].max() == fl.ROUND_MIN
+    assert (fin & (size > fl.CAP_OUTER) & (size < fl.HALF)).sum() >= 1
+    assert (fin & (size > fl.HALF) & (size < fl.LIMIT)).sum() >= 2
+    assert (~fin & (size == fl.LIMIT)).sum() >= 2
+    assert size.max() <= fl.LIMIT
+    mid = f["cls"] == "mid"
+    assert set(f["cls"]) == {"mid", "limit"}
+    assert (size[mid] < fl.HALF).all() and (size[~mid].max(axis=1) > fl.HALF).all()
+    # the values the rows were chosen for (what the oracle gave when they were chosen)
+    assert f["values"][fl.index_of("cfg5_pitchykappa_8", 152), 6] == -3.7721374410253943e-07
+    assert f["values"][fl.index_of("cfg5_pitchykappa_8", 7887), 6] == -1.8067332095127741e-09
+    assert f["values"][fl.index_of("cfg2_powerlaw_8", 1176506), 6] == 6.720804758928926e-05
+
+
+@pytest.mark.parametrize("cfg", fl.CONFIGS)
+def test_every_kind_has_a_list_past_lds(cfg):
+    """Each of the four Faraday kernels is given a list that spills to global memory.  The pitchy power-law rows come from a
+    scan of the first 4096 rows of its table when the fixture is written; had the scan found none, the file says so in
+    `notes` and this one condition is skipped with that note."""
+    f = fl.load()
+    size = f["max_outer_size"].astype(np.int64)[f["config"] == cfg]
+    if cfg == "cfg4_pitchypl_8" and "no Faraday outer list longer" in str(f["notes"]):
+        pytest.skip(str(f["notes"]))
+    assert (size > fl.CAP_OUTER).any()
+
+
+def _recompute_and_compare(oracle, cls):
+    f = fl.load()
+    tasks = [(int(i), slot) for i in np.flatnonzero(f["cls"] == cls) for slot in range(8)]
+    with ThreadPoolExecutor(min(16, os.cpu_count() or 1)) as pool:
+        res = list(pool.map(lambda t: fl.recompute(oracle, *t), tasks))
+    for (i, slot), (v, c) in zip(tasks, res):
+        where = (str(f["config"][i]), int(f["row"][i]), slot)
+        assert same_bits(v, f["values"][i, slot]), (where, v, f["values"][i, slot])
+        assert c["integrand_evals"] == f["integrand_evals"][i, slot], where
+        if slot >= 6:
+            for name in ("max_outer_size", "outer_qag_calls", "inner_qag_calls"):
+                assert c[name] == f[name][i, slot - 6], (where, name)
+
+
+def test_mid_rows_reproduce(oracle):
+    """The 'mid' rows, all eight slots, computed again by the oracle: the stored bits and counters."""
+    _recompute_and_compare(oracle, "mid")
+
+
+@pytest.mark.slow
+@pytest.mark.skipif(not os.environ.get("RIMPHONY_SLOW"), reason="set RIMPHONY_SLOW=1 (minutes of CPU per row)")
+def test_limit_rows_reproduce(oracle):
+    """The same for the 'limit' rows: quadratures of up to 4096 subintervals, a minute or two of CPU each."""
+    _recompute_and_compare(oracle, "limit")

@@ -11,6 +11,7 @@ import sys
 import numpy as np
 import pytest
 
+import faraday_long as fl
 import oracle_bind
 from rimphony_amd import api, capi, workload
 
@@ -396,6 +397,18 @@ def test_early_help_and_faraday_order_change_no_bit(gpu_ctx):
             assert q[0] == q[2] and min(q[1], q[3], q[4]) > q[0], q
         else:
             assert len(set(q)) == 1, q
+        # ... and the table all six settings agree on is the ORACLE's where the outer quadratures are longest: the batch holds
+        # three rows of the committed fixture of long quadratures (tests/golden/faraday_long_det.npz; lists of 4096 and of
+        # 3739 entries), whose rho_Q and rho_V carry the deterministic oracle's bits
+        long_rows = fl.load()
+        start = 1131072 if cfg == "cfg2_powerlaw_8" else 0
+        held = [i for i in range(len(long_rows["row"]))
+                if long_rows["config"][i] == cfg and long_rows["cls"][i] == "limit" and start <= long_rows["row"][i] < start + 12288]
+        assert len(held) == (1 if cfg == "cfg2_powerlaw_8" else 2), held
+        for i in held:
+            at = int(long_rows["row"][i]) - start
+            assert s[at] == long_rows["s"][i] and th[at] == long_rows["theta"][i]
+            assert same_bits(ref[0][at, 6:], long_rows["values"][i, 6:]).all(), (cfg, at, ref[0][at, 6:], long_rows["values"][i, 6:])
 
 
 def test_kernel_variants_change_no_bit(gpu_ctx):

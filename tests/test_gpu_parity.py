@@ -191,6 +191,36 @@ def test_qag_selftest_bit_exact(gpu_ctx, oracle):
     report_mismatch("qag long-list abserr", err, np.array([r[2] for r in ref]))
 
 
+def qag_past_half_inputs():
+    """Family 4 (triangle waves with many kinks), the shape of the long-list leg above, 256 cases."""
+    rng = np.random.default_rng(6)
+    M = 256
+    a = rng.uniform(-1, 0, M); b = a + rng.uniform(2, 6, M)
+    p0 = rng.uniform(20, 120, M); p1 = np.exp(rng.uniform(-2, 2, M))
+    return np.full(M, 4, dtype=np.int32), p0, p1, a, b
+
+
+@pytest.mark.parametrize("epsrel,limit,min_between", [(1e-6, 200, 0), (1e-6, 400, 10), (1e-8, 1000, 10)])
+def test_qag_selftest_past_half_the_limit(gpu_ctx, oracle, epsrel, limit, min_between):
+    """GSL's qpsrt keeps its order list fully sorted only while the workspace holds fewer than limit / 2 + 2 intervals;
+    beyond, it sorts the top limit + 1 - last entries only, and the kernels go on picking by argmax over (error, stamp).
+    Limits small enough that many cases end AT the limit (status 11, every pick of the second half made in that regime) and,
+    on two of the three legs, others converge strictly between limit / 2 + 2 and the limit: result, error estimate, status
+    and size are the oracle's, whose qpsrt is qpsrt.c's (oracle/rimo_quad.c)."""
+    fam, p0, p1, a, b = qag_past_half_inputs()
+    ref = [oracle_bind.qag_selftest(oracle, 4, p0[i], p1[i], a[i], b[i], 0., epsrel, limit) for i in range(len(a))]
+    rst = np.array([r[0] for r in ref]); rsz = np.array([r[3] for r in ref])
+    at_limit = int((rst == 11).sum())
+    between = int(((rsz > limit // 2 + 2) & (rsz < limit)).sum())
+    print("limit %d: %d cases end at the limit, %d strictly between limit/2 + 2 and the limit" % (limit, at_limit, between))
+    assert at_limit >= 60 and between >= min_between, (at_limit, between)
+    res, err, qst, size = gpu_ctx.qag_selftest(fam, p0, p1, a, b, 0., epsrel, limit)
+    assert (qst == rst).all(), np.flatnonzero(qst != rst)[:5]
+    assert (size == rsz).all(), np.flatnonzero(size != rsz)[:5]
+    report_mismatch("qag past half the limit, result", res, np.array([r[1] for r in ref]))
+    report_mismatch("qag past half the limit, abserr", err, np.array([r[2] for r in ref]))
+
+
 @pytest.mark.parametrize("kind", [0, 1, 2, 3])
 def test_norm_bit_exact(gpu_ctx, oracle, kind):
     cfg = {0: "cfg2_powerlaw_8", 1: "cfg3_thermal_8", 2: "cfg4_pitchypl_8", 3: "cfg5_pitchykappa_8"}[kind]
