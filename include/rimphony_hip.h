@@ -240,6 +240,31 @@ int rimphony_ctx_set_tables_2d(rimphony_ctx *ctx, size_t n_tables, size_t n_node
 int rimphony_ctx_set_tables_pitchy(rimphony_ctx *ctx, size_t n_tables, size_t n_nodes, double gamma_lo, double gamma_hi,
                                    const double *log_n, size_t n_mu, const double *log_g, const double *sin_k);
 
+/* Tabulated distributions on gamma nodes of the caller's choosing, for what nodes uniform in ln gamma cannot resolve: a
+ * cold or mildly relativistic core, where ln gamma ~ gamma - 1 and the whole sub-relativistic range falls into the first few
+ * intervals of a uniform grid.  Everything else is rimphony_ctx_set_tables_pitchy's:
+ * f(gamma, mu) = norm n(gamma) sin^k xi g(mu) / (gamma^2 beta) inside [gamma[0], gamma[n_nodes - 1]], 0 outside.
+ *   gamma   HOST, [n_nodes], 8 <= n_nodes <= 65536: the nodes, shared by the tables of the set; finite,
+ *           1 <= gamma[0] < gamma[1] < ..., and their logarithms as the library forms them strictly increasing too (two
+ *           gamma a rounding apart can share a logarithm: refused);
+ *   log_n   HOST, [n_tables][n_nodes]: ln n at the nodes;
+ *   n_mu, log_g   as for rimphony_ctx_set_tables_pitch, or 0 / NULL: no g;
+ *   sin_k   HOST, [n_tables], each finite in [0, 100], or NULL: no prefactor (k = 0).
+ * RIMPHONY_EINVAL, checked on the host, for a null gamma or log_n, a non-finite value, gamma[0] < 1, too few or too many
+ * nodes, nodes or logarithms not strictly increasing, and whatever rimphony_ctx_set_tables_pitchy refuses in log_g, n_mu and
+ * sin_k: the previous set stays.  n_tables = 0 clears the set.  The call replaces a set of any form and a set of any form
+ * replaces it.
+ * The interpolant is the natural cubic spline through (ln gamma_j, ln n_j), solved on the host on the non-uniform nodes; a
+ * straight line in (ln gamma, ln n) comes back as itself.  A sample finds its interval -- the last node at or below it,
+ * whatever the search does to get there -- through a guide of cells uniform in ln gamma and a bisection inside the cell:
+ * two guide words and at most 16 node words, 0 to 2 where the nodes are about as dense as the cells.
+ * An isotropic set of this form (no g, no sin_k) is computed with the general absorption term, as a set with k = 0 is:
+ * the same numbers as the isotropic form to the rounding of the extra term, not the same bits.
+ * With g, P is integrated on the device when the set is installed, as for rimphony_ctx_set_tables_pitchy.  A row is still
+ * RIMPHONY_TABULATED with one parameter, the table index; everything else is as for rimphony_ctx_set_tables_pitchy. */
+int rimphony_ctx_set_tables_grid(rimphony_ctx *ctx, size_t n_tables, size_t n_nodes, const double *gamma, const double *log_n,
+                                 size_t n_mu, const double *log_g, const double *sin_k);
+
 /* Work counters of the most recent batch call on this context (device-side
  * counts, read back synchronously): integrand samples, wave-wide evaluation
  * passes, inner QAG calls. */

@@ -116,6 +116,16 @@ extern "C" {
         log_g: *const c_double,
         sin_k: *const c_double,
     ) -> c_int;
+    pub fn rimphony_ctx_set_tables_grid(
+        ctx: *mut rimphony_ctx,
+        n_tables: usize,
+        n_nodes: usize,
+        gamma: *const c_double,
+        log_n: *const c_double,
+        n_mu: usize,
+        log_g: *const c_double,
+        sin_k: *const c_double,
+    ) -> c_int;
     pub fn rimphony_ctx_set_tables_2d(
         ctx: *mut rimphony_ctx,
         n_tables: usize,
@@ -285,6 +295,28 @@ impl HipContext {
             rimphony_ctx_set_tables_pitchy(
                 self.raw, log_n.len() / n_nodes, n_nodes, gamma_lo, gamma_hi, log_n.as_ptr(), n_mu,
                 if log_g.is_empty() { std::ptr::null() } else { log_g.as_ptr() }, sin_k.as_ptr(),
+            )
+        };
+        if rc != RIMPHONY_OK {
+            return Err(error_text(rc));
+        }
+        Ok(())
+    }
+
+    /// A table set on gamma nodes of the caller's choosing: `gamma` holds the strictly increasing nodes, shared by the tables
+    /// of `log_n`; `log_g` (with n_mu) and `sin_k` may be empty (include/rimphony_hip.h: rimphony_ctx_set_tables_grid).
+    pub fn set_tables_grid(&self, gamma: &[f64], log_n: &[f64], n_mu: usize, log_g: &[f64], sin_k: &[f64]) -> Result<(), String> {
+        let n_nodes = gamma.len();
+        if n_nodes == 0 || log_n.len() % n_nodes != 0 || log_g.len() != log_n.len() / n_nodes * n_mu
+            || (!sin_k.is_empty() && sin_k.len() != log_n.len() / n_nodes)
+        {
+            return Err(error_text(RIMPHONY_EINVAL));
+        }
+        let rc = unsafe {
+            rimphony_ctx_set_tables_grid(
+                self.raw, log_n.len() / n_nodes, n_nodes, gamma.as_ptr(), log_n.as_ptr(), n_mu,
+                if log_g.is_empty() { std::ptr::null() } else { log_g.as_ptr() },
+                if sin_k.is_empty() { std::ptr::null() } else { sin_k.as_ptr() },
             )
         };
         if rc != RIMPHONY_OK {

@@ -70,6 +70,7 @@ def build_hip(force=False, verbose=False):
     cmd = [hipcc] + HIPCC_FLAGS + [os.path.join(CSRC, "rimphony_hip.hip"), os.path.join(CSRC, "rimphony_diag.hip"),
                                     os.path.join(CSRC, "rimphony_group.hip"), os.path.join(CSRC, "rimphony_multi.hip"),
                                     os.path.join(CSRC, "rimphony_tab.hip"), os.path.join(CSRC, "rimphony_tab_group.hip"),
+                                    os.path.join(CSRC, "rimphony_tab_grid_group.hip"),
                                     "-ldl", "-o", LIB]
     if verbose:
         print(" ".join(cmd))
@@ -162,3 +163,8 @@ def build_pitchy_beam_oracle():
     """The CPU oracle of an analytic power law times sin^k xi times an exponential beam in cos xi
     (tests/support/pitchy_beam_oracle.cpp): what the tables with a sin^k prefactor are compared with.  Tests only."""
     return _build_dist_oracle("pitchy_beam_oracle.cpp", "liboracle_pitchy_beam.so")
+
+
+def build_tab_grid_oracle():
+    """The same for table sets on given gamma nodes (tests/support/tab_grid_oracle.cpp)."""
+    return _build_dist_oracle("tab_grid_oracle.cpp", "liboracle_tabgrid.so")

@@ -131,6 +131,32 @@ def check_sin_k(sin_k, n_tables):
     return np.ascontiguousarray(k)
 
 
+def grid_nodes_log_gm1(gamma_lo, gamma_hi, n_nodes):
+    """n_nodes gamma uniform in ln(gamma - 1) from gamma_lo to gamma_hi (1 < gamma_lo < gamma_hi), the ends exactly those:
+    as many nodes in every e-fold of gamma - 1, which is what a cold or mildly relativistic core needs
+    (Context.set_tables_grid)."""
+    if not (1.0 < gamma_lo < gamma_hi) or int(n_nodes) < 2:
+        raise ValueError("grid_nodes_log_gm1: expected 1 < gamma_lo < gamma_hi and at least two nodes")
+    gamma = 1.0 + np.exp(np.linspace(math.log(gamma_lo - 1.0), math.log(gamma_hi - 1.0), int(n_nodes)))
+    gamma[0], gamma[-1] = gamma_lo, gamma_hi
+    return gamma
+
+
+def check_grid_tables(gamma, log_n, log_g=None):
+    """A table set as rimphony_ctx_set_tables_grid accepts it -> (gamma, log_n, log_g), contiguous float64 [n_nodes],
+    [n_tables][n_nodes] and [n_tables][n_mu] or None; ValueError for what the library refuses with RIMPHONY_EINVAL (the
+    library itself judges whether the nodes' logarithms increase)."""
+    g = np.ascontiguousarray(np.asarray(gamma, dtype=np.float64))
+    if g.ndim != 1 or not TAB_MIN_NODES <= g.shape[0] <= TAB_MAX_NODES:
+        raise ValueError("gamma: expected %d to %d nodes, got shape %r" % (TAB_MIN_NODES, TAB_MAX_NODES, g.shape))
+    if not np.isfinite(g).all() or not g[0] >= 1.0 or not (np.diff(g) > 0.0).all():
+        raise ValueError("gamma: the nodes must be finite and strictly increasing from gamma[0] >= 1")
+    t, p = check_pitch_tables(float(g[0]), float(g[-1]), log_n, log_g)
+    if t.shape[1] != g.shape[0]:
+        raise ValueError("log_n: expected rows of %d values, one per node, got %d" % (g.shape[0], t.shape[1]))
+    return g, t, p
+
+
 TAB_2D_MIN_MU, TAB_2D_MAX_MU, TAB_2D_MAX_CELLS = 8, 1024, 1 << 20
 
 
@@ -225,6 +251,23 @@ class Context:
         capi.check(self.lib.rimphony_ctx_set_tables(self.handle, t.shape[0], t.shape[1], float(gamma_lo), float(gamma_hi),
                                                     t.ctypes.data_as(ctypes.POINTER(ctypes.c_double))),
                    "rimphony_ctx_set_tables")
+
+    def set_tables_grid(self, gamma, log_n, log_g=None, sin_k=None):
+        """The context's table set on gamma nodes of the caller's choosing: gamma [n_nodes] strictly increasing from >= 1,
+        shared by the tables; log_n [n_tables][n_nodes] (or [n_nodes]) = ln n at the nodes.  For what nodes uniform in
+        ln gamma cannot resolve, a cold thermal core above all (grid_nodes_log_gm1 gives nodes uniform in ln(gamma - 1)).
+        log_g and sin_k as for set_tables.  Replaces the previous set of any form; log_n None clears it.  Synchronous
+        (include/rimphony_hip.h: rimphony_ctx_set_tables_grid)."""
+        if log_n is None:
+            capi.check(self.lib.rimphony_ctx_set_tables_grid(self.handle, 0, 0, None, None, 0, None, None), "rimphony_ctx_set_tables_grid")
+            return
+        g, t, p = check_grid_tables(gamma, log_n, log_g)
+        k = None if sin_k is None else check_sin_k(sin_k, t.shape[0])
+        dp = ctypes.POINTER(ctypes.c_double)
+        capi.check(self.lib.rimphony_ctx_set_tables_grid(self.handle, t.shape[0], t.shape[1], g.ctypes.data_as(dp), t.ctypes.data_as(dp),
+                                                         0 if p is None else p.shape[1], None if p is None else p.ctypes.data_as(dp),
+                                                         None if k is None else k.ctypes.data_as(dp)),
+                   "rimphony_ctx_set_tables_grid")
 
     def set_tables_2d(self, gamma_lo, gamma_hi, log_n):
         """The context's table set for kind TABULATED as surfaces: log_n [n_tables][n_nodes][n_mu] (a 2-D array is one
@@ -842,6 +885,34 @@ class TabulatedDistribution2D(TabulatedDistribution):
 
     def _install(self, ctx):
         ctx.set_tables_2d(self.gamma_lo, self.gamma_hi, self.log_n)
+        return ctx
+
+
+class TabulatedDistributionGrid(TabulatedDistribution):
+    """A distribution given as a table on gamma nodes of its own: log_n [n_nodes] = ln n at the strictly increasing
+    gamma [n_nodes] (Context.set_tables_grid); f = norm n sin^k xi g / (gamma^2 beta) between the end nodes, 0 outside, the
+    natural cubic spline in (ln gamma, ln n) on the given nodes.  log_g and sin_k as for TabulatedDistribution.  Installs
+    its table whenever it computes, as TabulatedDistribution does."""
+
+    def __init__(self, gamma, log_n, log_g=None, sin_k=None):
+        self.gamma, self.log_n, self.log_g = check_grid_tables(
+            gamma, np.asarray(log_n, dtype=np.float64).reshape(1, -1),
+            None if log_g is None else np.asarray(log_g, dtype=np.float64).reshape(1, -1))
+        self.gamma_lo, self.gamma_hi = float(self.gamma[0]), float(self.gamma[-1])
+        self.sin_k = None if sin_k is None else check_sin_k(sin_k, 1)
+
+    @classmethod
+    def from_function(cls, fn, gamma, pitch_fn=None, n_mu=257, sin_k=None):
+        """Tabulate n(gamma) = fn(gamma) (vectorised, positive) at the given nodes and, if given, g(mu) = pitch_fn(mu)
+        (vectorised, positive) on n_mu nodes uniform in mu from -1 to +1; sin_k as in the constructor."""
+        gamma = np.asarray(gamma, dtype=np.float64)
+        log_g = None
+        if pitch_fn is not None:
+            log_g = np.log(np.asarray(pitch_fn(np.linspace(-1.0, 1.0, int(n_mu))), dtype=np.float64))
+        return cls(gamma, np.log(np.asarray(fn(gamma), dtype=np.float64)), log_g, sin_k)
+
+    def _install(self, ctx):
+        ctx.set_tables_grid(self.gamma, self.log_n, self.log_g, self.sin_k)
         return ctx
 
 

@@ -63,7 +63,7 @@ __global__ __launch_bounds__(64) void norm_kernel(ParamPtrs pp, size_t n, double
         DistParams d;
         load_params<KIND>(pp, i, d);
         // (the tabulated kind: dist_prepare replaces the table index in par[0], so the index is judged first)
-        constexpr bool TAB = KIND == DIST_TABULATED || KIND == DIST_TABULATED_PITCHY;
+        constexpr bool TAB = KIND == DIST_TABULATED || KIND == DIST_TABULATED_PITCHY || KIND == DIST_TABULATED_GRID;
         const bool tab_ok = !TAB || tab_row_ok(pp.p[1], d.par[0]);
         dist_prepare<KIND>(d, RIM_NAN);
 
@@ -84,7 +84,7 @@ __global__ __launch_bounds__(64) void norm_kernel(ParamPtrs pp, size_t n, double
 
         // (the tabulated kind's integrand, n(gamma) of its table, is dev_symphony.h's: the tests' table oracle shares it)
         auto f = [&](double x, bool active) -> double {
-            if (TAB) return active ? tab_norm_integrand(d, x) : 0.;
+            if (TAB) return active ? tab_norm_integrand<KIND>(d, x) : 0.;
             return active ? norm_integrand<KIND>(d, x) : 0.;
         };
         QagState q;

@@ -28,10 +28,14 @@ enum { DIST_POWER_LAW = 0, DIST_THERMAL_JUETTNER = 1, DIST_PITCHY_PL = 2, DIST_P
        DIST_TABULATED_2D = 6,
        // nor this one: the tabulated kind where every table carries a sin^k xi prefactor (rim_tab_build_pitchy), with or
        // without a pitch row.  Chosen by the host in the same way.
-       DIST_TABULATED_PITCHY = 7 };
+       DIST_TABULATED_PITCHY = 7,
+       // nor this one: the tabulated kind where the gamma nodes of the set are given, not uniform in ln gamma
+       // (rim_tab_build_grid); it carries a sin^k prefactor and a pitch row as DIST_TABULATED_PITCHY does.
+       DIST_TABULATED_GRID = 8 };
 constexpr bool dist_is_tab(int kind)
 {
-    return kind == DIST_TABULATED || kind == DIST_TABULATED_ISO || kind == DIST_TABULATED_2D || kind == DIST_TABULATED_PITCHY;
+    return kind == DIST_TABULATED || kind == DIST_TABULATED_ISO || kind == DIST_TABULATED_2D || kind == DIST_TABULATED_PITCHY ||
+        kind == DIST_TABULATED_GRID;
 }
 enum { STOKES_I = 0, STOKES_Q = 1, STOKES_V = 2 };
 enum { COEFF_EMISSION = 0, COEFF_ABSORPTION = 1, COEFF_FARADAY = 2 };
@@ -70,6 +74,31 @@ RIM_DEV bool tab_set_is_2d(const double *hdr) { return hdr[TAB_HDR_NMU] < 0.; }
 // carries the address of the pitch-row part, so tab_pitch_spline serves it as it is; k and n_mu sit at negative offsets
 // from there.  A table header is one 64-byte line.
 enum { TAB_PITCHY_PRE = 4, TAB_PITCHY_K = -4, TAB_PITCHY_NMU = -3 };
+// A set on given gamma nodes (rim_tab_build_grid): the header with TAB_HDR_ULO = u_0 = ln gamma_0, TAB_HDR_INVH = 1 / (the
+// width of a guide cell), TAB_HDR_H = G, the number of guide cells (a power of two >= n_nodes), TAB_HDR_NMU = n_mu.  Then
+// the guide, G + 1 32-bit words padded to a multiple of 64 bytes (tab_grid_guide_doubles): the cells are uniform in u over
+// [u_0, u_last], a u belongs to the cell tab_grid_cell() says, and word c holds min(the index of the last node in a cell
+// below c, n_nodes - 2) -- 0 where there is none --, so that the interval of a sample lies between words c and c + 1 of its
+// cell.  Then [n_tables][n_nodes][4] = {u_j, y_j, m_j, 1 / h_j} (h_j = u_{j+1} - u_j; 0 at the last node): the two nodes of
+// an interval are 64 contiguous bytes.  Then what follows the gamma rows of a sin^k set, with a header of its own in front:
+// TAB_HDR_DOUBLES words {n_tables, 0, gamma_0, gamma_last, 0, 0, 0, n_mu} and per table {k, n_mu, two spare}, the pitch
+// row's header and, where there is a g, its nodes.  Read as a set of no gamma nodes, that tail is a sin^k set's:
+// tab_pitchy_table_p_kernel integrates P into it as it stands.
+RIM_DEV size_t tab_grid_guide_doubles(size_t cells) { return ((cells + 2) / 2 + 7) & ~(size_t) 7; }
+RIM_DEV size_t tab_grid_tail(size_t n_tables, size_t n_nodes, size_t cells)
+{
+    return (size_t) TAB_HDR_DOUBLES + tab_grid_guide_doubles(cells) + n_tables * n_nodes * 4;
+}
+// the guide cell of u: u0 = u_0, inv_cell = 1 / (cell width), last_cell = G - 1.  Monotone in u, and formed from a clamped
+// copy: a NaN belongs to cell 0.  The host fills the guide with this very function, so a rounding in it moves a node and
+// the samples around it together.
+RIM_DEV long long tab_grid_cell(double u, double u0, double inv_cell, double last_cell)
+{
+    double xc = (u - u0) * inv_cell;
+    if (!(xc >= 0.)) xc = 0.;
+    if (xc > last_cell) xc = last_cell;
+    return (long long) xc;
+}
 
 // is `idx` (par[0] of a row) the index of a table of the set?
 RIM_DEV bool tab_row_ok(const double *hdr, double idx)
@@ -101,6 +130,24 @@ RIM_DEV void dist_prepare(DistParams &d, double norm)
             d.par[3] = hdr[TAB_HDR_INVH];
             d.par[4] = hdr[TAB_HDR_NNODES] - 2.;        // the index of the last interval in u
             d.inv_gamma_cutoff = hdr[TAB_HDR_H];
+            d.inv_kappa_width = hdr[TAB_HDR_GLO];
+            d.neg_inverse_t = hdr[TAB_HDR_GHI];
+            d.norm = ok ? norm : RIM_NAN;
+            return;
+        }
+        if (KIND == DIST_TABULATED_GRID) {
+            // a set on given nodes: par[0] the pitch-row part of the table's header in the tail (k: TAB_PITCHY_K from there),
+            // par[1] the table's nodes, par[2] u_0, par[3] 1 / (cell width), par[4] the index of the last guide cell;
+            // inv_gamma_cutoff, which carries the uniform step of the other forms, the bit pattern of the guide's address
+            const size_t nt = (size_t) hdr[TAB_HDR_NTABLES], cells = (size_t) hdr[TAB_HDR_H], nmu8 = (size_t) hdr[TAB_HDR_NMU];
+            const double *guide = hdr + TAB_HDR_DOUBLES;
+            d.par[0] = rim_frombits((uint64_t) (uintptr_t) (hdr + tab_grid_tail(nt, nn, cells) + TAB_HDR_DOUBLES +
+                                                            row * (TAB_PITCHY_PRE + TAB_PITCH_HDR + nmu8 * 2) + TAB_PITCHY_PRE));
+            d.par[1] = rim_frombits((uint64_t) (uintptr_t) (guide + tab_grid_guide_doubles(cells) + row * nn * 4));
+            d.par[2] = hdr[TAB_HDR_ULO];
+            d.par[3] = hdr[TAB_HDR_INVH];
+            d.par[4] = hdr[TAB_HDR_H] - 1.;
+            d.inv_gamma_cutoff = rim_frombits((uint64_t) (uintptr_t) guide);
             d.inv_kappa_width = hdr[TAB_HDR_GLO];
             d.neg_inverse_t = hdr[TAB_HDR_GHI];
             d.norm = ok ? norm : RIM_NAN;
@@ -192,7 +239,8 @@ RIM_DEV bool tab_kind_has_pitch(const DistParams &d)
 {
     // (a 2-D table and one with a sin^k prefactor always have a live d f / d mu: they take the general forms, as a pitch
     // row does)
-    return KIND == DIST_TABULATED_2D || KIND == DIST_TABULATED_PITCHY || (KIND != DIST_TABULATED_ISO && tab_has_pitch(d));
+    return KIND == DIST_TABULATED_2D || KIND == DIST_TABULATED_PITCHY || KIND == DIST_TABULATED_GRID ||
+        (KIND != DIST_TABULATED_ISO && tab_has_pitch(d));
 }
 
 // The spline G(mu) = ln g of a pitch row (tab_has_pitch) and dG/dmu at mu = cos xi.  The interval index is formed from a
@@ -223,14 +271,6 @@ RIM_DEV double tab_pitchy_p_integrand(const DistParams &d, double mu)
     return RimMath<0>::pow(rim_sqrt(1. - mu * mu), ph[TAB_PITCHY_K]) * rim_exp(gval);
 }
 
-// n(gamma) = exp(H(ln gamma)) of the table: the integrand of the normalisation (power_law.rs:95-96 for a table)
-RIM_DEV double tab_norm_integrand(const DistParams &d, double g)
-{
-    double hval, dhdu;
-    tab_spline(d, g, hval, dhdu);
-    return rim_exp(hval);
-}
-
 // The same Hermite cubic from four values that do not sit side by side: the value and the derivative with respect to t.
 RIM_DEV void tab_hermite4(double y0, double m0, double y1, double m1, double h, double t, double &val, double &dvaldt)
 {
@@ -239,6 +279,50 @@ RIM_DEV void tab_hermite4(double y0, double m0, double y1, double m1, double h, 
     const double c3 = b0 + b1 - 2. * dy;
     val = rim_fma(t, rim_fma(t, rim_fma(t, c3, c2), b0), y0);
     dvaldt = rim_fma(t, rim_fma(t, 3. * c3, 2. * c2), b0);
+}
+
+// The interval of u in a table on given nodes (d: dist_prepare<DIST_TABULATED_GRID>'s): the largest j <= n_nodes - 2 with
+// u_j <= u, 0 where there is none or u is a NaN.  The data alone define it; the guide only says where to look.  The
+// sample's cell c names two guide words: every node in a cell below c lies below u and every node in a cell above c above
+// it (tab_grid_cell is monotone), so the interval is one of guide[c] .. guide[c + 1], and a bisection over the u_j of the
+// row finds it.  Reads: the two guide words, then ceil(log2(guide[c + 1] - guide[c] + 1)) node words, 16 at the most.
+RIM_DEV long long tab_grid_interval(const DistParams &d, double u)
+{
+    const double *row = (const double *) (uintptr_t) rim_bits(d.par[1]);
+    const unsigned *guide = (const unsigned *) (uintptr_t) rim_bits(d.inv_gamma_cutoff);
+    const long long c = tab_grid_cell(u, d.par[2], d.par[3], d.par[4]);
+    long long lo = (long long) guide[c], hi = (long long) guide[c + 1];
+    while (lo < hi) {
+        const long long mid = (lo + hi + 1) >> 1;
+        if (row[4 * mid] <= u) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+
+// tab_spline for a table on given nodes: H(u) and dH/du at u = ln gamma.  t = (u - u_j) (1 / h_j) on the interval found,
+// the Hermite cubic with h_j = u_{j+1} - u_j formed from the two node words as the host formed it.  A NaN gives NaN from
+// interval 0; every read stays inside the set.  Only rim_log, explicit rim_fma and + - * here.
+RIM_DEV void tab_spline_grid(const DistParams &d, double gamma, double &hval, double &dhdu)
+{
+    const double *row = (const double *) (uintptr_t) rim_bits(d.par[1]);
+    const double u = rim_log(gamma);
+    const double *q = row + 4 * tab_grid_interval(d, u);
+    const double invh = q[3];
+    const double t = (u - q[0]) * invh;
+    double dhdt;
+    tab_hermite4(q[1], q[2], q[5], q[6], q[4] - q[0], t, hval, dhdt);
+    dhdu = dhdt * invh;
+}
+
+// n(gamma) = exp(H(ln gamma)) of the table: the integrand of the normalisation (power_law.rs:95-96 for a table)
+template <int KIND = DIST_TABULATED>
+RIM_DEV double tab_norm_integrand(const DistParams &d, double g)
+{
+    double hval, dhdu;
+    if (KIND == DIST_TABULATED_GRID) tab_spline_grid(d, g, hval, dhdu);
+    else tab_spline(d, g, hval, dhdu);
+    return rim_exp(hval);
 }
 
 // The surface S(u, mu) = ln n of a 2-D table at u = ln gamma, mu = cos xi, with dS/du and dS/dmu: bicubic Hermite on the
@@ -321,9 +405,10 @@ RIM_DEV void tab_calc_f_both(const DistParams &d, double gamma, double cos_xi, d
         return;
     }
     double hval, dhdu;
-    tab_spline(d, gamma, hval, dhdu);
+    if (KIND == DIST_TABULATED_GRID) tab_spline_grid(d, gamma, hval, dhdu);
+    else tab_spline(d, gamma, hval, dhdu);
     const double beta = rim_sqrt(1. - rim_div_moderate(1., gamma * gamma));
-    if (KIND == DIST_TABULATED_PITCHY) {
+    if (KIND == DIST_TABULATED_PITCHY || KIND == DIST_TABULATED_GRID) {
         // f = norm n(gamma) sin^k xi g(mu) / (gamma^2 beta), d f / d mu = f (G' - k mu / sin^2 xi): the factor and its term as
         // the pitchy kinds form them (pitchy_pl.rs:56-61), k a wave-uniform load; without a pitch row G = G' = 0
         const double *ph = (const double *) (uintptr_t) rim_bits(d.par[0]);

@@ -334,9 +334,9 @@ struct rimphony_ctx {
     unsigned long long hb_task;
     // what hipOccupancyMaxActiveBlocksPerMultiprocessor answered (-1: the query failed), asked once per context
     // (= per device) and instantiation: coop_kernel<P> by problem (0 Symphony, 1 Heyvaerts) and distribution kind,
-    int resident[2][8];             // (kind 4 four times: [4] a table set with pitch rows, [5] one without, [6] a 2-D set, [7] sin^k)
+    int resident[2][9];             // (kind 4 five times: [4] a table set with pitch rows, [5] one without, [6] a 2-D set, [7] sin^k, [8] given nodes)
     int resident_f32[4];            // ... the Symphony kernels' fp32-integrand variants,
-    int resident_group[2][8];       // ... group_kernel<P> [Symphony groups / Faraday pair][kind] (kind 4: the cells of `resident`; no Faraday pair)
+    int resident_group[2][9];       // ... group_kernel<P> [Symphony groups / Faraday pair][kind] (kind 4: the cells of `resident`; no Faraday pair)
     // 0: this context has the GPU to itself (it holds the device's lock file); 1: another context or process had
     // the device first -- smaller persistent grids, no cooperative tail (see rimphony_ctx_create)
     int shared_mode;
@@ -684,6 +684,45 @@ extern "C" int rimphony_ctx_set_tables_pitchy(rimphony_ctx *c, size_t n_tables, 
     return RIMPHONY_OK;
 }
 
+// A set on gamma nodes of its own: the sin^k form's contents on the given nodes.  The host solves the spline and fills the
+// guide (tab_spline.h: rim_tab_build_grid); where there are pitch rows, P is integrated on the device by the sin^k form's
+// kernel, which reads the tail of the set as a set of its own.  Complete on the device before the previous set is let go.
+extern "C" int rimphony_ctx_set_tables_grid(rimphony_ctx *c, size_t n_tables, size_t n_nodes, const double *gamma, const double *log_n,
+                                            size_t n_mu, const double *log_g, const double *sin_k)
+{
+    if (!c) return RIMPHONY_EINVAL;
+    if (!n_tables) return set_tables(c, 0, 0, 0., 0., nullptr, 0, nullptr);
+    if (rim_tab_check_grid(n_tables, n_nodes, gamma, log_n, n_mu, log_g, sin_k)) return RIMPHONY_EINVAL;
+    std::vector<double> blob;
+    try { rim_tab_build_grid(n_tables, n_nodes, gamma, log_n, n_mu, log_g, sin_k, blob); }
+    catch (const std::bad_alloc &) { return RIMPHONY_ENOMEM; }
+    RimCtxScope scope(c, nullptr);
+    int rc = scope.enter();
+    if (rc) return rc;
+    if (c->ev_batch_valid) HIP_TRY(hipEventSynchronize(c->ev_batch));
+    RimDevBuf<double> fresh = { nullptr, 0 };
+    rc = fresh.grow(blob.size(), blob.size() * sizeof(double), "the distribution tables");
+    if (rc) return rc;
+    const unsigned grid = persistent_grid(c, n_tables, 16);
+    rc = ensure_spill(c, grid);
+    if (rc) { fresh.release(); return rc; }
+    hipError_t e = hipMemcpy(fresh.p, blob.data(), blob.size() * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess && log_g) {
+        rim_tab_launch_pitchy_p(grid, nullptr, fresh.p + tab_grid_tail(n_tables, n_nodes, (size_t) blob[TAB_HDR_H]), c->d_spill.p);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+    if (e != hipSuccess) {
+        rim_set_last_error("installing the distribution tables", hipGetErrorString(e));
+        fresh.release();
+        return RIMPHONY_EHIP;
+    }
+    c->d_tab.release();
+    c->d_tab = fresh;
+    c->tab_form = RIM_TAB_FORM_GRID;
+    return RIMPHONY_OK;
+}
+
 static int rim_precision_check(const rimphony_ctx *c, int kind, int precision);
 
 // The argument checks of the batch entries, in the order every entry applies them: the kind and the `head` pointers
@@ -847,7 +886,7 @@ static int launch_coop(rimphony_ctx *c, int problem, int kind, int prec, const S
     PersistentKernel k = rim_coop_kernel(problem, kind, prec, c->tab_form);
     k.faraday = problem != 0;
     const int cell = kind != RIMPHONY_TABULATED ? kind : c->tab_form == RIM_TAB_FORM_PITCH ? 4 : c->tab_form == RIM_TAB_FORM_ISO ? 5 :
-                     c->tab_form == RIM_TAB_FORM_2D ? 6 : 7;
+                     c->tab_form == RIM_TAB_FORM_2D ? 6 : c->tab_form == RIM_TAB_FORM_PITCHY ? 7 : 8;
     k.resident = prec ? &c->resident_f32[kind] : &c->resident[problem][cell];
     k.spill = &c->d_spill;
     k.spill_doubles = SPILL_DOUBLES_PER_WAVE;
@@ -888,8 +927,8 @@ static int launch_group(rimphony_ctx *c, int kind, const SymArgs &a, uint32_t co
     const bool tab = kind == RIMPHONY_TABULATED;
     if (tab && faraday) return RIMPHONY_ENOTSUP;
     const int cell = !tab ? kind : c->tab_form == RIM_TAB_FORM_PITCH ? 4 : c->tab_form == RIM_TAB_FORM_ISO ? 5 :
-                     c->tab_form == RIM_TAB_FORM_2D ? 6 : 7;
-    k.fn = tab ? rim_tab_group_kernel(c->tab_form) : rim_group_kernel(kind, faraday);
+                     c->tab_form == RIM_TAB_FORM_2D ? 6 : c->tab_form == RIM_TAB_FORM_PITCHY ? 7 : 8;
+    k.fn = !tab ? rim_group_kernel(kind, faraday) : c->tab_form == RIM_TAB_FORM_GRID ? rim_tab_grid_group_kernel() : rim_tab_group_kernel(c->tab_form);
     k.waves = rim_group_waves(faraday);
     k.faraday = faraday != 0;
     k.resident = &c->resident_group[faraday ? 1 : 0][cell];
@@ -923,9 +962,13 @@ static const bool RIM_TAB_GROUP_DEFAULT[4] = {
     true,       // RIM_TAB_FORM_2D
     true,       // RIM_TAB_FORM_PITCHY
 };
+// ... and of a set on given gamma nodes (rimphony_tab_grid_group.hip): "group" like the others, NOT MEASURED either
+// (profiles/tabulated_grid_times.txt)
+static const bool RIM_TAB_GROUP_DEFAULT_GRID = true;
 static bool rim_tab_runs_group(const rimphony_ctx *c)
 {
     if (c->knobs.tab_group >= 0) return c->knobs.tab_group != 0;
+    if (c->tab_form == RIM_TAB_FORM_GRID) return RIM_TAB_GROUP_DEFAULT_GRID;
     return RIM_TAB_GROUP_DEFAULT[c->tab_form];
 }
 
@@ -1481,6 +1524,7 @@ const double *rim_ctx_norm(const rimphony_ctx *c) { return c->d_norm.p; }
 int rim_ctx_dist_kind(const rimphony_ctx *c, int kind)
 {
     if (kind != RIMPHONY_TABULATED) return kind;
+    if (c->tab_form == RIM_TAB_FORM_GRID) return (int) DIST_TABULATED_GRID;
     return c->tab_form == RIM_TAB_FORM_2D ? (int) DIST_TABULATED_2D : c->tab_form == RIM_TAB_FORM_PITCHY ? (int) DIST_TABULATED_PITCHY : kind;
 }
 double *rim_ctx_spill(const rimphony_ctx *c) { return c->d_spill.p; }

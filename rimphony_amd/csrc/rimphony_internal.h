@@ -94,7 +94,7 @@ struct RimCtxScope {
 const double *rim_ctx_norm(const rimphony_ctx *c);
 // the distribution kind whose instantiation serves `kind` on this context: DIST_TABULATED_2D (dev_symphony.h) for
 // RIMPHONY_TABULATED while a 2-D table set is installed, DIST_TABULATED_PITCHY while one with a sin^k prefactor is, `kind`
-// itself otherwise
+// (DIST_TABULATED_GRID while one on given gamma nodes is), itself otherwise
 int rim_ctx_dist_kind(const rimphony_ctx *c, int kind);
 double *rim_ctx_spill(const rimphony_ctx *c);
 
@@ -122,6 +122,7 @@ auto rim_with_kind5(int kind, F &&f)
     if (kind == 4) return f(std::integral_constant<int, 4>{});
     if (kind == 6) return f(std::integral_constant<int, 6>{});
     if (kind == 7) return f(std::integral_constant<int, 7>{});
+    if (kind == 8) return f(std::integral_constant<int, 8>{});      // DIST_TABULATED_GRID, a set on given gamma nodes
     return rim_with_kind(kind, f);
 }
 

@@ -13,6 +13,8 @@
 // A set with a sin^k xi prefactor runs a fourth family (DIST_TABULATED_PITCHY): k is one more wave-uniform load from the
 // table's header.  Where its tables have a g, P = 1/2 int (1 - mu^2)^(k/2) g dmu is integrated adaptively when the set is
 // installed (tab_pitchy_table_p_kernel): the integrand's derivative is singular at both ends for a non-integer k.
+// A set on given gamma nodes runs a fifth (DIST_TABULATED_GRID): the sin^k family with tab_spline_grid for the energy
+// table -- two guide words, a short bisection over the nodes' u_j, then the 64 bytes of the interval's two nodes.
 #include <hip/hip_runtime.h>
 #include "coop_kernel.h"
 #include "tab_launch.h"
@@ -115,6 +117,8 @@ RimCoopKernelInfo rim_tab_coop_kernel(int problem, int form)
         return problem ? coop_info<HeyvaertsProblem<DIST_TABULATED_2D>>() : coop_info<SymphonyProblem<DIST_TABULATED_2D>>();
     if (form == RIM_TAB_FORM_PITCHY)
         return problem ? coop_info<HeyvaertsProblem<DIST_TABULATED_PITCHY>>() : coop_info<SymphonyProblem<DIST_TABULATED_PITCHY>>();
+    if (form == RIM_TAB_FORM_GRID)
+        return problem ? coop_info<HeyvaertsProblem<DIST_TABULATED_GRID>>() : coop_info<SymphonyProblem<DIST_TABULATED_GRID>>();
     const bool pitch = form == RIM_TAB_FORM_PITCH;
     if (problem) return pitch ? coop_info<HeyvaertsProblem<DIST_TABULATED>>() : coop_info<HeyvaertsProblem<DIST_TABULATED_ISO>>();
     return pitch ? coop_info<SymphonyProblem<DIST_TABULATED>>() : coop_info<SymphonyProblem<DIST_TABULATED_ISO>>();
@@ -131,6 +135,10 @@ void rim_tab_launch_norm(int form, unsigned grid, hipStream_t st, const ParamPtr
         hipLaunchKernelGGL(norm_kernel<DIST_TABULATED_PITCHY>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pp, n, d_norm, queue, spill);
         return;
     }
+    if (form == RIM_TAB_FORM_GRID) {
+        hipLaunchKernelGGL(norm_kernel<DIST_TABULATED_GRID>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pp, n, d_norm, queue, spill);
+        return;
+    }
     hipLaunchKernelGGL(norm_kernel<DIST_TABULATED>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pp, n, d_norm, queue, spill);
 }
 
@@ -145,6 +153,10 @@ void rim_tab_launch_integrand(int form, unsigned grid, hipStream_t st, const Poi
         hipLaunchKernelGGL(integrand_kernel_n<DIST_TABULATED_PITCHY>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pa, d_norm, count, d_n, d_gamma, d_out);
         return;
     }
+    if (form == RIM_TAB_FORM_GRID) {
+        hipLaunchKernelGGL(integrand_kernel_n<DIST_TABULATED_GRID>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pa, d_norm, count, d_n, d_gamma, d_out);
+        return;
+    }
     hipLaunchKernelGGL(integrand_kernel_n<DIST_TABULATED>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pa, d_norm, count, d_n, d_gamma, d_out);
 }
 
@@ -157,6 +169,10 @@ void rim_tab_launch_gamma_integral(int form, unsigned grid, hipStream_t st, cons
     }
     if (form == RIM_TAB_FORM_PITCHY) {
         hipLaunchKernelGGL(gamma_integral_kernel<DIST_TABULATED_PITCHY>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pa, d_norm, count, d_n, d_out, spill);
+        return;
+    }
+    if (form == RIM_TAB_FORM_GRID) {
+        hipLaunchKernelGGL(gamma_integral_kernel<DIST_TABULATED_GRID>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pa, d_norm, count, d_n, d_out, spill);
         return;
     }
     hipLaunchKernelGGL(gamma_integral_kernel<DIST_TABULATED>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pa, d_norm, count, d_n, d_out, spill);

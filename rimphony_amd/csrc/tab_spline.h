@@ -20,6 +20,11 @@
 // kinds, set here; with g it is 0 as built and the caller fills it (the library on the device, the tests' oracle with its
 // own QAG), as the normalisation of a 2-D table.
 //
+// A set may stand on gamma nodes of its own choosing (rim_tab_check_grid, rim_tab_build_grid): strictly increasing, shared
+// by the tables of the set, with everything a sin^k set carries.  The natural cubic spline through (u_j, y_j), u_j =
+// rim_log(gamma_j), from the Thomas sweep on the non-uniform system; the layout of dev_symphony.h's tab_grid_*, with the
+// guide that tells a sample where to look for its interval.
+//
 // Plain C++ with the elementary functions of detmath.h, so that the library (hipcc's host pass) and the tests' table
 // oracle (g++) produce the same bits from the same table.
 #ifndef RIM_TAB_SPLINE_H
@@ -184,6 +189,116 @@ inline void rim_tab_build_pitchy(size_t n_tables, size_t n_nodes, double gamma_l
         ph[TAB_PITCH_INVH] = 1. / h;
         ph[TAB_PITCH_H] = h;
         rim_tab_spline_row(log_g + t * n_mu, n_mu, h, ph + TAB_PITCH_HDR, cp.data(), dp.data());
+    }
+}
+
+// rim_tab_check_pitchy() for a set on given nodes: gamma [n_nodes], finite, 1 <= gamma[0], strictly increasing, and so
+// are their logarithms as the build forms them (two gamma a rounding apart may share one: h_j = 0).  log_g, n_mu as for
+// rim_tab_check_pitch; sin_k may be null (no prefactor).
+inline int rim_tab_check_grid(size_t n_tables, size_t n_nodes, const double *gamma, const double *log_n, size_t n_mu,
+                              const double *log_g, const double *sin_k)
+{
+    using namespace rim;
+    if (!gamma || n_nodes < RIM_TAB_MIN_NODES || n_nodes > RIM_TAB_MAX_NODES) return -1;
+    for (size_t j = 0; j < n_nodes; j++)
+        if (!rim_isfinite(gamma[j])) return -1;
+    if (!(gamma[0] >= 1.)) return -1;
+    for (size_t j = 0; j + 1 < n_nodes; j++) {
+        if (!(gamma[j] < gamma[j + 1])) return -1;
+        if (!(rim_log(gamma[j]) < rim_log(gamma[j + 1]))) return -1;
+    }
+    if (rim_tab_check_pitch(n_tables, n_nodes, gamma[0], gamma[n_nodes - 1], log_n, n_mu, log_g)) return -1;
+    if (sin_k)
+        for (size_t t = 0; t < n_tables; t++)
+            if (!rim_isfinite(sin_k[t]) || !(sin_k[t] >= 0.) || !(sin_k[t] <= RIM_TAB_MAX_SIN_K)) return -1;
+    return 0;
+}
+
+// The slopes m[0 .. n-1] of the natural cubic spline through (u_j, y[j]) on nodes h[j] = u_{j+1} - u_j apart, ih[j] = 1 / h[j]:
+//   ih[j-1] m_{j-1} + 2 (ih[j-1] + ih[j]) m_j + ih[j] m_{j+1} = 3 (s_{j-1} ih[j-1] + s_j ih[j]),  s_j = (y_{j+1} - y_j) / h[j],
+// 2 m_0 + m_1 = 3 s_0 and its mirror at the ends.  One fixed order of operations: the bits depend on it.  cp, dp: n doubles.
+inline void rim_tab_spline_row_grid(const double *y, size_t n, const double *h, const double *ih, double *m, double *cp, double *dp)
+{
+    const size_t last = n - 1;
+    cp[0] = 0.5;
+    dp[0] = 3. * ((y[1] - y[0]) / h[0]) / 2.;
+    for (size_t j = 1; j < last; j++) {
+        const double sl = (y[j] - y[j - 1]) / h[j - 1], sr = (y[j + 1] - y[j]) / h[j];
+        const double rhs = 3. * (sl * ih[j - 1] + sr * ih[j]);
+        const double den = 2. * (ih[j - 1] + ih[j]) - ih[j - 1] * cp[j - 1];
+        cp[j] = ih[j] / den;
+        dp[j] = (rhs - ih[j - 1] * dp[j - 1]) / den;
+    }
+    m[last] = (3. * ((y[last] - y[last - 1]) / h[last - 1]) - dp[last - 1]) / (2. - cp[last - 1]);
+    for (size_t j = last; j-- > 0;) m[j] = dp[j] - cp[j] * m[j + 1];
+}
+
+// the set on given nodes as one block of doubles (dev_symphony.h: tab_grid_*); rim_tab_check_grid() has passed.  sin_k
+// null: k = 0 for every table.  P of a table with a pitch row is 0 as built and the caller fills it, as for a sin^k set.
+inline void rim_tab_build_grid(size_t n_tables, size_t n_nodes, const double *gamma, const double *log_n, size_t n_mu,
+                               const double *log_g, const double *sin_k, std::vector<double> &blob)
+{
+    using namespace rim;
+    if (!log_g) n_mu = 0;
+    size_t cells = 8;
+    while (cells < n_nodes) cells *= 2;
+    const size_t tail = tab_grid_tail(n_tables, n_nodes, cells);
+    const size_t stride = (size_t) TAB_PITCHY_PRE + TAB_PITCH_HDR + n_mu * 2;
+    blob.assign(tail + TAB_HDR_DOUBLES + n_tables * stride, 0.);
+    std::vector<double> u(n_nodes), h(n_nodes), ih(n_nodes), m(n_nodes), cp(n_nodes), dp(n_nodes);
+    for (size_t j = 0; j < n_nodes; j++) u[j] = rim_log(gamma[j]);
+    for (size_t j = 0; j + 1 < n_nodes; j++) { h[j] = u[j + 1] - u[j]; ih[j] = 1. / h[j]; }
+    h[n_nodes - 1] = 0.; ih[n_nodes - 1] = 0.;
+    const double inv_cell = (double) cells / (u[n_nodes - 1] - u[0]);
+    blob[TAB_HDR_NTABLES] = (double) n_tables;
+    blob[TAB_HDR_NNODES] = (double) n_nodes;
+    blob[TAB_HDR_GLO] = gamma[0];
+    blob[TAB_HDR_GHI] = gamma[n_nodes - 1];
+    blob[TAB_HDR_ULO] = u[0];
+    blob[TAB_HDR_INVH] = inv_cell;
+    blob[TAB_HDR_H] = (double) cells;
+    blob[TAB_HDR_NMU] = (double) n_mu;
+    // the guide: word c = min(the last node in a cell below c, n_nodes - 2), 0 where there is none
+    uint32_t *guide = (uint32_t *) (blob.data() + TAB_HDR_DOUBLES);
+    size_t j = 0;
+    for (size_t c = 0; c <= cells; c++) {
+        while (j < n_nodes && (size_t) tab_grid_cell(u[j], u[0], inv_cell, (double) (cells - 1)) < c) j++;
+        size_t w = j ? j - 1 : 0;
+        if (w > n_nodes - 2) w = n_nodes - 2;
+        guide[c] = (uint32_t) w;
+    }
+    for (size_t t = 0; t < n_tables; t++) {
+        const double *y = log_n + t * n_nodes;
+        double *row = blob.data() + TAB_HDR_DOUBLES + tab_grid_guide_doubles(cells) + t * n_nodes * 4;
+        rim_tab_spline_row_grid(y, n_nodes, h.data(), ih.data(), m.data(), cp.data(), dp.data());
+        for (size_t i = 0; i < n_nodes; i++) {
+            row[4 * i] = u[i];
+            row[4 * i + 1] = y[i];
+            row[4 * i + 2] = m[i];
+            row[4 * i + 3] = ih[i];
+        }
+    }
+    // the tail: a sin^k set's table headers and pitch rows behind a header that names no gamma nodes
+    double *th = blob.data() + tail;
+    th[TAB_HDR_NTABLES] = (double) n_tables;
+    th[TAB_HDR_GLO] = gamma[0];
+    th[TAB_HDR_GHI] = gamma[n_nodes - 1];
+    th[TAB_HDR_NMU] = (double) n_mu;
+    const double hm = n_mu ? 2. / (double) (n_mu - 1) : 0.;
+    std::vector<double> cpm(n_mu), dpm(n_mu);
+    for (size_t t = 0; t < n_tables; t++) {
+        double *ph = th + TAB_HDR_DOUBLES + t * stride + TAB_PITCHY_PRE;
+        const double k = sin_k ? sin_k[t] : 0.;
+        ph[TAB_PITCHY_K] = k;
+        ph[TAB_PITCHY_NMU] = (double) n_mu;
+        if (!n_mu) {
+            ph[TAB_PITCH_P] = rim_tab_sin_k_integral(k);
+            continue;
+        }
+        ph[TAB_PITCH_LAST] = (double) (n_mu - 2);
+        ph[TAB_PITCH_INVH] = 1. / hm;
+        ph[TAB_PITCH_H] = hm;
+        rim_tab_spline_row(log_g + t * n_mu, n_mu, hm, ph + TAB_PITCH_HDR, cpm.data(), dpm.data());
     }
 }
 

@@ -94,6 +94,19 @@ public:
                                              log_g.empty() ? nullptr : log_g.data(), n_tables ? sin_k.data() : nullptr),
               "rimphony_ctx_set_tables_pitchy");
     }
+    // A set on gamma nodes of the caller's choosing (rimphony_ctx_set_tables_grid): gamma [n_nodes] strictly increasing from
+    // >= 1, shared by the tables; log_n [n_tables][n_nodes]; log_g [n_tables][n_mu] and sin_k [n_tables] may be empty.
+    void set_tables_grid(size_t n_tables, const std::vector<double> &gamma, const std::vector<double> &log_n, size_t n_mu = 0,
+                         const std::vector<double> &log_g = {}, const std::vector<double> &sin_k = {}) const
+    {
+        if (log_n.size() != n_tables * gamma.size()) throw std::runtime_error("set_tables_grid: log_n must hold n_tables * n_nodes values");
+        if (log_g.size() != n_tables * n_mu) throw std::runtime_error("set_tables_grid: log_g must hold n_tables * n_mu values");
+        if (!sin_k.empty() && sin_k.size() != n_tables) throw std::runtime_error("set_tables_grid: sin_k must hold n_tables values");
+        check(rimphony_ctx_set_tables_grid(ctx_, n_tables, gamma.size(), n_tables ? gamma.data() : nullptr,
+                                           n_tables ? log_n.data() : nullptr, n_mu, log_g.empty() ? nullptr : log_g.data(),
+                                           sin_k.empty() ? nullptr : sin_k.data()),
+              "rimphony_ctx_set_tables_grid");
+    }
     // A 2-D set: log_n [n_tables][n_nodes][n_mu], mu fastest, = ln n(gamma, mu) at nodes uniform in ln gamma and in mu from -1
     // to +1 (rimphony_ctx_set_tables_2d): any f(gamma, cos xi), a non-separable one included.
     void set_tables_2d(size_t n_tables, size_t n_nodes, double gamma_lo, double gamma_hi, size_t n_mu,
@@ -385,6 +398,31 @@ private:
     double glo_, ghi_;
     size_t n_nodes_, n_mu_;
     std::vector<double> log_n_;
+};
+
+// A distribution given as a table on gamma nodes of its own: log_n [n_nodes] = ln n at the strictly increasing gamma
+// [n_nodes] (include/rimphony_hip.h: rimphony_ctx_set_tables_grid), for what nodes uniform in ln gamma cannot resolve.
+// log_g (ln g at nodes uniform in mu) may be empty; sin_k < 0: no prefactor.  Used as TabulatedDistribution is.
+class TabulatedDistributionGrid : public DistributionFunction {
+protected:
+    int abi_kind() const override { return RIMPHONY_TABULATED; }
+    std::vector<double> abi_params() const override { return {0.}; }      // the table index
+public:
+    TabulatedDistributionGrid(std::vector<double> gamma, std::vector<double> log_n, std::vector<double> log_g = {}, double sin_k = -1.)
+        : gamma_(std::move(gamma)), log_n_(std::move(log_n)), log_g_(std::move(log_g))
+    { if (sin_k >= 0.) sin_k_.push_back(sin_k); }
+    void install(const Context &ctx) const { ctx.set_tables_grid(1, gamma_, log_n_, log_g_.size(), log_g_, sin_k_); }
+    double calc_f(const Context &ctx, double gamma, double cos_xi) const
+    { install(ctx); return DistributionFunction::calc_f(ctx, gamma, cos_xi); }
+    std::array<double, 2> calc_f_derivatives(const Context &ctx, double gamma, double cos_xi) const
+    { install(ctx); return DistributionFunction::calc_f_derivatives(ctx, gamma, cos_xi); }
+    FullSynchrotronCalculator full_calculation(std::shared_ptr<Context> ctx) const
+    {
+        install(*ctx);
+        return FullSynchrotronCalculator(std::move(ctx), RIMPHONY_TABULATED, {0.});
+    }
+private:
+    std::vector<double> gamma_, log_n_, log_g_, sin_k_;
 };
 
 }  // namespace rimphony
