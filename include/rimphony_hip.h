@@ -152,7 +152,8 @@ const char *rimphony_version(void);
  * coefficients.  Taper the table so that n is negligible at both ends.
  * A context holds one table set at a time: the call copies it to the device (the slopes of the splines are solved on the
  * host, once), replaces the previous set and returns after the context's earlier work has finished; n_tables = 0 clears
- * the set.  A row of a batch names its table by index (the kind's one parameter, a double); a row whose index is not an
+ * the set.  Whatever its form, the new set is complete on the device before the previous one is let go: a call that is
+ * refused or fails leaves the previous set in place, and for the length of the call both sets are resident.  A row of a batch names its table by index (the kind's one parameter, a double); a row whose index is not an
  * integer in [0, n_tables) gets a NaN normalisation: all its selected slots are NaN with RIMPHONY_ST_NORM_FAIL.  With no
  * table set every entry refuses the kind with RIMPHONY_EINVAL.  In the _multi entries each context uses its OWN table
  * set: give every context the same tables.  The six Symphony coefficients of a point run in lock-step on the group kernel,

@@ -334,7 +334,7 @@ struct rimphony_ctx {
     unsigned long long hb_task;
     // what hipOccupancyMaxActiveBlocksPerMultiprocessor answered (-1: the query failed), asked once per context
     // (= per device) and instantiation: coop_kernel<P> by problem (0 Symphony, 1 Heyvaerts) and distribution kind,
-    int resident[2][9];             // (kind 4 five times: [4] a table set with pitch rows, [5] one without, [6] a 2-D set, [7] sin^k, [8] given nodes)
+    int resident[2][9];             // (kind 4 five times: the cell of a table set is its DIST_TABULATED* value, tab_kind below)
     int resident_f32[4];            // ... the Symphony kernels' fp32-integrand variants,
     int resident_group[2][9];       // ... group_kernel<P> [Symphony groups / Faraday pair][kind] (kind 4: the cells of `resident`; no Faraday pair)
     // 0: this context has the GPU to itself (it holds the device's lock file); 1: another context or process had
@@ -354,7 +354,7 @@ struct rimphony_ctx {
     RimDevBuf<char> d_gboard;       // [cap] GroupSlot + flag words behind
     // the table set of the tabulated distribution (rimphony_ctx_set_tables; dev_symphony.h has the layout), or empty
     RimDevBuf<double> d_tab;
-    int tab_form = RIM_TAB_FORM_ISO;    // isotropic, with pitch rows or 2-D (tab_launch.h): which instantiation of the kind's kernels runs
+    int tab_kind = DIST_TABULATED_ISO;  // the form of that set as its DIST_TABULATED* value (tab_launch.h): which instantiation of the kind's kernels runs
 };
 
 // ---- last error (thread-local text; the codes are in rimphony_hip.h) ---------------------------
@@ -543,7 +543,7 @@ static int launch_norm(rimphony_ctx *c, int kind, size_t n, const ParamPtrs &pp,
     const unsigned grid = persistent_grid(c, n, 16);
     int rc = ensure_spill(c, grid);
     if (rc) return rc;
-    if (kind == RIMPHONY_TABULATED) rim_tab_launch_norm(c->tab_form, grid, st, pp, n, d_norm, c->d_queue.p, c->d_spill.p);
+    if (kind == RIMPHONY_TABULATED) rim_tab_launch_norm(c->tab_kind, grid, st, pp, n, d_norm, c->d_queue.p, c->d_spill.p);
     else rim_with_kind(kind, [&](auto K) {
         hipLaunchKernelGGL(norm_kernel<decltype(K)::value>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pp, n, d_norm, c->d_queue.p, c->d_spill.p);
     });
@@ -565,8 +565,52 @@ static int check_tables(const rimphony_ctx *c, int kind)
     return (kind == RIMPHONY_TABULATED && !c->d_tab.p) ? RIMPHONY_EINVAL : RIMPHONY_OK;
 }
 
-static int set_tables(rimphony_ctx *c, size_t n_tables, size_t n_nodes, double gamma_lo, double gamma_hi, const double *log_n,
-                      size_t n_mu, const double *log_g)
+// The one way a table set comes into a context or leaves it.  `blob` is the set as the kernels read it (tab_spline.h), of the
+// form `tab_kind` (a DIST_TABULATED* value); an empty blob clears.  `fill`, if any, completes the set on the device, one wave
+// per table: the tables' normalisations of a 2-D set (rim_tab_launch_table_norms), or P of the tables of a set with a sin^k
+// prefactor and pitch rows (rim_tab_launch_pitchy_p), whose header is `fill_at` doubles into the set.  The new set is
+// complete on the device before the previous one is let go: a refusal or a failed allocation leaves the previous set in
+// place, and for the length of the call both are resident.
+typedef void (*RimTabFill)(unsigned grid, hipStream_t st, double *d_set, double *spill);
+static int install_tables(rimphony_ctx *c, const std::vector<double> &blob, int tab_kind, RimTabFill fill = nullptr, size_t fill_at = 0)
+{
+    RimCtxScope scope(c, nullptr);
+    int rc = scope.enter();
+    if (rc) return rc;
+    // the previous set may still be read by the context's earlier work
+    if (c->ev_batch_valid) HIP_TRY(hipEventSynchronize(c->ev_batch));
+    if (blob.empty()) {
+        c->d_tab.release();
+        c->tab_kind = DIST_TABULATED_ISO;
+        return RIMPHONY_OK;
+    }
+    RimDevBuf<double> fresh = { nullptr, 0 };
+    rc = fresh.grow(blob.size(), blob.size() * sizeof(double), "the distribution tables");
+    if (rc) return rc;
+    const unsigned grid = persistent_grid(c, (unsigned long long) blob[TAB_HDR_NTABLES], 16);
+    rc = ensure_spill(c, grid);
+    if (rc) { fresh.release(); return rc; }
+    hipError_t e = hipMemcpy(fresh.p, blob.data(), blob.size() * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess && fill) {
+        fill(grid, nullptr, fresh.p + fill_at, c->d_spill.p);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+    if (e != hipSuccess) {
+        rim_set_last_error("installing the distribution tables", hipGetErrorString(e));
+        fresh.release();
+        return RIMPHONY_EHIP;
+    }
+    c->d_tab.release();
+    c->d_tab = fresh;
+    c->tab_kind = tab_kind;
+    return RIMPHONY_OK;
+}
+
+// The five entries: check, build, install; n_tables = 0 clears through any of them.  A set of energy tables, each with a
+// pitch row (log_g) or none with one (log_g null and n_mu = 0: the isotropic form).
+extern "C" int rimphony_ctx_set_tables_pitch(rimphony_ctx *c, size_t n_tables, size_t n_nodes, double gamma_lo, double gamma_hi,
+                                             const double *log_n, size_t n_mu, const double *log_g)
 {
     if (!c) return RIMPHONY_EINVAL;
     std::vector<double> blob;
@@ -575,152 +619,62 @@ static int set_tables(rimphony_ctx *c, size_t n_tables, size_t n_nodes, double g
         try { rim_tab_build_pitch(n_tables, n_nodes, gamma_lo, gamma_hi, log_n, n_mu, log_g, blob); }
         catch (const std::bad_alloc &) { return RIMPHONY_ENOMEM; }
     }
-    RimCtxScope scope(c, nullptr);
-    int rc = scope.enter();
-    if (rc) return rc;
-    // the previous set may still be read by the context's earlier work
-    if (c->ev_batch_valid) HIP_TRY(hipEventSynchronize(c->ev_batch));
-    c->d_tab.release();
-    c->tab_form = RIM_TAB_FORM_ISO;
-    if (!n_tables) return RIMPHONY_OK;
-    rc = c->d_tab.grow(blob.size(), blob.size() * sizeof(double), "the distribution tables");
-    if (rc) return rc;
-    if (hipMemcpy(c->d_tab.p, blob.data(), blob.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
-        rim_set_last_error("hipMemcpy", "the distribution tables");
-        c->d_tab.release();
-        return RIMPHONY_EHIP;
-    }
-    c->tab_form = log_g ? RIM_TAB_FORM_PITCH : RIM_TAB_FORM_ISO;
-    return RIMPHONY_OK;
+    return install_tables(c, blob, log_g ? DIST_TABULATED : DIST_TABULATED_ISO);
 }
 
 extern "C" int rimphony_ctx_set_tables(rimphony_ctx *c, size_t n_tables, size_t n_nodes, double gamma_lo, double gamma_hi,
                                        const double *log_n)
 {
-    return set_tables(c, n_tables, n_nodes, gamma_lo, gamma_hi, log_n, 0, nullptr);
+    return rimphony_ctx_set_tables_pitch(c, n_tables, n_nodes, gamma_lo, gamma_hi, log_n, 0, nullptr);
 }
 
-extern "C" int rimphony_ctx_set_tables_pitch(rimphony_ctx *c, size_t n_tables, size_t n_nodes, double gamma_lo, double gamma_hi,
-                                             const double *log_n, size_t n_mu, const double *log_g)
-{
-    return set_tables(c, n_tables, n_nodes, gamma_lo, gamma_hi, log_n, n_mu, log_g);
-}
-
-// A 2-D set: ln n(gamma, mu) on a grid.  The normalisation of each table is integrated here, once, on the device (one wave
-// per table: rimphony_tab.hip) and kept in the table's header, where the rows of a batch read it.  The new set is complete
-// on the device before the previous one is let go: a refusal or a failed allocation leaves the previous set in place.
+// A 2-D set: ln n(gamma, mu) on a grid.  The normalisation of each table is integrated once, as the set comes in
+// (rimphony_tab.hip), and kept in the table's header, where the rows of a batch read it.
 extern "C" int rimphony_ctx_set_tables_2d(rimphony_ctx *c, size_t n_tables, size_t n_nodes, double gamma_lo, double gamma_hi,
                                           size_t n_mu, const double *log_n)
 {
     if (!c) return RIMPHONY_EINVAL;
-    if (!n_tables) return set_tables(c, 0, 0, 0., 0., nullptr, 0, nullptr);
-    if (rim_tab_check_2d(n_tables, n_nodes, gamma_lo, gamma_hi, n_mu, log_n)) return RIMPHONY_EINVAL;
     std::vector<double> blob;
-    try { rim_tab_build_2d(n_tables, n_nodes, gamma_lo, gamma_hi, n_mu, log_n, blob); }
-    catch (const std::bad_alloc &) { return RIMPHONY_ENOMEM; }
-    RimCtxScope scope(c, nullptr);
-    int rc = scope.enter();
-    if (rc) return rc;
-    if (c->ev_batch_valid) HIP_TRY(hipEventSynchronize(c->ev_batch));
-    RimDevBuf<double> fresh = { nullptr, 0 };
-    rc = fresh.grow(blob.size(), blob.size() * sizeof(double), "the distribution tables");
-    if (rc) return rc;
-    const unsigned grid = persistent_grid(c, n_tables, 16);
-    rc = ensure_spill(c, grid);
-    if (rc) { fresh.release(); return rc; }
-    hipError_t e = hipMemcpy(fresh.p, blob.data(), blob.size() * sizeof(double), hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        rim_tab_launch_table_norms(grid, nullptr, fresh.p, c->d_spill.p);
-        e = hipGetLastError();
+    if (n_tables) {
+        if (rim_tab_check_2d(n_tables, n_nodes, gamma_lo, gamma_hi, n_mu, log_n)) return RIMPHONY_EINVAL;
+        try { rim_tab_build_2d(n_tables, n_nodes, gamma_lo, gamma_hi, n_mu, log_n, blob); }
+        catch (const std::bad_alloc &) { return RIMPHONY_ENOMEM; }
     }
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-    if (e != hipSuccess) {
-        rim_set_last_error("installing the distribution tables", hipGetErrorString(e));
-        fresh.release();
-        return RIMPHONY_EHIP;
-    }
-    c->d_tab.release();
-    c->d_tab = fresh;
-    c->tab_form = RIM_TAB_FORM_2D;
-    return RIMPHONY_OK;
+    return install_tables(c, blob, DIST_TABULATED_2D, rim_tab_launch_table_norms);
 }
 
-// A set with a sin^k xi prefactor per table.  Without g, P is the closed form rim_tab_build_pitchy set on the host; with g
-// it is integrated here, once, on the device (one wave per table: rimphony_tab.hip) into the table's header, where
-// norm_kernel reads it.  As for a 2-D set, the new set is complete on the device before the previous one is let go.
+// A set with a sin^k xi prefactor per table (sin_k null: the entry above it).  Without g, P is the closed form
+// rim_tab_build_pitchy set on the host; with g it is integrated once, as the set comes in, into the table's header, where
+// norm_kernel reads it.
 extern "C" int rimphony_ctx_set_tables_pitchy(rimphony_ctx *c, size_t n_tables, size_t n_nodes, double gamma_lo, double gamma_hi,
                                               const double *log_n, size_t n_mu, const double *log_g, const double *sin_k)
 {
     if (!c) return RIMPHONY_EINVAL;
-    if (!sin_k || !n_tables) return set_tables(c, n_tables, n_nodes, gamma_lo, gamma_hi, log_n, n_mu, log_g);
-    if (rim_tab_check_pitchy(n_tables, n_nodes, gamma_lo, gamma_hi, log_n, n_mu, log_g, sin_k)) return RIMPHONY_EINVAL;
+    if (!sin_k) return rimphony_ctx_set_tables_pitch(c, n_tables, n_nodes, gamma_lo, gamma_hi, log_n, n_mu, log_g);
     std::vector<double> blob;
-    try { rim_tab_build_pitchy(n_tables, n_nodes, gamma_lo, gamma_hi, log_n, n_mu, log_g, sin_k, blob); }
-    catch (const std::bad_alloc &) { return RIMPHONY_ENOMEM; }
-    RimCtxScope scope(c, nullptr);
-    int rc = scope.enter();
-    if (rc) return rc;
-    if (c->ev_batch_valid) HIP_TRY(hipEventSynchronize(c->ev_batch));
-    RimDevBuf<double> fresh = { nullptr, 0 };
-    rc = fresh.grow(blob.size(), blob.size() * sizeof(double), "the distribution tables");
-    if (rc) return rc;
-    const unsigned grid = persistent_grid(c, n_tables, 16);
-    rc = ensure_spill(c, grid);
-    if (rc) { fresh.release(); return rc; }
-    hipError_t e = hipMemcpy(fresh.p, blob.data(), blob.size() * sizeof(double), hipMemcpyHostToDevice);
-    if (e == hipSuccess && log_g) {
-        rim_tab_launch_pitchy_p(grid, nullptr, fresh.p, c->d_spill.p);
-        e = hipGetLastError();
+    if (n_tables) {
+        if (rim_tab_check_pitchy(n_tables, n_nodes, gamma_lo, gamma_hi, log_n, n_mu, log_g, sin_k)) return RIMPHONY_EINVAL;
+        try { rim_tab_build_pitchy(n_tables, n_nodes, gamma_lo, gamma_hi, log_n, n_mu, log_g, sin_k, blob); }
+        catch (const std::bad_alloc &) { return RIMPHONY_ENOMEM; }
     }
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-    if (e != hipSuccess) {
-        rim_set_last_error("installing the distribution tables", hipGetErrorString(e));
-        fresh.release();
-        return RIMPHONY_EHIP;
-    }
-    c->d_tab.release();
-    c->d_tab = fresh;
-    c->tab_form = RIM_TAB_FORM_PITCHY;
-    return RIMPHONY_OK;
+    return install_tables(c, blob, DIST_TABULATED_PITCHY, log_g ? rim_tab_launch_pitchy_p : nullptr);
 }
 
-// A set on gamma nodes of its own: the sin^k form's contents on the given nodes.  The host solves the spline and fills the
-// guide (tab_spline.h: rim_tab_build_grid); where there are pitch rows, P is integrated on the device by the sin^k form's
-// kernel, which reads the tail of the set as a set of its own.  Complete on the device before the previous set is let go.
+// A set on gamma nodes of its own, always this form: the sin^k form's contents on the given nodes.  The host solves the
+// spline and fills the guide (tab_spline.h: rim_tab_build_grid); where there are pitch rows, P is integrated by the sin^k
+// form's kernel, which reads the tail of the set as a set of its own.
 extern "C" int rimphony_ctx_set_tables_grid(rimphony_ctx *c, size_t n_tables, size_t n_nodes, const double *gamma, const double *log_n,
                                             size_t n_mu, const double *log_g, const double *sin_k)
 {
     if (!c) return RIMPHONY_EINVAL;
-    if (!n_tables) return set_tables(c, 0, 0, 0., 0., nullptr, 0, nullptr);
-    if (rim_tab_check_grid(n_tables, n_nodes, gamma, log_n, n_mu, log_g, sin_k)) return RIMPHONY_EINVAL;
     std::vector<double> blob;
-    try { rim_tab_build_grid(n_tables, n_nodes, gamma, log_n, n_mu, log_g, sin_k, blob); }
-    catch (const std::bad_alloc &) { return RIMPHONY_ENOMEM; }
-    RimCtxScope scope(c, nullptr);
-    int rc = scope.enter();
-    if (rc) return rc;
-    if (c->ev_batch_valid) HIP_TRY(hipEventSynchronize(c->ev_batch));
-    RimDevBuf<double> fresh = { nullptr, 0 };
-    rc = fresh.grow(blob.size(), blob.size() * sizeof(double), "the distribution tables");
-    if (rc) return rc;
-    const unsigned grid = persistent_grid(c, n_tables, 16);
-    rc = ensure_spill(c, grid);
-    if (rc) { fresh.release(); return rc; }
-    hipError_t e = hipMemcpy(fresh.p, blob.data(), blob.size() * sizeof(double), hipMemcpyHostToDevice);
-    if (e == hipSuccess && log_g) {
-        rim_tab_launch_pitchy_p(grid, nullptr, fresh.p + tab_grid_tail(n_tables, n_nodes, (size_t) blob[TAB_HDR_H]), c->d_spill.p);
-        e = hipGetLastError();
+    if (n_tables) {
+        if (rim_tab_check_grid(n_tables, n_nodes, gamma, log_n, n_mu, log_g, sin_k)) return RIMPHONY_EINVAL;
+        try { rim_tab_build_grid(n_tables, n_nodes, gamma, log_n, n_mu, log_g, sin_k, blob); }
+        catch (const std::bad_alloc &) { return RIMPHONY_ENOMEM; }
     }
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-    if (e != hipSuccess) {
-        rim_set_last_error("installing the distribution tables", hipGetErrorString(e));
-        fresh.release();
-        return RIMPHONY_EHIP;
-    }
-    c->d_tab.release();
-    c->d_tab = fresh;
-    c->tab_form = RIM_TAB_FORM_GRID;
-    return RIMPHONY_OK;
+    return install_tables(c, blob, DIST_TABULATED_GRID, log_g ? rim_tab_launch_pitchy_p : nullptr,
+                          n_tables ? tab_grid_tail(n_tables, n_nodes, (size_t) blob[TAB_HDR_H]) : 0);
 }
 
 static int rim_precision_check(const rimphony_ctx *c, int kind, int precision);
@@ -800,10 +754,10 @@ static PersistentKernel coop_kernel_of()
     k.early_squad = (unsigned) P::EARLY_SQUAD;
     return k;
 }
-static PersistentKernel rim_coop_kernel(int problem, int kind, int prec, int tab_form)
+static PersistentKernel rim_coop_kernel(int problem, int kind, int prec, int tab_kind)
 {
     if (kind == RIMPHONY_TABULATED) {       // (its kernels live in rimphony_tab.hip; no fp32 variant: refused at the entry)
-        const RimCoopKernelInfo t = rim_tab_coop_kernel(problem, tab_form);
+        const RimCoopKernelInfo t = rim_tab_coop_kernel(problem, tab_kind);
         PersistentKernel k = {};
         k.fn = t.fn; k.waves = t.waves; k.early_help = t.early_help; k.early_squad = t.early_squad;
         return k;
@@ -883,11 +837,9 @@ static int launch_persistent(rimphony_ctx *c, const PersistentKernel &k, unsigne
 // One wave per (point, coefficient): coop_kernel<SymphonyProblem> (problem 0) or coop_kernel<HeyvaertsProblem> (1).
 static int launch_coop(rimphony_ctx *c, int problem, int kind, int prec, const SymArgs &a, hipStream_t st)
 {
-    PersistentKernel k = rim_coop_kernel(problem, kind, prec, c->tab_form);
+    PersistentKernel k = rim_coop_kernel(problem, kind, prec, c->tab_kind);
     k.faraday = problem != 0;
-    const int cell = kind != RIMPHONY_TABULATED ? kind : c->tab_form == RIM_TAB_FORM_PITCH ? 4 : c->tab_form == RIM_TAB_FORM_ISO ? 5 :
-                     c->tab_form == RIM_TAB_FORM_2D ? 6 : c->tab_form == RIM_TAB_FORM_PITCHY ? 7 : 8;
-    k.resident = prec ? &c->resident_f32[kind] : &c->resident[problem][cell];
+    k.resident = prec ? &c->resident_f32[kind] : &c->resident[problem][kind != RIMPHONY_TABULATED ? kind : c->tab_kind];
     k.spill = &c->d_spill;
     k.spill_doubles = SPILL_DOUBLES_PER_WAVE;
     k.board = &c->d_board;
@@ -926,12 +878,10 @@ static int launch_group(rimphony_ctx *c, int kind, const SymArgs &a, uint32_t co
     // (the tabulated kind: one instantiation and one cell per form of the installed set, as in launch_coop; Symphony groups only)
     const bool tab = kind == RIMPHONY_TABULATED;
     if (tab && faraday) return RIMPHONY_ENOTSUP;
-    const int cell = !tab ? kind : c->tab_form == RIM_TAB_FORM_PITCH ? 4 : c->tab_form == RIM_TAB_FORM_ISO ? 5 :
-                     c->tab_form == RIM_TAB_FORM_2D ? 6 : c->tab_form == RIM_TAB_FORM_PITCHY ? 7 : 8;
-    k.fn = !tab ? rim_group_kernel(kind, faraday) : c->tab_form == RIM_TAB_FORM_GRID ? rim_tab_grid_group_kernel() : rim_tab_group_kernel(c->tab_form);
+    k.fn = tab ? rim_tab_group_kernel(c->tab_kind) : rim_group_kernel(kind, faraday);
     k.waves = rim_group_waves(faraday);
     k.faraday = faraday != 0;
-    k.resident = &c->resident_group[faraday ? 1 : 0][cell];
+    k.resident = &c->resident_group[faraday ? 1 : 0][tab ? c->tab_kind : kind];
     k.spill = &c->d_gspill;
     // (never less than the Symphony groups' size)
     k.spill_doubles = faraday && SPILL_HEYGROUP_DOUBLES_PER_WAVE > SPILL_GROUP_DOUBLES_PER_WAVE ? SPILL_HEYGROUP_DOUBLES_PER_WAVE
@@ -954,22 +904,20 @@ static int launch_group(rimphony_ctx *c, int kind, const SymArgs &a, uint32_t co
 }
 
 // Where the Symphony slots of the tabulated distribution run when RIMPHONY_TAB_GROUP does not say: on the group kernel
-// (rimphony_tab_group.hip) or one wave per coefficient (rimphony_tab.hip), per form of the installed set.
-// NOT MEASURED yet (profiles/tabulated_group_times.txt): every form says "group" until that file has figures.
-static const bool RIM_TAB_GROUP_DEFAULT[4] = {
-    true,       // RIM_TAB_FORM_ISO
-    true,       // RIM_TAB_FORM_PITCH
-    true,       // RIM_TAB_FORM_2D
-    true,       // RIM_TAB_FORM_PITCHY
+// (rimphony_tab_group.hip, rimphony_tab_grid_group.hip) or one wave per coefficient (rimphony_tab.hip), per form of the
+// installed set.  NOT MEASURED yet: every form says "group" until the file its line names has figures --
+// profiles/tabulated_group_times.txt for the first four, profiles/tabulated_grid_times.txt for a set on given gamma nodes.
+static const bool RIM_TAB_GROUP_DEFAULT[5] = {      // [tab_kind - DIST_TABULATED]
+    true,       // DIST_TABULATED, pitch rows   NOT MEASURED (profiles/tabulated_group_times.txt)
+    true,       // DIST_TABULATED_ISO           NOT MEASURED (profiles/tabulated_group_times.txt)
+    true,       // DIST_TABULATED_2D            NOT MEASURED (profiles/tabulated_group_times.txt)
+    true,       // DIST_TABULATED_PITCHY        NOT MEASURED (profiles/tabulated_group_times.txt)
+    true,       // DIST_TABULATED_GRID          NOT MEASURED (profiles/tabulated_grid_times.txt)
 };
-// ... and of a set on given gamma nodes (rimphony_tab_grid_group.hip): "group" like the others, NOT MEASURED either
-// (profiles/tabulated_grid_times.txt)
-static const bool RIM_TAB_GROUP_DEFAULT_GRID = true;
 static bool rim_tab_runs_group(const rimphony_ctx *c)
 {
     if (c->knobs.tab_group >= 0) return c->knobs.tab_group != 0;
-    if (c->tab_form == RIM_TAB_FORM_GRID) return RIM_TAB_GROUP_DEFAULT_GRID;
-    return RIM_TAB_GROUP_DEFAULT[c->tab_form];
+    return RIM_TAB_GROUP_DEFAULT[c->tab_kind - DIST_TABULATED];
 }
 
 // `precision` of the batch entries.  F64 is the product.  F32_INTEGRAND (BASELINE configs[4]'s fp32-core integrand) is
@@ -1500,7 +1448,7 @@ extern "C" int rimphony_gamma_integrand_batch_device(rimphony_ctx *c, int kind, 
     rc = single_point_norm(c, kind, params, st);
     if (rc) return rc;
     const dim3 grid((unsigned) ((count + 63) / 64)), block(64);
-    if (kind == RIMPHONY_TABULATED) rim_tab_launch_integrand(c->tab_form, grid.x, st, pa, c->d_norm.p, count, d_n, d_gamma, d_out);
+    if (kind == RIMPHONY_TABULATED) rim_tab_launch_integrand(c->tab_kind, grid.x, st, pa, c->d_norm.p, count, d_n, d_gamma, d_out);
     else rim_with_kind(kind, [&](auto K) { hipLaunchKernelGGL(integrand_kernel_n<decltype(K)::value>, grid, block, RIM_DYN_LDS, st, pa, c->d_norm.p, count, d_n, d_gamma, d_out); });
     HIP_TRY(hipGetLastError());
     return RIMPHONY_OK;
@@ -1523,9 +1471,7 @@ int rim_wave_grid(rimphony_ctx *c, size_t count, int waves_per_cu, unsigned *gri
 const double *rim_ctx_norm(const rimphony_ctx *c) { return c->d_norm.p; }
 int rim_ctx_dist_kind(const rimphony_ctx *c, int kind)
 {
-    if (kind != RIMPHONY_TABULATED) return kind;
-    if (c->tab_form == RIM_TAB_FORM_GRID) return (int) DIST_TABULATED_GRID;
-    return c->tab_form == RIM_TAB_FORM_2D ? (int) DIST_TABULATED_2D : c->tab_form == RIM_TAB_FORM_PITCHY ? (int) DIST_TABULATED_PITCHY : kind;
+    return kind == RIMPHONY_TABULATED ? rim_tab_seam_kind(c->tab_kind) : kind;
 }
 double *rim_ctx_spill(const rimphony_ctx *c) { return c->d_spill.p; }
 
@@ -1547,7 +1493,7 @@ extern "C" int rimphony_gamma_integral_batch_device(rimphony_ctx *c, int kind, c
     const unsigned grid = persistent_grid(c, count, 16);
     rc = ensure_spill(c, grid);
     if (rc) return rc;
-    if (kind == RIMPHONY_TABULATED) rim_tab_launch_gamma_integral(c->tab_form, grid, st, pa, c->d_norm.p, count, d_n, d_out, c->d_spill.p);
+    if (kind == RIMPHONY_TABULATED) rim_tab_launch_gamma_integral(c->tab_kind, grid, st, pa, c->d_norm.p, count, d_n, d_out, c->d_spill.p);
     else rim_with_kind(kind, [&](auto K) { hipLaunchKernelGGL(gamma_integral_kernel<decltype(K)::value>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pa, c->d_norm.p, count, d_n, d_out, c->d_spill.p); });
     HIP_TRY(hipGetLastError());
     return RIMPHONY_OK;

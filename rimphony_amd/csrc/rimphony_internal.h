@@ -92,15 +92,14 @@ struct RimCtxScope {
     RimCtxScope &operator=(const RimCtxScope &) = delete;
 };
 const double *rim_ctx_norm(const rimphony_ctx *c);
-// the distribution kind whose instantiation serves `kind` on this context: DIST_TABULATED_2D (dev_symphony.h) for
-// RIMPHONY_TABULATED while a 2-D table set is installed, DIST_TABULATED_PITCHY while one with a sin^k prefactor is, `kind`
-// (DIST_TABULATED_GRID while one on given gamma nodes is), itself otherwise
+// the distribution kind whose instantiation serves `kind` on this context: for RIMPHONY_TABULATED the form of the installed
+// table set as rim_tab_seam_kind reads it, `kind` itself otherwise
 int rim_ctx_dist_kind(const rimphony_ctx *c, int kind);
 double *rim_ctx_spill(const rimphony_ctx *c);
 
 // The one place where a run-time distribution kind picks a template instantiation: f(std::integral_constant<int, K>{}).
-// Every entry has validated `kind` before, so anything else is kind 3 (kind 4, the tabulated distribution, never gets here:
-// rim_with_kind5, and rimphony_tab.hip for the kernels of coop_kernel.h).
+// Every entry has validated `kind` before, so anything else is kind 3 (the tabulated distribution never gets here:
+// rim_with_tab_kind below).
 template <class F>
 auto rim_with_kind(int kind, F &&f)
 {
@@ -112,18 +111,35 @@ auto rim_with_kind(int kind, F &&f)
     }
 }
 
-// The same for the translation units that also serve the tabulated distribution (kind 4, and 6 = DIST_TABULATED_2D and
-// 7 = DIST_TABULATED_PITCHY, its forms for a 2-D table set and for one with a sin^k prefactor: rim_ctx_dist_kind).  rimphony_group.hip keeps the four-way form: its kernels exist for the
-// four analytic kinds only; the tabulated kind's group kernels are reached by the form of the table set (tab_launch.h:
-// rim_tab_group_kernel, rimphony_tab_group.hip).
+// The same for the tabulated distribution, whose instantiations go by the form of the installed table set: the set's
+// DIST_TABULATED* value (dev_symphony.h), which is what a context remembers, the cell of its occupancy caches and the
+// argument of tab_launch.h.  Anything but the four named forms is DIST_TABULATED, a set with pitch rows.
+template <class F>
+auto rim_with_tab_kind(int tab_kind, F &&f)
+{
+    using namespace rim;
+    switch (tab_kind) {
+    case DIST_TABULATED_ISO: return f(std::integral_constant<int, DIST_TABULATED_ISO>{});
+    case DIST_TABULATED_2D: return f(std::integral_constant<int, DIST_TABULATED_2D>{});
+    case DIST_TABULATED_PITCHY: return f(std::integral_constant<int, DIST_TABULATED_PITCHY>{});
+    case DIST_TABULATED_GRID: return f(std::integral_constant<int, DIST_TABULATED_GRID>{});
+    default: return f(std::integral_constant<int, DIST_TABULATED>{});
+    }
+}
+
+// Only coop_kernel and group_kernel have an instantiation for DIST_TABULATED_ISO (the persistent kernels keep the code
+// isotropic tables always ran); every other kernel reads a set without pitch rows with its DIST_TABULATED instantiation,
+// same bits.  This is the one place that says so.
+constexpr int rim_tab_seam_kind(int tab_kind) { return tab_kind == rim::DIST_TABULATED_ISO ? (int) rim::DIST_TABULATED : tab_kind; }
+
+// rim_with_kind for the translation units whose kernels serve all kinds (rim_ctx_dist_kind supplies `kind`).
+// rimphony_group.hip keeps the four-way form: its kernels exist for the four analytic kinds only; the tabulated kind's
+// group kernels are reached through tab_launch.h (rim_tab_group_kernel).
 template <class F>
 auto rim_with_kind5(int kind, F &&f)
 {
-    if (kind == 4) return f(std::integral_constant<int, 4>{});
-    if (kind == 6) return f(std::integral_constant<int, 6>{});
-    if (kind == 7) return f(std::integral_constant<int, 7>{});
-    if (kind == 8) return f(std::integral_constant<int, 8>{});      // DIST_TABULATED_GRID, a set on given gamma nodes
-    return rim_with_kind(kind, f);
+    if (!rim::dist_is_tab(kind)) return rim_with_kind(kind, f);
+    return rim_with_tab_kind(kind, [&](auto K) { return f(std::integral_constant<int, rim_tab_seam_kind(decltype(K)::value)>{}); });
 }
 
 // Leaves the calling thread on the device it came with, whichever way the scope ends.

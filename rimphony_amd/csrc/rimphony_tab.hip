@@ -2,7 +2,8 @@
 // the one-wave-per-coefficient Symphony and Faraday kernels and the two unit seams of coop_kernel.h.  The kind's group
 // kernels -- the Symphony coefficients of a point in lock-step -- have a unit of their own, rimphony_tab_group.hip
 // (rimphony_group.hip keeps its four instantiations); which of the two runs the Symphony slots of a form is
-// RIM_TAB_GROUP_DEFAULT's and RIMPHONY_TAB_GROUP's matter (rimphony_hip.hip).  A sample reads its four spline words with plain
+// RIM_TAB_GROUP_DEFAULT's and RIMPHONY_TAB_GROUP's matter (rimphony_hip.hip).  Every host function here takes the form of the
+// installed set as its DIST_TABULATED* value and is one dispatch over it (rimphony_internal.h: rim_with_tab_kind).  A sample reads its four spline words with plain
 // global loads -- a 4096-node table is 64 KB and stays in cache.  A table with a pitch-angle factor g(cos xi) reads four more
 // from its pitch row, whose address travels in par[0] (dev_symphony.h: dist_prepare<DIST_TABULATED>, tab_pitch_spline).
 // The two persistent kernels exist twice: for sets with pitch rows and, "no pitch row" known at compile time, for sets without.
@@ -111,69 +112,42 @@ static RimCoopKernelInfo coop_info()
 
 // A set without pitch rows runs the instantiations that know so at compile time (DIST_TABULATED_ISO): the code isotropic
 // tables had before the pitch factor existed.  Same bits either way.
-RimCoopKernelInfo rim_tab_coop_kernel(int problem, int form)
+RimCoopKernelInfo rim_tab_coop_kernel(int problem, int tab_kind)
 {
-    if (form == RIM_TAB_FORM_2D)
-        return problem ? coop_info<HeyvaertsProblem<DIST_TABULATED_2D>>() : coop_info<SymphonyProblem<DIST_TABULATED_2D>>();
-    if (form == RIM_TAB_FORM_PITCHY)
-        return problem ? coop_info<HeyvaertsProblem<DIST_TABULATED_PITCHY>>() : coop_info<SymphonyProblem<DIST_TABULATED_PITCHY>>();
-    if (form == RIM_TAB_FORM_GRID)
-        return problem ? coop_info<HeyvaertsProblem<DIST_TABULATED_GRID>>() : coop_info<SymphonyProblem<DIST_TABULATED_GRID>>();
-    const bool pitch = form == RIM_TAB_FORM_PITCH;
-    if (problem) return pitch ? coop_info<HeyvaertsProblem<DIST_TABULATED>>() : coop_info<HeyvaertsProblem<DIST_TABULATED_ISO>>();
-    return pitch ? coop_info<SymphonyProblem<DIST_TABULATED>>() : coop_info<SymphonyProblem<DIST_TABULATED_ISO>>();
+    return rim_with_tab_kind(tab_kind, [&](auto K) {
+        constexpr int KIND = decltype(K)::value;
+        return problem ? coop_info<HeyvaertsProblem<KIND>>() : coop_info<SymphonyProblem<KIND>>();
+    });
 }
 
-void rim_tab_launch_norm(int form, unsigned grid, hipStream_t st, const ParamPtrs &pp, size_t n, double *d_norm,
+// The next three kernels have no DIST_TABULATED_ISO instantiation: an isotropic set runs DIST_TABULATED's
+// (rim_tab_seam_kind).  The rows of a 2-D set read their table's normalisation; no norm_kernel exists for that form.
+void rim_tab_launch_norm(int tab_kind, unsigned grid, hipStream_t st, const ParamPtrs &pp, size_t n, double *d_norm,
                          unsigned long long *queue, double *spill)
 {
-    if (form == RIM_TAB_FORM_2D) {
-        hipLaunchKernelGGL(tab2d_row_norm_kernel, dim3((unsigned) ((n + 255) / 256)), dim3(256), RIM_DYN_LDS, st, pp, n, d_norm);
-        return;
-    }
-    if (form == RIM_TAB_FORM_PITCHY) {
-        hipLaunchKernelGGL(norm_kernel<DIST_TABULATED_PITCHY>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pp, n, d_norm, queue, spill);
-        return;
-    }
-    if (form == RIM_TAB_FORM_GRID) {
-        hipLaunchKernelGGL(norm_kernel<DIST_TABULATED_GRID>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pp, n, d_norm, queue, spill);
-        return;
-    }
-    hipLaunchKernelGGL(norm_kernel<DIST_TABULATED>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pp, n, d_norm, queue, spill);
+    rim_with_tab_kind(tab_kind, [&](auto K) {
+        constexpr int KIND = rim_tab_seam_kind(decltype(K)::value);
+        if constexpr (KIND == DIST_TABULATED_2D)
+            hipLaunchKernelGGL(tab2d_row_norm_kernel, dim3((unsigned) ((n + 255) / 256)), dim3(256), RIM_DYN_LDS, st, pp, n, d_norm);
+        else
+            hipLaunchKernelGGL(norm_kernel<KIND>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pp, n, d_norm, queue, spill);
+    });
 }
 
-void rim_tab_launch_integrand(int form, unsigned grid, hipStream_t st, const PointArgs &pa, const double *d_norm, size_t count,
+void rim_tab_launch_integrand(int tab_kind, unsigned grid, hipStream_t st, const PointArgs &pa, const double *d_norm, size_t count,
                               const double *d_n, const double *d_gamma, double *d_out)
 {
-    if (form == RIM_TAB_FORM_2D) {
-        hipLaunchKernelGGL(integrand_kernel_n<DIST_TABULATED_2D>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pa, d_norm, count, d_n, d_gamma, d_out);
-        return;
-    }
-    if (form == RIM_TAB_FORM_PITCHY) {
-        hipLaunchKernelGGL(integrand_kernel_n<DIST_TABULATED_PITCHY>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pa, d_norm, count, d_n, d_gamma, d_out);
-        return;
-    }
-    if (form == RIM_TAB_FORM_GRID) {
-        hipLaunchKernelGGL(integrand_kernel_n<DIST_TABULATED_GRID>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pa, d_norm, count, d_n, d_gamma, d_out);
-        return;
-    }
-    hipLaunchKernelGGL(integrand_kernel_n<DIST_TABULATED>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pa, d_norm, count, d_n, d_gamma, d_out);
+    rim_with_tab_kind(tab_kind, [&](auto K) {
+        constexpr int KIND = rim_tab_seam_kind(decltype(K)::value);
+        hipLaunchKernelGGL(integrand_kernel_n<KIND>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pa, d_norm, count, d_n, d_gamma, d_out);
+    });
 }
 
-void rim_tab_launch_gamma_integral(int form, unsigned grid, hipStream_t st, const PointArgs &pa, const double *d_norm, size_t count,
+void rim_tab_launch_gamma_integral(int tab_kind, unsigned grid, hipStream_t st, const PointArgs &pa, const double *d_norm, size_t count,
                                    const double *d_n, double *d_out, double *spill)
 {
-    if (form == RIM_TAB_FORM_2D) {
-        hipLaunchKernelGGL(gamma_integral_kernel<DIST_TABULATED_2D>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pa, d_norm, count, d_n, d_out, spill);
-        return;
-    }
-    if (form == RIM_TAB_FORM_PITCHY) {
-        hipLaunchKernelGGL(gamma_integral_kernel<DIST_TABULATED_PITCHY>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pa, d_norm, count, d_n, d_out, spill);
-        return;
-    }
-    if (form == RIM_TAB_FORM_GRID) {
-        hipLaunchKernelGGL(gamma_integral_kernel<DIST_TABULATED_GRID>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pa, d_norm, count, d_n, d_out, spill);
-        return;
-    }
-    hipLaunchKernelGGL(gamma_integral_kernel<DIST_TABULATED>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pa, d_norm, count, d_n, d_out, spill);
+    rim_with_tab_kind(tab_kind, [&](auto K) {
+        constexpr int KIND = rim_tab_seam_kind(decltype(K)::value);
+        hipLaunchKernelGGL(gamma_integral_kernel<KIND>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pa, d_norm, count, d_n, d_out, spill);
+    });
 }

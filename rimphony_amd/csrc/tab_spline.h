@@ -38,12 +38,17 @@
 #define RIM_TAB_MIN_NODES 8
 #define RIM_TAB_MAX_NODES 65536
 
-// 0, or -1 for bad geometry or a non-finite value
+// the checks say 0, or -1 for bad geometry or a non-finite value.  The range of a set: finite, 1 <= gamma_lo < gamma_hi
+inline int rim_tab_check_range(double gamma_lo, double gamma_hi)
+{
+    return (!rim_isfinite(gamma_lo) || !rim_isfinite(gamma_hi) || !(gamma_lo >= 1.) || !(gamma_lo < gamma_hi)) ? -1 : 0;
+}
+
 inline int rim_tab_check(size_t n_tables, size_t n_nodes, double gamma_lo, double gamma_hi, const double *log_n)
 {
     if (n_tables < 1 || n_nodes < RIM_TAB_MIN_NODES || n_nodes > RIM_TAB_MAX_NODES || !log_n) return -1;
     if (n_tables > ((size_t) 1 << 40) / n_nodes) return -1;
-    if (!rim_isfinite(gamma_lo) || !rim_isfinite(gamma_hi) || !(gamma_lo >= 1.) || !(gamma_lo < gamma_hi)) return -1;
+    if (rim_tab_check_range(gamma_lo, gamma_hi)) return -1;
     for (size_t i = 0; i < n_tables * n_nodes; i++)
         if (!rim_isfinite(log_n[i])) return -1;
     return 0;
@@ -68,6 +73,21 @@ inline void rim_tab_spline_row(const double *y, size_t n, double h, double *row,
     for (size_t j = 0; j <= last; j++) row[2 * j] = y[j];
 }
 
+// the eight words every set begins with (dev_symphony.h, TAB_HDR_*)
+inline void rim_tab_set_header(double *hdr, size_t n_tables, size_t n_nodes, double gamma_lo, double gamma_hi, double u_lo,
+                               double inv_h, double h, double n_mu)
+{
+    using namespace rim;
+    hdr[TAB_HDR_NTABLES] = (double) n_tables;
+    hdr[TAB_HDR_NNODES] = (double) n_nodes;
+    hdr[TAB_HDR_GLO] = gamma_lo;
+    hdr[TAB_HDR_GHI] = gamma_hi;
+    hdr[TAB_HDR_ULO] = u_lo;
+    hdr[TAB_HDR_INVH] = inv_h;
+    hdr[TAB_HDR_H] = h;
+    hdr[TAB_HDR_NMU] = n_mu;
+}
+
 // the table set as one block of doubles; rim_tab_check() has passed
 inline void rim_tab_build(size_t n_tables, size_t n_nodes, double gamma_lo, double gamma_hi, const double *log_n,
                           std::vector<double> &blob)
@@ -76,13 +96,7 @@ inline void rim_tab_build(size_t n_tables, size_t n_nodes, double gamma_lo, doub
     const double u_lo = rim_log(gamma_lo), u_hi = rim_log(gamma_hi);
     const double h = (u_hi - u_lo) / (double) (n_nodes - 1);
     blob.assign((size_t) TAB_HDR_DOUBLES + n_tables * n_nodes * 2, 0.);
-    blob[TAB_HDR_NTABLES] = (double) n_tables;
-    blob[TAB_HDR_NNODES] = (double) n_nodes;
-    blob[TAB_HDR_GLO] = gamma_lo;
-    blob[TAB_HDR_GHI] = gamma_hi;
-    blob[TAB_HDR_ULO] = u_lo;
-    blob[TAB_HDR_INVH] = 1. / h;
-    blob[TAB_HDR_H] = h;
+    rim_tab_set_header(blob.data(), n_tables, n_nodes, gamma_lo, gamma_hi, u_lo, 1. / h, h, 0.);
     std::vector<double> cp(n_nodes), dp(n_nodes);
     for (size_t t = 0; t < n_tables; t++)
         rim_tab_spline_row(log_n + t * n_nodes, n_nodes, h, blob.data() + TAB_HDR_DOUBLES + t * n_nodes * 2, cp.data(), dp.data());
@@ -142,14 +156,20 @@ inline void rim_tab_build_pitch(size_t n_tables, size_t n_nodes, double gamma_lo
 
 #define RIM_TAB_MAX_SIN_K 100.
 
-// rim_tab_check_pitch() for a set with a sin^k xi prefactor: sin_k [n_tables], every k finite and in [0, RIM_TAB_MAX_SIN_K]
+// sin_k [n_tables]: every k finite and in [0, RIM_TAB_MAX_SIN_K]
+inline int rim_tab_check_sin_k(size_t n_tables, const double *sin_k)
+{
+    for (size_t t = 0; t < n_tables; t++)
+        if (!rim_isfinite(sin_k[t]) || !(sin_k[t] >= 0.) || !(sin_k[t] <= RIM_TAB_MAX_SIN_K)) return -1;
+    return 0;
+}
+
+// rim_tab_check_pitch() for a set with a sin^k xi prefactor, sin_k as above
 inline int rim_tab_check_pitchy(size_t n_tables, size_t n_nodes, double gamma_lo, double gamma_hi, const double *log_n,
                                 size_t n_mu, const double *log_g, const double *sin_k)
 {
     if (rim_tab_check_pitch(n_tables, n_nodes, gamma_lo, gamma_hi, log_n, n_mu, log_g) || !sin_k) return -1;
-    for (size_t t = 0; t < n_tables; t++)
-        if (!rim_isfinite(sin_k[t]) || !(sin_k[t] >= 0.) || !(sin_k[t] <= RIM_TAB_MAX_SIN_K)) return -1;
-    return 0;
+    return rim_tab_check_sin_k(n_tables, sin_k);
 }
 
 // 1/2 int (1 - mu^2)^(k/2) dmu = Gamma(3/2) Gamma(1 + k/2) / Gamma(3/2 + k/2): hyperg_2F1_at_1(0.5, -0.5 k, 1.5) of
@@ -165,6 +185,25 @@ inline double rim_tab_sin_k_integral(double k)
     return rim_exp(lc + lcab - lca - lcb);
 }
 
+// Table t of the sin^k tables that start at `tables` (dev_symphony.h: TAB_PITCHY_*): its k and, for n_mu > 0, its pitch
+// row from log_g at nodes hm apart (P is 0 as built), else the closed form of P.  cp, dp: n_mu doubles.
+inline void rim_tab_build_pitchy_table(double *tables, size_t t, double k, size_t n_mu, const double *log_g, double hm,
+                                       double *cp, double *dp)
+{
+    using namespace rim;
+    double *ph = tables + t * ((size_t) TAB_PITCHY_PRE + TAB_PITCH_HDR + n_mu * 2) + TAB_PITCHY_PRE;
+    ph[TAB_PITCHY_K] = k;
+    ph[TAB_PITCHY_NMU] = (double) n_mu;
+    if (!n_mu) {
+        ph[TAB_PITCH_P] = rim_tab_sin_k_integral(k);
+        return;
+    }
+    ph[TAB_PITCH_LAST] = (double) (n_mu - 2);
+    ph[TAB_PITCH_INVH] = 1. / hm;
+    ph[TAB_PITCH_H] = hm;
+    rim_tab_spline_row(log_g + t * n_mu, n_mu, hm, ph + TAB_PITCH_HDR, cp, dp);
+}
+
 // the set with a sin^k prefactor as one block of doubles (dev_symphony.h: TAB_PITCHY_*); rim_tab_check_pitchy() has passed
 inline void rim_tab_build_pitchy(size_t n_tables, size_t n_nodes, double gamma_lo, double gamma_hi, const double *log_n,
                                  size_t n_mu, const double *log_g, const double *sin_k, std::vector<double> &blob)
@@ -172,24 +211,13 @@ inline void rim_tab_build_pitchy(size_t n_tables, size_t n_nodes, double gamma_l
     using namespace rim;
     rim_tab_build(n_tables, n_nodes, gamma_lo, gamma_hi, log_n, blob);
     if (!log_g) n_mu = 0;
-    const size_t base = blob.size(), stride = (size_t) TAB_PITCHY_PRE + TAB_PITCH_HDR + n_mu * 2;
-    blob.resize(base + n_tables * stride, 0.);
+    const size_t base = blob.size();
+    blob.resize(base + n_tables * ((size_t) TAB_PITCHY_PRE + TAB_PITCH_HDR + n_mu * 2), 0.);
     blob[TAB_HDR_NMU] = (double) n_mu;
     const double h = n_mu ? 2. / (double) (n_mu - 1) : 0.;
     std::vector<double> cp(n_mu), dp(n_mu);
-    for (size_t t = 0; t < n_tables; t++) {
-        double *ph = blob.data() + base + t * stride + TAB_PITCHY_PRE;
-        ph[TAB_PITCHY_K] = sin_k[t];
-        ph[TAB_PITCHY_NMU] = (double) n_mu;
-        if (!n_mu) {
-            ph[TAB_PITCH_P] = rim_tab_sin_k_integral(sin_k[t]);
-            continue;
-        }
-        ph[TAB_PITCH_LAST] = (double) (n_mu - 2);
-        ph[TAB_PITCH_INVH] = 1. / h;
-        ph[TAB_PITCH_H] = h;
-        rim_tab_spline_row(log_g + t * n_mu, n_mu, h, ph + TAB_PITCH_HDR, cp.data(), dp.data());
-    }
+    for (size_t t = 0; t < n_tables; t++)
+        rim_tab_build_pitchy_table(blob.data() + base, t, sin_k[t], n_mu, log_g, h, cp.data(), dp.data());
 }
 
 // rim_tab_check_pitchy() for a set on given nodes: gamma [n_nodes], finite, 1 <= gamma[0], strictly increasing, and so
@@ -208,10 +236,7 @@ inline int rim_tab_check_grid(size_t n_tables, size_t n_nodes, const double *gam
         if (!(rim_log(gamma[j]) < rim_log(gamma[j + 1]))) return -1;
     }
     if (rim_tab_check_pitch(n_tables, n_nodes, gamma[0], gamma[n_nodes - 1], log_n, n_mu, log_g)) return -1;
-    if (sin_k)
-        for (size_t t = 0; t < n_tables; t++)
-            if (!rim_isfinite(sin_k[t]) || !(sin_k[t] >= 0.) || !(sin_k[t] <= RIM_TAB_MAX_SIN_K)) return -1;
-    return 0;
+    return sin_k ? rim_tab_check_sin_k(n_tables, sin_k) : 0;
 }
 
 // The slopes m[0 .. n-1] of the natural cubic spline through (u_j, y[j]) on nodes h[j] = u_{j+1} - u_j apart, ih[j] = 1 / h[j]:
@@ -250,14 +275,7 @@ inline void rim_tab_build_grid(size_t n_tables, size_t n_nodes, const double *ga
     for (size_t j = 0; j + 1 < n_nodes; j++) { h[j] = u[j + 1] - u[j]; ih[j] = 1. / h[j]; }
     h[n_nodes - 1] = 0.; ih[n_nodes - 1] = 0.;
     const double inv_cell = (double) cells / (u[n_nodes - 1] - u[0]);
-    blob[TAB_HDR_NTABLES] = (double) n_tables;
-    blob[TAB_HDR_NNODES] = (double) n_nodes;
-    blob[TAB_HDR_GLO] = gamma[0];
-    blob[TAB_HDR_GHI] = gamma[n_nodes - 1];
-    blob[TAB_HDR_ULO] = u[0];
-    blob[TAB_HDR_INVH] = inv_cell;
-    blob[TAB_HDR_H] = (double) cells;
-    blob[TAB_HDR_NMU] = (double) n_mu;
+    rim_tab_set_header(blob.data(), n_tables, n_nodes, gamma[0], gamma[n_nodes - 1], u[0], inv_cell, (double) cells, (double) n_mu);
     // the guide: word c = min(the last node in a cell below c, n_nodes - 2), 0 where there is none
     uint32_t *guide = (uint32_t *) (blob.data() + TAB_HDR_DOUBLES);
     size_t j = 0;
@@ -280,26 +298,11 @@ inline void rim_tab_build_grid(size_t n_tables, size_t n_nodes, const double *ga
     }
     // the tail: a sin^k set's table headers and pitch rows behind a header that names no gamma nodes
     double *th = blob.data() + tail;
-    th[TAB_HDR_NTABLES] = (double) n_tables;
-    th[TAB_HDR_GLO] = gamma[0];
-    th[TAB_HDR_GHI] = gamma[n_nodes - 1];
-    th[TAB_HDR_NMU] = (double) n_mu;
+    rim_tab_set_header(th, n_tables, 0, gamma[0], gamma[n_nodes - 1], 0., 0., 0., (double) n_mu);
     const double hm = n_mu ? 2. / (double) (n_mu - 1) : 0.;
     std::vector<double> cpm(n_mu), dpm(n_mu);
-    for (size_t t = 0; t < n_tables; t++) {
-        double *ph = th + TAB_HDR_DOUBLES + t * stride + TAB_PITCHY_PRE;
-        const double k = sin_k ? sin_k[t] : 0.;
-        ph[TAB_PITCHY_K] = k;
-        ph[TAB_PITCHY_NMU] = (double) n_mu;
-        if (!n_mu) {
-            ph[TAB_PITCH_P] = rim_tab_sin_k_integral(k);
-            continue;
-        }
-        ph[TAB_PITCH_LAST] = (double) (n_mu - 2);
-        ph[TAB_PITCH_INVH] = 1. / hm;
-        ph[TAB_PITCH_H] = hm;
-        rim_tab_spline_row(log_g + t * n_mu, n_mu, hm, ph + TAB_PITCH_HDR, cpm.data(), dpm.data());
-    }
+    for (size_t t = 0; t < n_tables; t++)
+        rim_tab_build_pitchy_table(th + TAB_HDR_DOUBLES, t, sin_k ? sin_k[t] : 0., n_mu, log_g, hm, cpm.data(), dpm.data());
 }
 
 #define RIM_TAB_2D_MIN_MU 8
@@ -312,7 +315,7 @@ inline int rim_tab_check_2d(size_t n_tables, size_t n_nodes, double gamma_lo, do
     if (n_tables < 1 || n_nodes < RIM_TAB_MIN_NODES || n_nodes > RIM_TAB_MAX_NODES || !log_n) return -1;
     if (n_mu < RIM_TAB_2D_MIN_MU || n_mu > RIM_TAB_2D_MAX_MU || n_nodes * n_mu > RIM_TAB_2D_MAX_CELLS) return -1;
     if (n_tables > ((size_t) 1 << 40) / (n_nodes * n_mu)) return -1;
-    if (!rim_isfinite(gamma_lo) || !rim_isfinite(gamma_hi) || !(gamma_lo >= 1.) || !(gamma_lo < gamma_hi)) return -1;
+    if (rim_tab_check_range(gamma_lo, gamma_hi)) return -1;
     for (size_t i = 0; i < n_tables * n_nodes * n_mu; i++)
         if (!rim_isfinite(log_n[i])) return -1;
     return 0;
@@ -330,14 +333,7 @@ inline void rim_tab_build_2d(size_t n_tables, size_t n_nodes, double gamma_lo, d
     const double hm = 2. / (double) (n_mu - 1);
     const size_t per_table = n_nodes * n_mu * 4;
     blob.assign((size_t) TAB_HDR_DOUBLES + n_tables * TAB_2D_HDR + n_tables * per_table, 0.);
-    blob[TAB_HDR_NTABLES] = (double) n_tables;
-    blob[TAB_HDR_NNODES] = (double) n_nodes;
-    blob[TAB_HDR_GLO] = gamma_lo;
-    blob[TAB_HDR_GHI] = gamma_hi;
-    blob[TAB_HDR_ULO] = u_lo;
-    blob[TAB_HDR_INVH] = 1. / h;
-    blob[TAB_HDR_H] = h;
-    blob[TAB_HDR_NMU] = -(double) n_mu;
+    rim_tab_set_header(blob.data(), n_tables, n_nodes, gamma_lo, gamma_hi, u_lo, 1. / h, h, -(double) n_mu);
     const size_t longest = n_nodes > n_mu ? n_nodes : n_mu;
     std::vector<double> y(longest), pairs(2 * longest), cp(longest), dp(longest);
     for (size_t t = 0; t < n_tables; t++) {

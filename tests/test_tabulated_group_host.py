@@ -63,10 +63,9 @@ def test_build_and_export():
     for recipe in ("build_variant.sh", "build_prof.sh"):
         for line in open(os.path.join(ROOT, "tools", recipe)):
             assert ("rimphony_tab.hip" in line) == ("rimphony_tab_group.hip" in line), (recipe, line)
-    assert re.search(r"const void \*rim_tab_group_kernel\(int form\);", open(os.path.join(CSRC, "tab_launch.h")).read())
-    unit = open(UNIT).read()
-    for k in ("DIST_TABULATED", "DIST_TABULATED_ISO", "DIST_TABULATED_2D", "DIST_TABULATED_PITCHY"):
-        assert "group_kernel<SymGroupProblem<%s>>" % k in unit
+    assert re.search(r"const void \*rim_tab_group_kernel\(int tab_kind\);", open(os.path.join(CSRC, "tab_launch.h")).read())
+    # (which instantiations the unit holds is test_tab_group_kernel_resources_leave_room_for_its_grid's exact name set)
+    assert "group_kernel<SymGroupProblem<KIND>>" in open(UNIT).read()
     group = open(os.path.join(CSRC, "rimphony_group.hip")).read()
     assert "DIST_TABULATED" not in group and "rim_with_kind5" not in group
     assert "group_kernel<SymGroupProblem<KIND>>" in group and "rim_with_kind(kind" in group
@@ -84,7 +83,7 @@ def test_build_and_export():
 
 def test_knob_text():
     """RIMPHONY_TAB_GROUP is in the knob table and in DESIGN.md's table of environment variables with the same default,
-    and the per-form default table cites the measurement it comes from."""
+    and the one per-form default table cites the measurements it comes from."""
     src = open(os.path.join(CSRC, "rimphony_hip.hip")).read()
     m = re.search(r'\{ "RIMPHONY_TAB_GROUP", KNOB_INT, &RimKnobs::tab_group, (-?\d+), INT_MIN, 1,', src)
     assert m and int(m.group(1)) == -1
@@ -94,6 +93,11 @@ def test_knob_text():
     assert len(row) == 1
     cells = [c.strip() for c in row[0].split("|")]
     assert cells[3].startswith("-1") and "at most 1" in cells[2]
-    dflt = src[src.index("RIM_TAB_GROUP_DEFAULT[4]") - 600:src.index("RIM_TAB_GROUP_DEFAULT[4]")]
-    assert "profiles/tabulated_group_times.txt" in dflt
-    assert os.path.exists(os.path.join(ROOT, "profiles", "tabulated_group_times.txt"))
+    # one table for the five forms; the comment above it cites both measurement files
+    assert len(re.findall(r"^static const bool RIM_TAB_GROUP_DEFAULT\w*", src, re.M)) == 1
+    at = src.index("static const bool RIM_TAB_GROUP_DEFAULT[5]")
+    dflt = src[at - 600:at]
+    dflt = dflt[dflt.index("// Where the Symphony slots of the tabulated distribution run"):]
+    for cited in ("profiles/tabulated_group_times.txt", "profiles/tabulated_grid_times.txt"):
+        assert cited in dflt
+        assert os.path.exists(os.path.join(ROOT, cited))

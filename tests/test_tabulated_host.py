@@ -5,6 +5,7 @@ refuse what the library refuses.  CPU only."""
 import ctypes
 import os
 import re
+import subprocess
 
 import numpy as np
 import pytest
@@ -46,17 +47,33 @@ def test_kind_and_entry_in_library_header_and_mirrors():
     assert "class TabulatedDistribution" in hpp and "rimphony_ctx_set_tables" in hpp
 
 
-def test_group_unit_keeps_four_way_dispatch():
-    """The kind never runs on the group kernels: their translation unit dispatches over the four analytic kinds only, and
-    the kernels of kind 4 have a unit of their own that the build compiles."""
+def test_group_unit_keeps_four_way_dispatch(tmp_path):
+    """The kind never runs on the analytic kinds' group kernels: their translation unit dispatches over the four analytic
+    kinds only, and the kernels of kind 4 have a unit of their own that the build compiles.  That unit, compiled alone for
+    gfx950, defines exactly its 24 kernels, by mangled name: the three of a set's installation and 2-D row norms, the two
+    persistent kernels for all five forms (K = DIST_TABULATED .. DIST_TABULATED_GRID = 4 .. 8), norm_kernel for the forms
+    that have one (a 2-D set's rows load theirs; an isotropic set runs K = 4) and the two unit seams for K = 4, 6, 7, 8."""
     from rimphony_amd import _build
     csrc = os.path.join(ROOT, "rimphony_amd", "csrc")
     group = open(os.path.join(csrc, "rimphony_group.hip")).read()
     assert "rim_with_kind5" not in group and "DIST_TABULATED" not in group
-    assert os.path.join(csrc, "rimphony_tab.hip") in _build.hip_sources()
-    tab = open(os.path.join(csrc, "rimphony_tab.hip")).read()
-    for inst in ("SymphonyProblem<DIST_TABULATED>", "HeyvaertsProblem<DIST_TABULATED>", "norm_kernel<DIST_TABULATED>"):
-        assert inst in tab
+    unit = os.path.join(csrc, "rimphony_tab.hip")
+    assert unit in _build.hip_sources()
+    hipcc = _build.find_hipcc()
+    if hipcc is None:
+        pytest.skip("no hipcc")
+    flags = [f for f in _build.HIPCC_FLAGS if f not in ("-shared", "-fPIC")]
+    r = subprocess.run([hipcc] + flags + ["--cuda-device-only", "-S", unit, "-o", str(tmp_path / "tab.s")],
+                       capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-2000:]
+    got = re.findall(r"^\s*\.amdhsa_kernel (\S+)$", open(tmp_path / "tab.s").read(), re.M)
+    want = ["_Z23tab2d_table_norm_kernelPdS_", "_Z21tab2d_row_norm_kernel9ParamPtrsmPd", "_Z25tab_pitchy_table_p_kernelPdS_"]
+    want += ["_Z11coop_kernelI15SymphonyProblemILi%dELi0EEEv7SymArgs" % k for k in (4, 5, 6, 7, 8)]
+    want += ["_Z11coop_kernelI16HeyvaertsProblemILi%dEEEv7SymArgs" % k for k in (4, 5, 6, 7, 8)]
+    want += ["_Z11norm_kernelILi%dEEv9ParamPtrsmPdPyS1_" % k for k in (4, 7, 8)]
+    want += ["_Z18integrand_kernel_nILi%dEEv9PointArgsPKdmS2_S2_Pd" % k for k in (4, 6, 7, 8)]
+    want += ["_Z21gamma_integral_kernelILi%dEEv9PointArgsPKdmS2_PdS3_" % k for k in (4, 6, 7, 8)]
+    assert len(want) == 24 and sorted(got) == sorted(want)
 
 
 def test_straight_line_table_is_the_power_law():
