@@ -446,99 +446,50 @@ class Context:
         torch.cuda.synchronize(self._dev())
         return j.cpu().numpy(), dj.cpu().numpy()
 
-    def gamma_integrand_batch(self, kind, params, coeff, stokes, s, theta, n, gamma):
-        dn, dg = self._as_dev(n), self._as_dev(gamma)
-        out = torch.empty_like(dn)
-        par = (ctypes.c_double * len(params))(*params)
-        capi.check(self.lib.rimphony_gamma_integrand_batch_device(
-            self.handle, kind, par, int(coeff), int(stokes), s, theta, dn.numel(),
-            ctypes.c_void_p(dn.data_ptr()), ctypes.c_void_p(dg.data_ptr()), ctypes.c_void_p(out.data_ptr()),
-            self._stream()), "rimphony_gamma_integrand_batch_device")
+    def _seam(self, entry, kind, params, scalars, arrays, n_out=1):
+        """One call of a per-point seam, rimphony_<entry>_batch_device(ctx, kind, params, *scalars, count, *arrays,
+        *outputs, stream): the arrays to the device, n_out outputs of their length, the call, and the results back as
+        numpy arrays (one array if n_out == 1, else a tuple)."""
+        name = "rimphony_%s_batch_device" % entry
+        dev = [self._as_dev(a) for a in arrays]
+        outs = [torch.empty_like(dev[0]) for _ in range(n_out)]
+        capi.check(getattr(self.lib, name)(
+            self.handle, kind, (ctypes.c_double * len(params))(*params), *scalars, dev[0].numel(),
+            *[ctypes.c_void_p(t.data_ptr()) for t in dev + outs], self._stream()), name)
         torch.cuda.synchronize(self._dev())
-        return out.cpu().numpy()
+        res = tuple(t.cpu().numpy() for t in outs)
+        return res[0] if n_out == 1 else res
+
+    def gamma_integrand_batch(self, kind, params, coeff, stokes, s, theta, n, gamma):
+        return self._seam("gamma_integrand", kind, params, (int(coeff), int(stokes), s, theta), (n, gamma))
 
     def gamma_integral_batch(self, kind, params, coeff, stokes, negative_lobe, s, theta, n):
-        dn = self._as_dev(n)
-        out = torch.empty_like(dn)
-        par = (ctypes.c_double * len(params))(*params)
-        capi.check(self.lib.rimphony_gamma_integral_batch_device(
-            self.handle, kind, par, int(coeff), int(stokes), int(negative_lobe), s, theta, dn.numel(),
-            ctypes.c_void_p(dn.data_ptr()), ctypes.c_void_p(out.data_ptr()), self._stream()),
-            "rimphony_gamma_integral_batch_device")
-        torch.cuda.synchronize(self._dev())
-        return out.cpu().numpy()
+        return self._seam("gamma_integral", kind, params, (int(coeff), int(stokes), int(negative_lobe), s, theta), (n,))
 
     def n_integral_batch(self, kind, params, coeff, stokes, negative_lobe, s, theta, n_lo, n_hi):
         """diagnostic_symphony_n_integral over arrays of [n_lo, n_hi] ranges of one parameter point."""
-        dlo, dhi = self._as_dev(n_lo), self._as_dev(n_hi)
-        out = torch.empty_like(dlo)
-        par = (ctypes.c_double * len(params))(*params)
-        capi.check(self.lib.rimphony_n_integral_batch_device(
-            self.handle, kind, par, int(coeff), int(stokes), int(negative_lobe), s, theta, dlo.numel(),
-            ctypes.c_void_p(dlo.data_ptr()), ctypes.c_void_p(dhi.data_ptr()), ctypes.c_void_p(out.data_ptr()), self._stream()),
-            "rimphony_n_integral_batch_device")
-        torch.cuda.synchronize(self._dev())
-        return out.cpu().numpy()
+        return self._seam("n_integral", kind, params, (int(coeff), int(stokes), int(negative_lobe), s, theta), (n_lo, n_hi))
 
     def deriv_probe_batch(self, kind, params, coeff, stokes, negative_lobe, s, theta, n_start):
         """gsl::deriv_central as n_integration drives it (symphony.rs:238-240): d(gamma_integral)/dn at each n_start."""
-        dn = self._as_dev(n_start)
-        out = torch.empty_like(dn)
-        par = (ctypes.c_double * len(params))(*params)
-        capi.check(self.lib.rimphony_deriv_probe_batch_device(
-            self.handle, kind, par, int(coeff), int(stokes), int(negative_lobe), s, theta, dn.numel(),
-            ctypes.c_void_p(dn.data_ptr()), ctypes.c_void_p(out.data_ptr()), self._stream()),
-            "rimphony_deriv_probe_batch_device")
-        torch.cuda.synchronize(self._dev())
-        return out.cpu().numpy()
+        return self._seam("deriv_probe", kind, params, (int(coeff), int(stokes), int(negative_lobe), s, theta), (n_start,))
 
     def gamma_contribution_batch(self, kind, params, coeff, stokes, s, theta, gamma):
         """diagnostic_symphony_gamma_contribution over an array of gammas of one parameter point."""
-        dg = self._as_dev(gamma)
-        out = torch.empty_like(dg)
-        par = (ctypes.c_double * len(params))(*params)
-        capi.check(self.lib.rimphony_gamma_contribution_batch_device(
-            self.handle, kind, par, int(coeff), int(stokes), s, theta, dg.numel(),
-            ctypes.c_void_p(dg.data_ptr()), ctypes.c_void_p(out.data_ptr()), self._stream()),
-            "rimphony_gamma_contribution_batch_device")
-        torch.cuda.synchronize(self._dev())
-        return out.cpu().numpy()
+        return self._seam("gamma_contribution", kind, params, (int(coeff), int(stokes), s, theta), (gamma,))
 
     def calc_f_batch(self, kind, params, gamma, cos_xi, norm=None):
         """DistributionFunction::calc_f and calc_f_derivatives (lib.rs:111-146) of one distribution over arrays:
         returns (f, dfdg, dfdcx).  norm=None uses the distribution's own normalisation."""
-        dg, dc = self._as_dev(gamma), self._as_dev(cos_xi)
-        f, a, b = torch.empty_like(dg), torch.empty_like(dg), torch.empty_like(dg)
-        par = (ctypes.c_double * len(params))(*params)
-        capi.check(self.lib.rimphony_calc_f_batch_device(
-            self.handle, kind, par, float("nan") if norm is None else float(norm), dg.numel(),
-            ctypes.c_void_p(dg.data_ptr()), ctypes.c_void_p(dc.data_ptr()), ctypes.c_void_p(f.data_ptr()),
-            ctypes.c_void_p(a.data_ptr()), ctypes.c_void_p(b.data_ptr()), self._stream()),
-            "rimphony_calc_f_batch_device")
-        torch.cuda.synchronize(self._dev())
-        return f.cpu().numpy(), a.cpu().numpy(), b.cpu().numpy()
+        return self._seam("calc_f", kind, params, (float("nan") if norm is None else float(norm),), (gamma, cos_xi), n_out=3)
 
     def hey_element_batch(self, kind, params, stokes, s, theta, qr, fixed, v):
         """Heyvaerts inner integrand (h/f element, quasi-resonant if qr) of one parameter point over arrays."""
-        df, dv = self._as_dev(fixed), self._as_dev(v)
-        out = torch.empty_like(df)
-        par = (ctypes.c_double * len(params))(*params)
-        capi.check(self.lib.rimphony_hey_element_batch_device(
-            self.handle, kind, par, int(stokes), s, theta, int(qr), df.numel(), ctypes.c_void_p(df.data_ptr()),
-            ctypes.c_void_p(dv.data_ptr()), ctypes.c_void_p(out.data_ptr()), self._stream()), "rimphony_hey_element_batch_device")
-        torch.cuda.synchronize(self._dev())
-        return out.cpu().numpy()
+        return self._seam("hey_element", kind, params, (int(stokes), s, theta, int(qr)), (fixed, v))
 
     def hey_outer_batch(self, kind, params, stokes, s, theta, qr, u):
         """Heyvaerts outer integrand (one inner integral per abscissa) of one parameter point over an array."""
-        du = self._as_dev(u)
-        out = torch.empty_like(du)
-        par = (ctypes.c_double * len(params))(*params)
-        capi.check(self.lib.rimphony_hey_outer_batch_device(
-            self.handle, kind, par, int(stokes), s, theta, int(qr), du.numel(), ctypes.c_void_p(du.data_ptr()),
-            ctypes.c_void_p(out.data_ptr()), self._stream()), "rimphony_hey_outer_batch_device")
-        torch.cuda.synchronize(self._dev())
-        return out.cpu().numpy()
+        return self._seam("hey_outer", kind, params, (int(stokes), s, theta, int(qr)), (u,))
 
     def qag_selftest(self, family, p0, p1, a, b, epsabs, epsrel, limit):
         fam = torch.as_tensor(family, dtype=torch.int32).to(self._dev()).contiguous()

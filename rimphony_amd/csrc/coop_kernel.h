@@ -786,14 +786,8 @@ __global__ __launch_bounds__(64) void gamma_integral_kernel(PointArgs pa, const 
     const IStore inner = istore_carve(s_inner, CAP_INNER, spill_base + (size_t) blockIdx.x * SPILL_DOUBLES_PER_WAVE, SPILL_INNER);
     __shared__ QagPark s_qpark;
     if (threadIdx.x == 0) { s_qpark.ctr = WaveCounters{0, 0, 0}; s_qpark.hb = nullptr; }
-    SymPoint pt;
-    pt.s = pa.s;
-    rim_sincos(pa.theta, &pt.sin_th, &pt.cos_th);
-    pt.coeff = pa.coeff;
-    pt.stokes = pa.stokes;
-    DistParams d;
-    for (int k = 0; k < 5; k++) d.par[k] = pa.par[k];
-    dist_prepare<KIND>(d, norm_ptr[0]);
+    const SymPoint pt = sym_point_of(pa);
+    const DistParams d = dist_of<KIND>(pa, norm_ptr[0]);
     for (size_t i = blockIdx.x; i < count; i += gridDim.x) {
         const double n = nvals[i];
         LeungOrder ord_tmp[2];
@@ -816,14 +810,8 @@ __global__ void integrand_kernel_n(PointArgs pa, const double *norm_ptr, size_t 
 {
     const size_t i = (size_t) blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= count) return;
-    SymPoint pt;
-    pt.s = pa.s;
-    rim_sincos(pa.theta, &pt.sin_th, &pt.cos_th);
-    pt.coeff = pa.coeff;
-    pt.stokes = pa.stokes;
-    DistParams d;
-    for (int k = 0; k < 5; k++) d.par[k] = pa.par[k];
-    dist_prepare<KIND>(d, norm_ptr[0]);
+    const SymPoint pt = sym_point_of(pa);
+    const DistParams d = dist_of<KIND>(pa, norm_ptr[0]);
     LeungOrder ord[2];
     const SymOrder so = sym_order(n[i], ord);
     out[i] = gamma_integrand<KIND>(pt, d, so, gamma[i]);

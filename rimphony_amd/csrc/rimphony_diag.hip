@@ -7,6 +7,35 @@
 
 using namespace rim;
 
+// A task's state machine driven through the steps the product kernels take -- post a batch of requests, evaluate them one
+// after the other with the whole wave, consume -- for as long as it is in one of the two phases.
+template <int KIND>
+__device__ __forceinline__ void sym_drive(const SymPoint &pt, const DistParams &d, const GKLane &g, const IStore &inner,
+                                          const IStore &outer, TaskState *s_park, QagPark *s_qpark, TaskState &T, int ph_a, int ph_b)
+{
+    while (T.phase == ph_a || T.phase == ph_b) {
+        SymBatch B;
+        if (!sym_post(pt, g, outer, T, B)) break;
+        __syncthreads();
+        if (g.lane == 0) *s_park = T;
+        int batch_status = 0;
+        double gval = 0.;
+        unsigned long long mask = wv_ballot(B.req_active);
+        while (mask) {
+            const int k = __builtin_ffsll((long long) mask) - 1;
+            mask &= mask - 1;
+            const double n = readlane_d(B.req_n, k);
+            const int lb = wv_readlane(B.req_lobe, k);
+            const double val = sym_eval_request<KIND>(pt, d, g, inner, s_qpark, n, lb, batch_status);
+            if (g.lane == k) gval = val;
+        }
+        __syncthreads();
+        T = *s_park;
+        task_uniformize(T);
+        sym_consume(pt, g, outer, T, B, gval, uni(batch_status));
+    }
+}
+
 // diagnostic_symphony_n_integral (lib.rs:254-260): one outer QAG over n in [n_lo, n_hi] of the gamma-integral,
 // run through the same post / evaluate / consume steps as a chunk of n_integration.
 template <int KIND>
@@ -23,14 +52,8 @@ __global__ __launch_bounds__(64) void n_integral_kernel(PointArgs pa, const doub
     const IStore outer = istore_carve(s_outer, CAP_OUTER, spill + RIM_ISTORE_DOUBLES(SPILL_INNER), SPILL_OUTER);
     __shared__ QagPark s_qpark;
     if (threadIdx.x == 0) { s_qpark.ctr = WaveCounters{0, 0, 0}; s_qpark.hb = nullptr; }
-    SymPoint pt;
-    pt.s = pa.s;
-    rim_sincos(pa.theta, &pt.sin_th, &pt.cos_th);
-    pt.coeff = pa.coeff;
-    pt.stokes = pa.stokes;
-    DistParams d;
-    for (int k = 0; k < 5; k++) d.par[k] = pa.par[k];
-    dist_prepare<KIND>(d, norm_ptr[0]);
+    const SymPoint pt = sym_point_of(pa);
+    const DistParams d = dist_of<KIND>(pa, norm_ptr[0]);
     for (size_t i = blockIdx.x; i < count; i += gridDim.x) {
         TaskState T;
         sym_begin(pt, T);
@@ -40,27 +63,7 @@ __global__ __launch_bounds__(64) void n_integral_kernel(PointArgs pa, const doub
         T.qb = uni(n_hi[i]);
         T.ni_failed = 0;
         qag_begin(T.oq, 0., 1e-3, 1000);
-        while (T.phase == PH_QAG_FIRST || T.phase == PH_QAG_BISECT) {
-            SymBatch B;
-            if (!sym_post(pt, g, outer, T, B)) break;
-            __syncthreads();
-            if (g.lane == 0) s_park = T;
-            int batch_status = 0;
-            double gval = 0.;
-            unsigned long long mask = wv_ballot(B.req_active);
-            while (mask) {
-                const int k = __builtin_ffsll((long long) mask) - 1;
-                mask &= mask - 1;
-                const double n = readlane_d(B.req_n, k);
-                const int lb = wv_readlane(B.req_lobe, k);
-                const double val = sym_eval_request<KIND>(pt, d, g, inner, &s_qpark, n, lb, batch_status);
-                if (g.lane == k) gval = val;
-            }
-            __syncthreads();
-            T = s_park;
-            task_uniformize(T);
-            sym_consume(pt, g, outer, T, B, gval, uni(batch_status));
-        }
+        sym_drive<KIND>(pt, d, g, inner, outer, &s_park, &s_qpark, T, PH_QAG_FIRST, PH_QAG_BISECT);
         // sym_consume has run the chunk's epilogue: contrib holds the QAG value, ni_failed an Err
         if (g.lane == 0) out[i] = (T.ni_failed || (T.status & ST_OUTER_FAIL)) ? RIM_NAN : T.contrib;
     }
@@ -84,14 +87,8 @@ __global__ __launch_bounds__(64) void deriv_probe_kernel(PointArgs pa, const dou
     const IStore outer = istore_carve(s_outer, CAP_OUTER, spill + RIM_ISTORE_DOUBLES(SPILL_INNER), SPILL_OUTER);
     __shared__ QagPark s_qpark;
     if (threadIdx.x == 0) { s_qpark.ctr = WaveCounters{0, 0, 0}; s_qpark.hb = nullptr; }
-    SymPoint pt;
-    pt.s = pa.s;
-    rim_sincos(pa.theta, &pt.sin_th, &pt.cos_th);
-    pt.coeff = pa.coeff;
-    pt.stokes = pa.stokes;
-    DistParams d;
-    for (int k = 0; k < 5; k++) d.par[k] = pa.par[k];
-    dist_prepare<KIND>(d, norm_ptr[0]);
+    const SymPoint pt = sym_point_of(pa);
+    const DistParams d = dist_of<KIND>(pa, norm_ptr[0]);
     for (size_t i = blockIdx.x; i < count; i += gridDim.x) {
         TaskState T;
         sym_begin(pt, T);
@@ -99,27 +96,7 @@ __global__ __launch_bounds__(64) void deriv_probe_kernel(PointArgs pa, const dou
         T.n_start = uni(n_start[i]);
         T.dr_h = 1e-10 * T.n_start;
         T.phase = PH_DERIV1;
-        while (T.phase == PH_DERIV1 || T.phase == PH_DERIV2) {
-            SymBatch B;
-            if (!sym_post(pt, g, outer, T, B)) break;
-            __syncthreads();
-            if (g.lane == 0) s_park = T;
-            int batch_status = 0;
-            double gval = 0.;
-            unsigned long long mask = wv_ballot(B.req_active);
-            while (mask) {
-                const int k = __builtin_ffsll((long long) mask) - 1;
-                mask &= mask - 1;
-                const double n = readlane_d(B.req_n, k);
-                const int lb = wv_readlane(B.req_lobe, k);
-                const double val = sym_eval_request<KIND>(pt, d, g, inner, &s_qpark, n, lb, batch_status);
-                if (g.lane == k) gval = val;
-            }
-            __syncthreads();
-            T = s_park;
-            task_uniformize(T);
-            sym_consume(pt, g, outer, T, B, gval, uni(batch_status));
-        }
+        sym_drive<KIND>(pt, d, g, inner, outer, &s_park, &s_qpark, T, PH_DERIV1, PH_DERIV2);
         if (g.lane == 0) out[i] = T.dr_r0;
     }
 }
@@ -138,14 +115,8 @@ __global__ __launch_bounds__(64) void gamma_contribution_kernel(PointArgs pa, co
     const IStore st = istore_carve(s_store, CAP_INNER, spill_base + (size_t) blockIdx.x * SPILL_DOUBLES_PER_WAVE, SPILL_INNER);
     __shared__ QagPark s_qpark;
     if (threadIdx.x == 0) { s_qpark.ctr = WaveCounters{0, 0, 0}; s_qpark.hb = nullptr; }
-    SymPoint pt;
-    pt.s = pa.s;
-    rim_sincos(pa.theta, &pt.sin_th, &pt.cos_th);
-    pt.coeff = pa.coeff;
-    pt.stokes = pa.stokes;
-    DistParams d;
-    for (int k = 0; k < 5; k++) d.par[k] = pa.par[k];
-    dist_prepare<KIND>(d, norm_ptr[0]);
+    const SymPoint pt = sym_point_of(pa);
+    const DistParams d = dist_of<KIND>(pa, norm_ptr[0]);
     for (size_t i = blockIdx.x; i < count; i += gridDim.x) {
         const double gamma = uni(gammas[i]);
         const double delta = rim_fabs(pt.cos_th) * rim_sqrt(gamma * gamma - 1.);
@@ -197,19 +168,10 @@ extern "C" int rimphony_n_integral_batch_device(rimphony_ctx *c, int kind, const
                                                 void *stream)
 {
     if (!c || (count && (!d_n_lo || !d_n_hi || !d_out))) return RIMPHONY_EINVAL;
-    hipStream_t st = (hipStream_t) stream;
-    RimCtxScope scope(c, st);          // the context's lock + ordering behind earlier work on its workspace
-    { const int rc0 = scope.enter(); if (rc0) return rc0; }
-    PointArgs pa;
-    int rc = rim_point_setup(c, kind, params, coeff, stokes, negative_lobe, s, theta, st, pa);
-    if (rc) return rc;
-    if (count == 0) return RIMPHONY_OK;
-    unsigned grid = 0;
-    rc = rim_wave_grid(c, count, 16, &grid);
-    if (rc) return rc;
-    const double *norm = rim_ctx_norm(c);
-    double *spill = rim_ctx_spill(c);
-    rim_with_kind5(rim_ctx_dist_kind(c, kind), [&](auto K) { hipLaunchKernelGGL(n_integral_kernel<decltype(K)::value>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pa, norm, count, d_n_lo, d_n_hi, d_out, spill); });
+    RimPointSeam m;
+    const int rc = m.begin(c, kind, params, coeff, stokes, negative_lobe, s, theta, count, 16, stream);
+    if (rc || !count) return rc;
+    rim_with_kind5(m.kind, [&](auto K) { hipLaunchKernelGGL(n_integral_kernel<decltype(K)::value>, dim3(m.grid), dim3(64), RIM_DYN_LDS, m.st, m.pa, m.norm, count, d_n_lo, d_n_hi, d_out, m.spill); });
     HIP_TRY(hipGetLastError());
     return RIMPHONY_OK;
 }
@@ -219,19 +181,10 @@ extern "C" int rimphony_deriv_probe_batch_device(rimphony_ctx *c, int kind, cons
                                                  size_t count, const double *d_n_start, double *d_out, void *stream)
 {
     if (!c || (count && (!d_n_start || !d_out))) return RIMPHONY_EINVAL;
-    hipStream_t st = (hipStream_t) stream;
-    RimCtxScope scope(c, st);          // the context's lock + ordering behind earlier work on its workspace
-    { const int rc0 = scope.enter(); if (rc0) return rc0; }
-    PointArgs pa;
-    int rc = rim_point_setup(c, kind, params, coeff, stokes, negative_lobe, s, theta, st, pa);
-    if (rc) return rc;
-    if (count == 0) return RIMPHONY_OK;
-    unsigned grid = 0;
-    rc = rim_wave_grid(c, count, 16, &grid);
-    if (rc) return rc;
-    const double *norm = rim_ctx_norm(c);
-    double *spill = rim_ctx_spill(c);
-    rim_with_kind5(rim_ctx_dist_kind(c, kind), [&](auto K) { hipLaunchKernelGGL(deriv_probe_kernel<decltype(K)::value>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pa, norm, count, d_n_start, d_out, spill); });
+    RimPointSeam m;
+    const int rc = m.begin(c, kind, params, coeff, stokes, negative_lobe, s, theta, count, 16, stream);
+    if (rc || !count) return rc;
+    rim_with_kind5(m.kind, [&](auto K) { hipLaunchKernelGGL(deriv_probe_kernel<decltype(K)::value>, dim3(m.grid), dim3(64), RIM_DYN_LDS, m.st, m.pa, m.norm, count, d_n_start, d_out, m.spill); });
     HIP_TRY(hipGetLastError());
     return RIMPHONY_OK;
 }
@@ -241,19 +194,10 @@ extern "C" int rimphony_gamma_contribution_batch_device(rimphony_ctx *c, int kin
                                                         double *d_out, void *stream)
 {
     if (!c || (count && (!d_gamma || !d_out))) return RIMPHONY_EINVAL;
-    hipStream_t st = (hipStream_t) stream;
-    RimCtxScope scope(c, st);          // the context's lock + ordering behind earlier work on its workspace
-    { const int rc0 = scope.enter(); if (rc0) return rc0; }
-    PointArgs pa;
-    int rc = rim_point_setup(c, kind, params, coeff, stokes, 0, s, theta, st, pa);
-    if (rc) return rc;
-    if (count == 0) return RIMPHONY_OK;
-    unsigned grid = 0;
-    rc = rim_wave_grid(c, count, 8, &grid);
-    if (rc) return rc;
-    const double *norm = rim_ctx_norm(c);
-    double *spill = rim_ctx_spill(c);
-    rim_with_kind5(rim_ctx_dist_kind(c, kind), [&](auto K) { hipLaunchKernelGGL(gamma_contribution_kernel<decltype(K)::value>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pa, norm, count, d_gamma, d_out, spill); });
+    RimPointSeam m;
+    const int rc = m.begin(c, kind, params, coeff, stokes, 0, s, theta, count, 8, stream);
+    if (rc || !count) return rc;
+    rim_with_kind5(m.kind, [&](auto K) { hipLaunchKernelGGL(gamma_contribution_kernel<decltype(K)::value>, dim3(m.grid), dim3(64), RIM_DYN_LDS, m.st, m.pa, m.norm, count, d_gamma, d_out, m.spill); });
     HIP_TRY(hipGetLastError());
     return RIMPHONY_OK;
 }
@@ -268,9 +212,7 @@ __global__ void calc_f_kernel(PointArgs pa, const double *norm_ptr, double norm_
 {
     const size_t i = (size_t) blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= count) return;
-    DistParams d;
-    for (int k = 0; k < 5; k++) d.par[k] = pa.par[k];
-    dist_prepare<KIND>(d, rim_isnan(norm_override) ? norm_ptr[0] : norm_override);
+    const DistParams d = dist_of<KIND>(pa, rim_isnan(norm_override) ? norm_ptr[0] : norm_override);
     if (f) f[i] = calc_f<KIND>(d, gamma[i], cos_xi[i]);
     if (dfdg || dfdcx) {
         double a, b;
@@ -285,17 +227,11 @@ extern "C" int rimphony_calc_f_batch_device(rimphony_ctx *c, int kind, const dou
                                             double *d_f, double *d_dfdg, double *d_dfdcx, void *stream)
 {
     if (!c || (count && (!d_gamma || !d_cos_xi))) return RIMPHONY_EINVAL;
-    hipStream_t st = (hipStream_t) stream;
-    RimCtxScope scope(c, st);          // the context's lock + ordering behind earlier work on its workspace
-    { const int rc0 = scope.enter(); if (rc0) return rc0; }
-    PointArgs pa;
+    RimPointSeam m;
     // coefficient / stokes / s / theta play no part in f; any valid values satisfy the argument checks
-    int rc = rim_point_setup(c, kind, params, 0, 0, 0, 1., 1., st, pa);
-    if (rc) return rc;
-    if (count == 0) return RIMPHONY_OK;
-    const double *norm = rim_ctx_norm(c);
-    const dim3 grid((unsigned) ((count + 63) / 64)), block(64);
-    rim_with_kind5(rim_ctx_dist_kind(c, kind), [&](auto K) { hipLaunchKernelGGL(calc_f_kernel<decltype(K)::value>, grid, block, RIM_DYN_LDS, st, pa, norm, norm_override, count, d_gamma, d_cos_xi, d_f, d_dfdg, d_dfdcx); });
+    const int rc = m.begin(c, kind, params, 0, 0, 0, 1., 1., count, 0, stream);
+    if (rc || !count) return rc;
+    rim_with_kind5(m.kind, [&](auto K) { hipLaunchKernelGGL(calc_f_kernel<decltype(K)::value>, dim3(m.grid), dim3(64), RIM_DYN_LDS, m.st, m.pa, m.norm, norm_override, count, d_gamma, d_cos_xi, d_f, d_dfdg, d_dfdcx); });
     HIP_TRY(hipGetLastError());
     return RIMPHONY_OK;
 }
@@ -306,6 +242,10 @@ extern "C" int rimphony_calc_f_batch(rimphony_ctx *c, int kind, const double *pa
 {
     if (!c || (count && (!gamma || !cos_xi))) return RIMPHONY_EINVAL;
     if (count == 0) return rimphony_calc_f_batch_device(c, kind, params, norm_override, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+    int dev = -1;
+    const int rcd = rimphony_ctx_device(c, &dev);          // the staging buffer belongs on the context's device
+    if (rcd) return rcd;
+    HIP_TRY(hipSetDevice(dev));
     double *buf = nullptr;
     if (hipMalloc(&buf, 5 * count * sizeof(double)) != hipSuccess) return RIMPHONY_ENOMEM;
     int rc = RIMPHONY_EHIP;
@@ -331,7 +271,7 @@ extern "C" int rimphony_calc_f_batch(rimphony_ctx *c, int kind, const double *pa
 // The Faraday coefficients are compared with the oracle end to end; these two seams let a divergence be localised:
 // the element functions (one thread per (fixed, v) pair) and the outer integrands (one wave per abscissa: the inner
 // QAG of hey_eval_request).
-static __device__ HeyPoint hey_point_of(const PointArgs &pa)
+static __device__ __forceinline__ HeyPoint hey_point_of(const PointArgs &pa)
 {
     HeyPoint pt;
     pt.s = pa.s;
@@ -348,9 +288,7 @@ __global__ void hey_element_kernel(PointArgs pa, const double *norm_ptr, int qr,
     const size_t i = (size_t) blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= count) return;
     const HeyPoint pt = hey_point_of(pa);
-    DistParams d;
-    for (int k = 0; k < 5; k++) d.par[k] = pa.par[k];
-    dist_prepare<KIND>(d, norm_ptr[0]);
+    const DistParams d = dist_of<KIND>(pa, norm_ptr[0]);
     const HeyConsts hc = hey_consts();
     out[i] = hey_element<KIND>(pt, d, hc, qr != 0, fixed[i], v[i]);
 }
@@ -369,9 +307,7 @@ __global__ __launch_bounds__(64) void hey_outer_kernel(PointArgs pa, const doubl
     HeyPoint pt = hey_point_of(pa);
     pt.s = uni(pt.s); pt.sin_th = uni(pt.sin_th); pt.cos_th = uni(pt.cos_th);
     pt.sigma0 = uni(pt.sigma0); pt.sigma0_sq = uni(pt.sigma0_sq); pt.dinv = uni(pt.dinv);
-    DistParams d;
-    for (int k = 0; k < 5; k++) d.par[k] = pa.par[k];
-    dist_prepare<KIND>(d, norm_ptr[0]);
+    const DistParams d = dist_of<KIND>(pa, norm_ptr[0]);
     const HeyConsts hc = hey_consts();
     for (size_t i = blockIdx.x; i < count; i += gridDim.x) {
         int st = 0;
@@ -386,16 +322,10 @@ extern "C" int rimphony_hey_element_batch_device(rimphony_ctx *c, int kind, cons
                                                  void *stream)
 {
     if (!c || (count && (!d_fixed || !d_v || !d_out)) || (stokes != RIMPHONY_STOKES_Q && stokes != RIMPHONY_STOKES_V)) return RIMPHONY_EINVAL;
-    hipStream_t st = (hipStream_t) stream;
-    RimCtxScope scope(c, st);          // the context's lock + ordering behind earlier work on its workspace
-    { const int rc0 = scope.enter(); if (rc0) return rc0; }
-    PointArgs pa;
-    int rc = rim_point_setup(c, kind, params, 0, stokes, 0, s, theta, st, pa);
-    if (rc) return rc;
-    if (count == 0) return RIMPHONY_OK;
-    const double *norm = rim_ctx_norm(c);
-    const dim3 grid((unsigned) ((count + 63) / 64)), block(64);
-    rim_with_kind5(rim_ctx_dist_kind(c, kind), [&](auto K) { hipLaunchKernelGGL(hey_element_kernel<decltype(K)::value>, grid, block, RIM_DYN_LDS, st, pa, norm, qr, count, d_fixed, d_v, d_out); });
+    RimPointSeam m;
+    const int rc = m.begin(c, kind, params, 0, stokes, 0, s, theta, count, 0, stream);
+    if (rc || !count) return rc;
+    rim_with_kind5(m.kind, [&](auto K) { hipLaunchKernelGGL(hey_element_kernel<decltype(K)::value>, dim3(m.grid), dim3(64), RIM_DYN_LDS, m.st, m.pa, m.norm, qr, count, d_fixed, d_v, d_out); });
     HIP_TRY(hipGetLastError());
     return RIMPHONY_OK;
 }
@@ -404,18 +334,10 @@ extern "C" int rimphony_hey_outer_batch_device(rimphony_ctx *c, int kind, const 
                                                int qr, size_t count, const double *d_u, double *d_out, void *stream)
 {
     if (!c || (count && (!d_u || !d_out)) || (stokes != RIMPHONY_STOKES_Q && stokes != RIMPHONY_STOKES_V)) return RIMPHONY_EINVAL;
-    hipStream_t st = (hipStream_t) stream;
-    RimCtxScope scope(c, st);          // the context's lock + ordering behind earlier work on its workspace
-    { const int rc0 = scope.enter(); if (rc0) return rc0; }
-    PointArgs pa;
-    int rc = rim_point_setup(c, kind, params, 0, stokes, 0, s, theta, st, pa);
-    if (rc) return rc;
-    if (count == 0) return RIMPHONY_OK;
-    unsigned grid = 0;
-    rc = rim_wave_grid(c, count, 16, &grid);
-    if (rc) return rc;
-    const double *norm = rim_ctx_norm(c);
-    rim_with_kind5(rim_ctx_dist_kind(c, kind), [&](auto K) { hipLaunchKernelGGL(hey_outer_kernel<decltype(K)::value>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pa, norm, qr, count, d_u, d_out, rim_ctx_spill(c)); });
+    RimPointSeam m;
+    const int rc = m.begin(c, kind, params, 0, stokes, 0, s, theta, count, 16, stream);
+    if (rc || !count) return rc;
+    rim_with_kind5(m.kind, [&](auto K) { hipLaunchKernelGGL(hey_outer_kernel<decltype(K)::value>, dim3(m.grid), dim3(64), RIM_DYN_LDS, m.st, m.pa, m.norm, qr, count, d_u, d_out, m.spill); });
     HIP_TRY(hipGetLastError());
     return RIMPHONY_OK;
 }

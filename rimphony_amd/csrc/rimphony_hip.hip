@@ -1431,70 +1431,54 @@ static int single_point_norm(rimphony_ctx *c, int kind, const double *params, hi
     return launch_norm(c, kind, 1, pp, c->d_norm.p, st);
 }
 
+// the one entry path of the per-point seams (rimphony_internal.h)
+int RimPointSeam::begin(rimphony_ctx *c, int kind_, const double *params, int coeff, int stokes, int negative_lobe, double s,
+                        double theta, size_t count, int waves_per_cu, void *stream)
+{
+    int rc = fill_point_args(c, kind_, params, coeff, stokes, negative_lobe, s, theta, pa);
+    if (rc || count == 0) return rc;
+    st = (hipStream_t) stream;
+    scope.emplace(c, st);              // the context's lock; enter() selects c->device and orders st behind earlier work
+    rc = scope->enter();
+    if (rc) return rc;
+    rc = single_point_norm(c, kind_, params, st);
+    if (rc) return rc;
+    if (waves_per_cu) {
+        grid = persistent_grid(c, count, waves_per_cu);
+        rc = ensure_spill(c, grid);
+        if (rc) return rc;
+    } else grid = (unsigned) ((count + 63) / 64);
+    norm = c->d_norm.p;
+    spill = c->d_spill.p;
+    kind = kind_ == RIMPHONY_TABULATED ? rim_tab_seam_kind(c->tab_kind) : kind_;
+    return RIMPHONY_OK;
+}
+
 extern "C" int rimphony_gamma_integrand_batch_device(rimphony_ctx *c, int kind, const double *params,
                                                      int coeff, int stokes, double s, double theta,
                                                      size_t count, const double *d_n, const double *d_gamma,
                                                      double *d_out, void *stream)
 {
     if (!c || (count && (!d_n || !d_gamma || !d_out))) return RIMPHONY_EINVAL;
-    PointArgs pa;
-    int rc = fill_point_args(c, kind, params, coeff, stokes, 0, s, theta, pa);
-    if (rc) return rc;
-    if (count == 0) return RIMPHONY_OK;
-    hipStream_t st = (hipStream_t) stream;
-    RimCtxScope scope(c, st);
-    rc = scope.enter();
-    if (rc) return rc;
-    rc = single_point_norm(c, kind, params, st);
-    if (rc) return rc;
-    const dim3 grid((unsigned) ((count + 63) / 64)), block(64);
-    if (kind == RIMPHONY_TABULATED) rim_tab_launch_integrand(c->tab_kind, grid.x, st, pa, c->d_norm.p, count, d_n, d_gamma, d_out);
-    else rim_with_kind(kind, [&](auto K) { hipLaunchKernelGGL(integrand_kernel_n<decltype(K)::value>, grid, block, RIM_DYN_LDS, st, pa, c->d_norm.p, count, d_n, d_gamma, d_out); });
+    RimPointSeam m;
+    const int rc = m.begin(c, kind, params, coeff, stokes, 0, s, theta, count, 0, stream);
+    if (rc || !count) return rc;
+    if (kind == RIMPHONY_TABULATED) rim_tab_launch_integrand(m.kind, m.grid, m.st, m.pa, m.norm, count, d_n, d_gamma, d_out);
+    else rim_with_kind(kind, [&](auto K) { hipLaunchKernelGGL(integrand_kernel_n<decltype(K)::value>, dim3(m.grid), dim3(64), RIM_DYN_LDS, m.st, m.pa, m.norm, count, d_n, d_gamma, d_out); });
     HIP_TRY(hipGetLastError());
     return RIMPHONY_OK;
 }
-
-// helpers shared with rimphony_diag.hip (rimphony_internal.h)
-int rim_point_setup(rimphony_ctx *c, int kind, const double *params, int coeff, int stokes, int negative_lobe,
-                    double s, double theta, hipStream_t st, PointArgs &pa)
-{
-    int rc = fill_point_args(c, kind, params, coeff, stokes, negative_lobe, s, theta, pa);
-    if (rc) return rc;
-    HIP_TRY(hipSetDevice(c->device));
-    return single_point_norm(c, kind, params, st);
-}
-int rim_wave_grid(rimphony_ctx *c, size_t count, int waves_per_cu, unsigned *grid)
-{
-    *grid = persistent_grid(c, count, waves_per_cu);
-    return ensure_spill(c, *grid);
-}
-const double *rim_ctx_norm(const rimphony_ctx *c) { return c->d_norm.p; }
-int rim_ctx_dist_kind(const rimphony_ctx *c, int kind)
-{
-    return kind == RIMPHONY_TABULATED ? rim_tab_seam_kind(c->tab_kind) : kind;
-}
-double *rim_ctx_spill(const rimphony_ctx *c) { return c->d_spill.p; }
 
 extern "C" int rimphony_gamma_integral_batch_device(rimphony_ctx *c, int kind, const double *params,
                                                     int coeff, int stokes, int negative_lobe, double s, double theta,
                                                     size_t count, const double *d_n, double *d_out, void *stream)
 {
     if (!c || (count && (!d_n || !d_out))) return RIMPHONY_EINVAL;
-    PointArgs pa;
-    int rc = fill_point_args(c, kind, params, coeff, stokes, negative_lobe, s, theta, pa);
-    if (rc) return rc;
-    if (count == 0) return RIMPHONY_OK;
-    hipStream_t st = (hipStream_t) stream;
-    RimCtxScope scope(c, st);
-    rc = scope.enter();
-    if (rc) return rc;
-    rc = single_point_norm(c, kind, params, st);
-    if (rc) return rc;
-    const unsigned grid = persistent_grid(c, count, 16);
-    rc = ensure_spill(c, grid);
-    if (rc) return rc;
-    if (kind == RIMPHONY_TABULATED) rim_tab_launch_gamma_integral(c->tab_kind, grid, st, pa, c->d_norm.p, count, d_n, d_out, c->d_spill.p);
-    else rim_with_kind(kind, [&](auto K) { hipLaunchKernelGGL(gamma_integral_kernel<decltype(K)::value>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pa, c->d_norm.p, count, d_n, d_out, c->d_spill.p); });
+    RimPointSeam m;
+    const int rc = m.begin(c, kind, params, coeff, stokes, negative_lobe, s, theta, count, 16, stream);
+    if (rc || !count) return rc;
+    if (kind == RIMPHONY_TABULATED) rim_tab_launch_gamma_integral(m.kind, m.grid, m.st, m.pa, m.norm, count, d_n, d_out, m.spill);
+    else rim_with_kind(kind, [&](auto K) { hipLaunchKernelGGL(gamma_integral_kernel<decltype(K)::value>, dim3(m.grid), dim3(64), RIM_DYN_LDS, m.st, m.pa, m.norm, count, d_n, d_out, m.spill); });
     HIP_TRY(hipGetLastError());
     return RIMPHONY_OK;
 }

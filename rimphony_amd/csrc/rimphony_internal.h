@@ -7,6 +7,7 @@
 #define RIMPHONY_INTERNAL_H
 
 #include <hip/hip_runtime.h>
+#include <optional>
 #include <type_traits>
 #include "../../include/rimphony_hip.h"
 #include "symphony_wave.h"
@@ -65,12 +66,25 @@ struct PointArgs {
     double s, theta;
     int coeff, stokes, negative_lobe;
 };
+// what the seam kernels make of it: the point, and the distribution with the normalisation the host left in norm[0]
+__device__ __forceinline__ rim::SymPoint sym_point_of(const PointArgs &pa)
+{
+    rim::SymPoint pt;
+    pt.s = pa.s;
+    rim_sincos(pa.theta, &pt.sin_th, &pt.cos_th);
+    pt.coeff = pa.coeff;
+    pt.stokes = pa.stokes;
+    return pt;
+}
+template <int KIND>
+__device__ __forceinline__ rim::DistParams dist_of(const PointArgs &pa, double norm)
+{
+    rim::DistParams d;
+    for (int k = 0; k < 5; k++) d.par[k] = pa.par[k];
+    rim::dist_prepare<KIND>(d, norm);
+    return d;
+}
 
-// validate + normalise one host-described parameter point (norm -> rim_ctx_norm(c)[0]) on `st`
-int rim_point_setup(rimphony_ctx *c, int kind, const double *params, int coeff, int stokes, int negative_lobe,
-                    double s, double theta, hipStream_t st, PointArgs &pa);
-// persistent grid of single-wave workgroups for `count` work items + its per-wave spill region
-int rim_wave_grid(rimphony_ctx *c, size_t count, int waves_per_cu, unsigned *grid);
 // Every entry point that touches the context's workspace (norms, spill regions, staging buffers, queue words) runs
 // inside one of these: the context's (recursive) host lock for the whole call -- staging, launches, synchronisation and
 // copy-out included --, the device selected, `st` ordered behind the previous call's work on the workspace, and that
@@ -91,11 +105,25 @@ struct RimCtxScope {
     RimCtxScope(const RimCtxScope &) = delete;
     RimCtxScope &operator=(const RimCtxScope &) = delete;
 };
-const double *rim_ctx_norm(const rimphony_ctx *c);
-// the distribution kind whose instantiation serves `kind` on this context: for RIMPHONY_TABULATED the form of the installed
-// table set as rim_tab_seam_kind reads it, `kind` itself otherwise
-int rim_ctx_dist_kind(const rimphony_ctx *c, int kind);
-double *rim_ctx_spill(const rimphony_ctx *c);
+
+// The one way into the eight per-point seams (one host-described parameter point, arrays of abscissae).  begin(), in this
+// order: the point validated on the host (kind, params, coeff and stokes ranges, a table set for the tabulated kind) before
+// any lock or HIP call; count == 0 is RIMPHONY_OK with nothing enqueued; then the scope (lock, device, ordering), the
+// point's normalisation into norm[0], and the grid: waves_per_cu == 0 is one thread per item in blocks of 64, anything else a
+// persistent grid of single-wave workgroups with its region of `spill`.  `kind` is the instantiation that serves the
+// point: the form of the installed table set as rim_tab_seam_kind reads it for RIMPHONY_TABULATED, the kind itself
+// otherwise.  The entry then launches on `st` and asks hipGetLastError(); the scope ends with the object.
+struct RimPointSeam {
+    std::optional<RimCtxScope> scope;
+    PointArgs pa;
+    hipStream_t st;
+    unsigned grid;
+    const double *norm;
+    double *spill;
+    int kind;
+    int begin(rimphony_ctx *c, int kind, const double *params, int coeff, int stokes, int negative_lobe, double s, double theta,
+              size_t count, int waves_per_cu, void *stream);
+};
 
 // The one place where a run-time distribution kind picks a template instantiation: f(std::integral_constant<int, K>{}).
 // Every entry has validated `kind` before, so anything else is kind 3 (the tabulated distribution never gets here:
@@ -132,7 +160,7 @@ auto rim_with_tab_kind(int tab_kind, F &&f)
 // same bits.  This is the one place that says so.
 constexpr int rim_tab_seam_kind(int tab_kind) { return tab_kind == rim::DIST_TABULATED_ISO ? (int) rim::DIST_TABULATED : tab_kind; }
 
-// rim_with_kind for the translation units whose kernels serve all kinds (rim_ctx_dist_kind supplies `kind`).
+// rim_with_kind for the translation units whose kernels serve all kinds (RimPointSeam::kind supplies `kind`).
 // rimphony_group.hip keeps the four-way form: its kernels exist for the four analytic kinds only; the tabulated kind's
 // group kernels are reached through tab_launch.h (rim_tab_group_kernel).
 template <class F>
