@@ -266,6 +266,34 @@ int rimphony_ctx_set_tables_pitchy(rimphony_ctx *ctx, size_t n_tables, size_t n_
 int rimphony_ctx_set_tables_grid(rimphony_ctx *ctx, size_t n_tables, size_t n_nodes, const double *gamma, const double *log_n,
                                  size_t n_mu, const double *log_g, const double *sin_k);
 
+/* Tabulated distributions as 2-D surfaces on gamma nodes of the caller's choosing: what rimphony_ctx_set_tables_2d holds -- an
+ * anisotropy that grows with energy, a beam on an isotropic core, a loss cone above some gamma -- on the nodes
+ * rimphony_ctx_set_tables_grid takes, for a cold or mildly relativistic core under an anisotropic tail (a PIC or Fokker-Planck
+ * histogram), which a grid uniform in ln gamma cannot resolve within the 2-D form's node limit.
+ * f(gamma, mu) = norm exp(S(ln gamma, mu)) / (gamma^2 beta) inside [gamma[0], gamma[n_nodes - 1]], +0 outside;
+ * df/dgamma = f (S_u / gamma - 1 / gamma - gamma / (gamma^2 - 1)), df/dmu = f S_mu; the normalisation as for the 2-D form.
+ *   gamma   HOST, [n_nodes], 8 <= n_nodes <= 65536: the nodes, shared by the tables of the set, exactly as for
+ *           rimphony_ctx_set_tables_grid: finite, 1 <= gamma[0] < gamma[1] < ..., their logarithms as the library forms them
+ *           strictly increasing too;
+ *   log_n   HOST, [n_tables][n_nodes][n_mu], mu fastest: ln n at (gamma_i, mu_j), the mu nodes uniform from -1 to +1, end
+ *           points included; 8 <= n_mu <= 1024, n_nodes n_mu <= 2^20, every value finite.
+ * Anything else is RIMPHONY_EINVAL, checked on the host, and the previous set stays; so it does when a device allocation
+ * fails (RIMPHONY_ENOMEM).  n_tables = 0 clears the set.  The call replaces a set of any form and a set of any form replaces it.
+ * S is the tensor-product natural cubic spline through the data at (u_i = ln gamma_i, mu_j), solved on the host on the
+ * non-uniform u nodes, evaluated as a bicubic on the cell with the cell's own width.  A surface bilinear in (ln gamma, mu)
+ * comes back as itself; on nodes uniform in ln gamma the form gives what rimphony_ctx_set_tables_2d gives, and a sum
+ * y(gamma_i) + G(mu_j) what rimphony_ctx_set_tables_grid makes of (y, G), each in other arithmetic (agreement to rounding, not
+ * to the bit).  A sample finds its interval in u as for rimphony_ctx_set_tables_grid -- the last node at or below it, through
+ * two guide words and a bisection of at most 16 node words -- and its mu cell as for the 2-D form: a mu a rounding beyond +-1
+ * extrapolates the end cell, a NaN gives NaN.
+ * The normalisation of each table is integrated once, on the device, when the set is installed, as for the 2-D form; a table
+ * whose quadrature fails has a NaN normalisation and its rows are NaN with RIMPHONY_ST_NORM_FAIL, the other tables are
+ * unaffected.  A row is still RIMPHONY_TABULATED with one parameter, the table index.  Everything else -- a bad index, the
+ * precisions and closed forms refused, the _multi entries, RIMPHONY_TAB_GROUP (this form follows the 2-D form's default) -- is
+ * as for rimphony_ctx_set_tables_2d.  Not offered: mu nodes of the caller's choosing, a grid per table, a sin^k prefactor. */
+int rimphony_ctx_set_tables_2d_grid(rimphony_ctx *ctx, size_t n_tables, size_t n_nodes, const double *gamma, size_t n_mu,
+                                    const double *log_n);
+
 /* Work counters of the most recent batch call on this context (device-side
  * counts, read back synchronously): integrand samples, wave-wide evaluation
  * passes, inner QAG calls. */

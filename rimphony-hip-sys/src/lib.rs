@@ -135,6 +135,14 @@ extern "C" {
         n_mu: usize,
         log_n: *const c_double,
     ) -> c_int;
+    pub fn rimphony_ctx_set_tables_2d_grid(
+        ctx: *mut rimphony_ctx,
+        n_tables: usize,
+        n_nodes: usize,
+        gamma: *const c_double,
+        n_mu: usize,
+        log_n: *const c_double,
+    ) -> c_int;
 
     pub fn rimphony_last_work(ctx: *mut rimphony_ctx, out: *mut rimphony_work) -> c_int;
     pub fn rimphony_last_tail(ctx: *mut rimphony_ctx, out: *mut u64) -> c_int;
@@ -337,6 +345,25 @@ impl HipContext {
         let rc = unsafe {
             rimphony_ctx_set_tables_2d(
                 self.raw, log_n.len() / (n_nodes * n_mu), n_nodes, gamma_lo, gamma_hi, n_mu, log_n.as_ptr(),
+            )
+        };
+        if rc != RIMPHONY_OK {
+            return Err(error_text(rc));
+        }
+        Ok(())
+    }
+
+    /// A 2-D table set on gamma nodes of the caller's choosing: `gamma` holds the strictly increasing nodes, shared by the
+    /// n_tables surfaces of gamma.len() x n_mu values in `log_n`, mu fastest and uniform from -1 to +1
+    /// (include/rimphony_hip.h: rimphony_ctx_set_tables_2d_grid).
+    pub fn set_tables_2d_grid(&self, gamma: &[f64], n_mu: usize, log_n: &[f64]) -> Result<(), String> {
+        let n_nodes = gamma.len();
+        if n_nodes == 0 || n_mu == 0 || log_n.len() % (n_nodes * n_mu) != 0 {
+            return Err(error_text(RIMPHONY_EINVAL));
+        }
+        let rc = unsafe {
+            rimphony_ctx_set_tables_2d_grid(
+                self.raw, log_n.len() / (n_nodes * n_mu), n_nodes, gamma.as_ptr(), n_mu, log_n.as_ptr(),
             )
         };
         if rc != RIMPHONY_OK {

@@ -71,6 +71,7 @@ def build_hip(force=False, verbose=False):
                                     os.path.join(CSRC, "rimphony_group.hip"), os.path.join(CSRC, "rimphony_multi.hip"),
                                     os.path.join(CSRC, "rimphony_tab.hip"), os.path.join(CSRC, "rimphony_tab_group.hip"),
                                     os.path.join(CSRC, "rimphony_tab_grid_group.hip"),
+                                    os.path.join(CSRC, "rimphony_tab_2d_grid.hip"), os.path.join(CSRC, "rimphony_tab_2d_grid_group.hip"),
                                     "-ldl", "-o", LIB]
     if verbose:
         print(" ".join(cmd))
@@ -168,3 +169,8 @@ def build_pitchy_beam_oracle():
 def build_tab_grid_oracle():
     """The same for table sets on given gamma nodes (tests/support/tab_grid_oracle.cpp)."""
     return _build_dist_oracle("tab_grid_oracle.cpp", "liboracle_tabgrid.so")
+
+
+def build_tab2d_grid_oracle():
+    """The same for 2-D table sets on given gamma nodes (tests/support/tab2d_grid_oracle.cpp)."""
+    return _build_dist_oracle("tab2d_grid_oracle.cpp", "liboracle_tab2dgrid.so")

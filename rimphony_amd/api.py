@@ -182,6 +182,21 @@ def check_tables_2d(gamma_lo, gamma_hi, log_n):
     return t
 
 
+def check_tables_2d_grid(gamma, log_n):
+    """A 2-D table set on given nodes as rimphony_ctx_set_tables_2d_grid accepts it -> (gamma, log_n), contiguous float64
+    [n_nodes] and [n_tables][n_nodes][n_mu] (a 2-D array is one table); ValueError for what the library refuses with
+    RIMPHONY_EINVAL (the library itself judges whether the nodes' logarithms increase)."""
+    g = np.ascontiguousarray(np.asarray(gamma, dtype=np.float64))
+    if g.ndim != 1 or not TAB_MIN_NODES <= g.shape[0] <= TAB_MAX_NODES:
+        raise ValueError("gamma: expected %d to %d nodes, got shape %r" % (TAB_MIN_NODES, TAB_MAX_NODES, g.shape))
+    if not np.isfinite(g).all() or not g[0] >= 1.0 or not (np.diff(g) > 0.0).all():
+        raise ValueError("gamma: the nodes must be finite and strictly increasing from gamma[0] >= 1")
+    t = check_tables_2d(float(g[0]), float(g[-1]), log_n)
+    if t.shape[1] != g.shape[0]:
+        raise ValueError("log_n: expected %d rows of mu nodes per table, one per gamma node, got %d" % (g.shape[0], t.shape[1]))
+    return g, t
+
+
 class Context:
     """Owns a rimphony_ctx bound to one GPU."""
 
@@ -282,6 +297,21 @@ class Context:
         capi.check(self.lib.rimphony_ctx_set_tables_2d(self.handle, t.shape[0], t.shape[1], float(gamma_lo), float(gamma_hi),
                                                        t.shape[2], t.ctypes.data_as(ctypes.POINTER(ctypes.c_double))),
                    "rimphony_ctx_set_tables_2d")
+
+    def set_tables_2d_grid(self, gamma, log_n):
+        """The context's table set as surfaces on gamma nodes of the caller's choosing: gamma [n_nodes] strictly increasing
+        from >= 1, shared by the tables; log_n [n_tables][n_nodes][n_mu] (a 2-D array is one table) = ln n(gamma_i, mu_j),
+        the mu nodes uniform from -1 to +1.  What set_tables_2d holds, on the nodes set_tables_grid takes: a cold core under
+        an anisotropic tail.  Replaces the previous set of any form; log_n None clears it.  Synchronous: the normalisation of
+        every table is integrated here, once (include/rimphony_hip.h: rimphony_ctx_set_tables_2d_grid)."""
+        if log_n is None:
+            capi.check(self.lib.rimphony_ctx_set_tables_2d_grid(self.handle, 0, 0, None, 0, None), "rimphony_ctx_set_tables_2d_grid")
+            return
+        g, t = check_tables_2d_grid(gamma, log_n)
+        dp = ctypes.POINTER(ctypes.c_double)
+        capi.check(self.lib.rimphony_ctx_set_tables_2d_grid(self.handle, t.shape[0], t.shape[1], g.ctypes.data_as(dp), t.shape[2],
+                                                            t.ctypes.data_as(dp)),
+                   "rimphony_ctx_set_tables_2d_grid")
 
     # -- batched compute() -------------------------------------------------------
     def _check_input(self, name, t, n):
@@ -864,6 +894,33 @@ class TabulatedDistributionGrid(TabulatedDistribution):
 
     def _install(self, ctx):
         ctx.set_tables_grid(self.gamma, self.log_n, self.log_g, self.sin_k)
+        return ctx
+
+
+class TabulatedDistribution2DGrid(TabulatedDistribution):
+    """A distribution given as a surface on gamma nodes of its own: log_n [n_nodes][n_mu] = ln n(gamma_i, mu_j) at the
+    strictly increasing gamma [n_nodes] and at mu nodes uniform from -1 to +1 (Context.set_tables_2d_grid);
+    f = norm exp(S(ln gamma, mu)) / (gamma^2 beta) between the end nodes, 0 outside, S the tensor-product natural cubic
+    spline on the given nodes.  Installs its table whenever it computes, as TabulatedDistribution does."""
+
+    def __init__(self, gamma, log_n):
+        log_n = np.asarray(log_n, dtype=np.float64)
+        if log_n.ndim != 2:
+            raise ValueError("log_n: expected one table, [n_nodes][n_mu]")
+        self.gamma, self.log_n = check_tables_2d_grid(gamma, log_n)
+        self.gamma_lo, self.gamma_hi = float(self.gamma[0]), float(self.gamma[-1])
+
+    @classmethod
+    def from_function(cls, fn, gamma, n_mu=65):
+        """Tabulate n(gamma, mu) = fn(gamma[:, None], mu[None, :]) (vectorised, positive) at the given gamma nodes and
+        n_mu nodes uniform in mu from -1 to +1."""
+        gamma = np.asarray(gamma, dtype=np.float64)
+        mu = np.linspace(-1.0, 1.0, int(n_mu))
+        n = np.broadcast_to(np.asarray(fn(gamma[:, None], mu[None, :]), dtype=np.float64), (gamma.shape[0], int(n_mu)))
+        return cls(gamma, np.log(n))
+
+    def _install(self, ctx):
+        ctx.set_tables_2d_grid(self.gamma, self.log_n)
         return ctx
 
 

@@ -31,11 +31,14 @@ enum { DIST_POWER_LAW = 0, DIST_THERMAL_JUETTNER = 1, DIST_PITCHY_PL = 2, DIST_P
        DIST_TABULATED_PITCHY = 7,
        // nor this one: the tabulated kind where the gamma nodes of the set are given, not uniform in ln gamma
        // (rim_tab_build_grid); it carries a sin^k prefactor and a pitch row as DIST_TABULATED_PITCHY does.
-       DIST_TABULATED_GRID = 8 };
+       DIST_TABULATED_GRID = 8,
+       // nor this one: the tabulated kind where the set is a 2-D one on given gamma nodes (rim_tab_build_2d_grid): the surface
+       // of DIST_TABULATED_2D, the lookup of DIST_TABULATED_GRID.
+       DIST_TABULATED_2D_GRID = 9 };
 constexpr bool dist_is_tab(int kind)
 {
     return kind == DIST_TABULATED || kind == DIST_TABULATED_ISO || kind == DIST_TABULATED_2D || kind == DIST_TABULATED_PITCHY ||
-        kind == DIST_TABULATED_GRID;
+        kind == DIST_TABULATED_GRID || kind == DIST_TABULATED_2D_GRID;
 }
 enum { STOKES_I = 0, STOKES_Q = 1, STOKES_V = 2 };
 enum { COEFF_EMISSION = 0, COEFF_ABSORPTION = 1, COEFF_FARADAY = 2 };
@@ -100,6 +103,20 @@ RIM_DEV long long tab_grid_cell(double u, double u0, double inv_cell, double las
     return (long long) xc;
 }
 
+// A 2-D set on given gamma nodes (rim_tab_build_2d_grid): the header of a set on given nodes -- TAB_HDR_ULO = u_0, TAB_HDR_INVH
+// = 1 / (the width of a guide cell), TAB_HDR_H = G, the number of guide cells -- with TAB_HDR_NMU = -n_mu as a 2-D set has it.
+// Then, where a 2-D set has them, n_tables table headers of TAB_2D_HDR words (the mu geometry and the table's normalisation
+// in TAB_2D_NORM: tab2d_row_norm_kernel reads either form).  Then the guide of a set on given nodes, G + 1 32-bit words padded
+// to a multiple of 64 bytes, and straight behind it the u nodes of the set, [n_nodes][2] = {u_i, 1 / h_i} (h_i = u_{i+1} - u_i;
+// 0 at the last node), padded likewise (tab_2d_grid_unode_doubles): a row carries the address of the guide and that of the u
+// nodes, whose first word is u_0.  Then [n_tables][n_nodes][n_mu][4] = {S, S_u, S_mu, S_umu}, mu fastest, as in a 2-D set.
+RIM_DEV size_t tab_2d_grid_unode_doubles(size_t n_nodes) { return (2 * n_nodes + 7) & ~(size_t) 7; }
+RIM_DEV size_t tab_2d_grid_guide_at(size_t n_tables) { return (size_t) TAB_HDR_DOUBLES + n_tables * TAB_2D_HDR; }
+RIM_DEV size_t tab_2d_grid_nodes_at(size_t n_tables, size_t n_nodes, size_t cells)
+{
+    return tab_2d_grid_guide_at(n_tables) + tab_grid_guide_doubles(cells) + tab_2d_grid_unode_doubles(n_nodes);
+}
+
 // is `idx` (par[0] of a row) the index of a table of the set?
 RIM_DEV bool tab_row_ok(const double *hdr, double idx)
 {
@@ -130,6 +147,23 @@ RIM_DEV void dist_prepare(DistParams &d, double norm)
             d.par[3] = hdr[TAB_HDR_INVH];
             d.par[4] = hdr[TAB_HDR_NNODES] - 2.;        // the index of the last interval in u
             d.inv_gamma_cutoff = hdr[TAB_HDR_H];
+            d.inv_kappa_width = hdr[TAB_HDR_GLO];
+            d.neg_inverse_t = hdr[TAB_HDR_GHI];
+            d.norm = ok ? norm : RIM_NAN;
+            return;
+        }
+        if (KIND == DIST_TABULATED_2D_GRID) {
+            // a 2-D set on given nodes: par[0] the table's header and par[1] its node data, as for a 2-D set; par[2] the
+            // address of the set's u nodes (u_0 is their first word), par[3] 1 / (cell width), par[4] the index of the last
+            // guide cell; inv_gamma_cutoff the bit pattern of the guide's address, as for a set on given nodes
+            const size_t nt = (size_t) hdr[TAB_HDR_NTABLES], cells = (size_t) hdr[TAB_HDR_H], nmu9 = (size_t) -hdr[TAB_HDR_NMU];
+            const double *guide = hdr + tab_2d_grid_guide_at(nt);
+            d.par[0] = rim_frombits((uint64_t) (uintptr_t) (hdr + TAB_HDR_DOUBLES + row * TAB_2D_HDR));
+            d.par[1] = rim_frombits((uint64_t) (uintptr_t) (hdr + tab_2d_grid_nodes_at(nt, nn, cells) + row * nn * nmu9 * 4));
+            d.par[2] = rim_frombits((uint64_t) (uintptr_t) (guide + tab_grid_guide_doubles(cells)));
+            d.par[3] = hdr[TAB_HDR_INVH];
+            d.par[4] = hdr[TAB_HDR_H] - 1.;
+            d.inv_gamma_cutoff = rim_frombits((uint64_t) (uintptr_t) guide);
             d.inv_kappa_width = hdr[TAB_HDR_GLO];
             d.neg_inverse_t = hdr[TAB_HDR_GHI];
             d.norm = ok ? norm : RIM_NAN;
@@ -240,6 +274,7 @@ RIM_DEV bool tab_kind_has_pitch(const DistParams &d)
     // (a 2-D table and one with a sin^k prefactor always have a live d f / d mu: they take the general forms, as a pitch
     // row does)
     return KIND == DIST_TABULATED_2D || KIND == DIST_TABULATED_PITCHY || KIND == DIST_TABULATED_GRID ||
+        KIND == DIST_TABULATED_2D_GRID ||
         (KIND != DIST_TABULATED_ISO && tab_has_pitch(d));
 }
 
@@ -365,8 +400,63 @@ RIM_DEV void tab_bicubic(const DistParams &d, double gamma, double mu, double &s
     dsdmu = dsdtm * minvh;
 }
 
+// The interval of u in a 2-D set on given nodes (d: dist_prepare<DIST_TABULATED_2D_GRID>'s): tab_grid_interval on the set's
+// u nodes, two words apart.  The largest i <= n_nodes - 2 with u_i <= u, 0 where there is none or u is a NaN; the data alone
+// define it.  Reads: the two guide words, then at most 16 node words.
+RIM_DEV long long tab_2d_grid_interval(const DistParams &d, double u)
+{
+    const double *un = (const double *) (uintptr_t) rim_bits(d.par[2]);
+    const unsigned *guide = (const unsigned *) (uintptr_t) rim_bits(d.inv_gamma_cutoff);
+    const long long c = tab_grid_cell(u, un[0], d.par[3], d.par[4]);
+    long long lo = (long long) guide[c], hi = (long long) guide[c + 1];
+    while (lo < hi) {
+        const long long mid = (lo + hi + 1) >> 1;
+        if (un[2 * mid] <= u) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+
+// tab_bicubic for a 2-D set on given nodes: the same bicubic on the cell found by tab_2d_grid_interval, with the cell's own
+// h_i = u_{i+1} - u_i, formed from the two node words as the host formed it, and its 1 / h_i in the two Hermite steps along u
+// and in dS/du; t_u = (u - u_i) (1 / h_i).  The mu index from a clamped copy; a NaN gives NaN from cell 0; every read stays
+// inside the set.  Only rim_log, explicit rim_fma and + - * /.
+RIM_DEV void tab_bicubic_grid(const DistParams &d, double gamma, double mu, double &sval, double &dsdu, double &dsdmu)
+{
+    const double *th = (const double *) (uintptr_t) rim_bits(d.par[0]);
+    const double *nodes = (const double *) (uintptr_t) rim_bits(d.par[1]);
+    const double *un = (const double *) (uintptr_t) rim_bits(d.par[2]);
+    const double mlast = th[TAB_2D_LAST], minvh = th[TAB_2D_INVH], mh = th[TAB_2D_H];
+    const double u = rim_log(gamma);
+    const long long i = tab_2d_grid_interval(d, u);
+    const double *q = un + 2 * i;
+    const double uinvh = q[1], uh = q[2] - q[0];
+    const double tu = (u - q[0]) * uinvh;
+    const double z = (mu + 1.) * minvh;
+    double zc = z;
+    if (!(zc >= 0.)) zc = 0.;
+    if (zc > mlast) zc = mlast;
+    const long long j = (long long) zc;
+    const double tm = z - (double) j;
+    const long long nmu = (long long) mlast + 2;
+    const double *a = nodes + (i * nmu + j) * 4;        // nodes (i, j), (i, j + 1)
+    const double *b = a + nmu * 4;                      // nodes (i + 1, j), (i + 1, j + 1)
+    double va, dva, wa, dwa, vb, dvb, wb, dwb;
+    tab_hermite4(a[0], a[2], a[4], a[6], mh, tm, va, dva);
+    tab_hermite4(a[1], a[3], a[5], a[7], mh, tm, wa, dwa);
+    tab_hermite4(b[0], b[2], b[4], b[6], mh, tm, vb, dvb);
+    tab_hermite4(b[1], b[3], b[5], b[7], mh, tm, wb, dwb);
+    double dsdtu, dsdtm, unused;
+    tab_hermite4(va, wa, vb, wb, uh, tu, sval, dsdtu);
+    tab_hermite4(dva, dwa, dvb, dwb, uh, tu, dsdtm, unused);
+    dsdu = dsdtu * uinvh;
+    dsdmu = dsdtm * minvh;
+}
+
 // nbar(gamma) = 1/2 int exp(S(ln gamma, mu)) dmu of a 2-D table: the integrand of its normalisation.  The 31-point Kronrod
-// rule (xgk, wgk: gk31_table.h) on every mu cell, summed in node order -- the rule P of a pitch row uses.
+// rule (xgk, wgk: gk31_table.h) on every mu cell, summed in node order -- the rule P of a pitch row uses.  KIND: the form
+// of the set, DIST_TABULATED_2D or DIST_TABULATED_2D_GRID.
+template <int KIND = DIST_TABULATED_2D>
 RIM_DEV double tab_2d_norm_integrand(const DistParams &d, double g, const double *xgk, const double *wgk)
 {
     const double *th = (const double *) (uintptr_t) rim_bits(d.par[0]);
@@ -378,7 +468,8 @@ RIM_DEV double tab_2d_norm_integrand(const DistParams &d, double g, const double
         double acc = 0.;
         for (int k = 0; k < 31; k++) {
             double sval, dsdu, dsdmu;
-            tab_bicubic(d, g, centre + half * xgk[k], sval, dsdu, dsdmu);
+            if (KIND == DIST_TABULATED_2D_GRID) tab_bicubic_grid(d, g, centre + half * xgk[k], sval, dsdu, dsdmu);
+            else tab_bicubic(d, g, centre + half * xgk[k], sval, dsdu, dsdmu);
             acc += wgk[k] * rim_exp(sval);
         }
         sum += half * acc;
@@ -394,10 +485,11 @@ RIM_DEV void tab_calc_f_both(const DistParams &d, double gamma, double cos_xi, d
 {
     f = 0.; dfdg = 0.; dfdcx = 0.;
     if (gamma < d.inv_kappa_width || gamma > d.neg_inverse_t) return;
-    if (KIND == DIST_TABULATED_2D) {
+    if (KIND == DIST_TABULATED_2D || KIND == DIST_TABULATED_2D_GRID) {
         // f = norm exp(S(ln gamma, mu)) / (gamma^2 beta), d f / d mu = f S_mu: one exponential per sample
         double sval, dsdu, dsdmu;
-        tab_bicubic(d, gamma, cos_xi, sval, dsdu, dsdmu);
+        if (KIND == DIST_TABULATED_2D_GRID) tab_bicubic_grid(d, gamma, cos_xi, sval, dsdu, dsdmu);
+        else tab_bicubic(d, gamma, cos_xi, sval, dsdu, dsdmu);
         const double beta2 = rim_sqrt(1. - rim_div_moderate(1., gamma * gamma));
         f = d.norm * rim_exp(sval) / (gamma * gamma * beta2);
         dfdg = f * (dsdu / gamma - 1. / gamma - gamma / (gamma * gamma - 1.));

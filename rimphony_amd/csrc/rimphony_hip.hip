@@ -334,9 +334,9 @@ struct rimphony_ctx {
     unsigned long long hb_task;
     // what hipOccupancyMaxActiveBlocksPerMultiprocessor answered (-1: the query failed), asked once per context
     // (= per device) and instantiation: coop_kernel<P> by problem (0 Symphony, 1 Heyvaerts) and distribution kind,
-    int resident[2][9];             // (kind 4 five times: the cell of a table set is its DIST_TABULATED* value, tab_kind below)
+    int resident[2][10];            // (kind 4 six times: the cell of a table set is its DIST_TABULATED* value, tab_kind below)
     int resident_f32[4];            // ... the Symphony kernels' fp32-integrand variants,
-    int resident_group[2][9];       // ... group_kernel<P> [Symphony groups / Faraday pair][kind] (kind 4: the cells of `resident`; no Faraday pair)
+    int resident_group[2][10];      // ... group_kernel<P> [Symphony groups / Faraday pair][kind] (kind 4: the cells of `resident`; no Faraday pair)
     // 0: this context has the GPU to itself (it holds the device's lock file); 1: another context or process had
     // the device first -- smaller persistent grids, no cooperative tail (see rimphony_ctx_create)
     int shared_mode;
@@ -607,7 +607,7 @@ static int install_tables(rimphony_ctx *c, const std::vector<double> &blob, int 
     return RIMPHONY_OK;
 }
 
-// The five entries: check, build, install; n_tables = 0 clears through any of them.  A set of energy tables, each with a
+// The six entries: check, build, install; n_tables = 0 clears through any of them.  A set of energy tables, each with a
 // pitch row (log_g) or none with one (log_g null and n_mu = 0: the isotropic form).
 extern "C" int rimphony_ctx_set_tables_pitch(rimphony_ctx *c, size_t n_tables, size_t n_nodes, double gamma_lo, double gamma_hi,
                                              const double *log_n, size_t n_mu, const double *log_g)
@@ -675,6 +675,22 @@ extern "C" int rimphony_ctx_set_tables_grid(rimphony_ctx *c, size_t n_tables, si
     }
     return install_tables(c, blob, DIST_TABULATED_GRID, log_g ? rim_tab_launch_pitchy_p : nullptr,
                           n_tables ? tab_grid_tail(n_tables, n_nodes, (size_t) blob[TAB_HDR_H]) : 0);
+}
+
+// A 2-D set on gamma nodes of its own: the 2-D form's surface on the given-nodes form's lookup (tab_spline.h:
+// rim_tab_build_2d_grid).  The normalisation of each table is integrated once, as the set comes in (rimphony_tab_2d_grid.hip),
+// into the word of the table's header where the rows of a batch read it.
+extern "C" int rimphony_ctx_set_tables_2d_grid(rimphony_ctx *c, size_t n_tables, size_t n_nodes, const double *gamma, size_t n_mu,
+                                               const double *log_n)
+{
+    if (!c) return RIMPHONY_EINVAL;
+    std::vector<double> blob;
+    if (n_tables) {
+        if (rim_tab_check_2d_grid(n_tables, n_nodes, gamma, n_mu, log_n)) return RIMPHONY_EINVAL;
+        try { rim_tab_build_2d_grid(n_tables, n_nodes, gamma, n_mu, log_n, blob); }
+        catch (const std::bad_alloc &) { return RIMPHONY_ENOMEM; }
+    }
+    return install_tables(c, blob, DIST_TABULATED_2D_GRID, rim_tab_2d_grid_launch_table_norms);
 }
 
 static int rim_precision_check(const rimphony_ctx *c, int kind, int precision);
@@ -903,10 +919,10 @@ static int launch_group(rimphony_ctx *c, int kind, const SymArgs &a, uint32_t co
     });
 }
 
-// Where the Symphony slots of the tabulated distribution run when RIMPHONY_TAB_GROUP does not say: on the group kernel
-// (rimphony_tab_group.hip, rimphony_tab_grid_group.hip) or one wave per coefficient (rimphony_tab.hip), per form of the
-// installed set.  NOT MEASURED yet: every form says "group" until the file its line names has figures --
-// profiles/tabulated_group_times.txt for the first four, profiles/tabulated_grid_times.txt for a set on given gamma nodes.
+// Where the Symphony slots of the tabulated distribution run when RIMPHONY_TAB_GROUP does not say: on the group kernel or
+// one wave per coefficient, per form of the installed set; a 2-D set on given nodes (DIST_TABULATED_2D_GRID) has no line of
+// its own and takes the 2-D form's.  NOT MEASURED yet: every form says "group" until the file its line names has figures --
+// profiles/tabulated_group_times.txt, profiles/tabulated_grid_times.txt for a set on given gamma nodes.
 static const bool RIM_TAB_GROUP_DEFAULT[5] = {      // [tab_kind - DIST_TABULATED]
     true,       // DIST_TABULATED, pitch rows   NOT MEASURED (profiles/tabulated_group_times.txt)
     true,       // DIST_TABULATED_ISO           NOT MEASURED (profiles/tabulated_group_times.txt)
@@ -917,7 +933,8 @@ static const bool RIM_TAB_GROUP_DEFAULT[5] = {      // [tab_kind - DIST_TABULATE
 static bool rim_tab_runs_group(const rimphony_ctx *c)
 {
     if (c->knobs.tab_group >= 0) return c->knobs.tab_group != 0;
-    return RIM_TAB_GROUP_DEFAULT[c->tab_kind - DIST_TABULATED];
+    const int form = c->tab_kind == DIST_TABULATED_2D_GRID ? (int) DIST_TABULATED_2D : c->tab_kind;
+    return RIM_TAB_GROUP_DEFAULT[form - DIST_TABULATED];
 }
 
 // `precision` of the batch entries.  F64 is the product.  F32_INTEGRAND (BASELINE configs[4]'s fp32-core integrand) is

@@ -16,6 +16,9 @@
 // installed (tab_pitchy_table_p_kernel): the integrand's derivative is singular at both ends for a non-integer k.
 // A set on given gamma nodes runs a fifth (DIST_TABULATED_GRID): the sin^k family with tab_spline_grid for the energy
 // table -- two guide words, a short bisection over the nodes' u_j, then the 64 bytes of the interval's two nodes.
+// A 2-D set on given gamma nodes (DIST_TABULATED_2D_GRID) has its kernels in a unit of its own, rimphony_tab_2d_grid.hip, for the
+// reason the group kernels have theirs; the dispatches here hand the form on.  Its rows read their normalisation with
+// tab2d_row_norm_kernel, as a 2-D set's do.
 #include <hip/hip_runtime.h>
 #include "coop_kernel.h"
 #include "tab_launch.h"
@@ -102,13 +105,7 @@ void rim_tab_launch_pitchy_p(unsigned grid, hipStream_t st, double *d_set, doubl
 }
 
 template <class P>
-static RimCoopKernelInfo coop_info()
-{
-    RimCoopKernelInfo k;
-    k.fn = reinterpret_cast<const void *>(coop_kernel<P>);
-    k.waves = (int) P::WAVES; k.early_help = P::EARLY_HELP != 0; k.early_squad = (unsigned) P::EARLY_SQUAD;
-    return k;
-}
+static RimCoopKernelInfo coop_info() { return rim_coop_info<P>(reinterpret_cast<const void *>(coop_kernel<P>)); }
 
 // A set without pitch rows runs the instantiations that know so at compile time (DIST_TABULATED_ISO): the code isotropic
 // tables had before the pitch factor existed.  Same bits either way.
@@ -116,7 +113,8 @@ RimCoopKernelInfo rim_tab_coop_kernel(int problem, int tab_kind)
 {
     return rim_with_tab_kind(tab_kind, [&](auto K) {
         constexpr int KIND = decltype(K)::value;
-        return problem ? coop_info<HeyvaertsProblem<KIND>>() : coop_info<SymphonyProblem<KIND>>();
+        if constexpr (KIND == DIST_TABULATED_2D_GRID) return rim_tab_2d_grid_coop_kernel(problem);
+        else return problem ? coop_info<HeyvaertsProblem<KIND>>() : coop_info<SymphonyProblem<KIND>>();
     });
 }
 
@@ -127,7 +125,7 @@ void rim_tab_launch_norm(int tab_kind, unsigned grid, hipStream_t st, const Para
 {
     rim_with_tab_kind(tab_kind, [&](auto K) {
         constexpr int KIND = rim_tab_seam_kind(decltype(K)::value);
-        if constexpr (KIND == DIST_TABULATED_2D)
+        if constexpr (KIND == DIST_TABULATED_2D || KIND == DIST_TABULATED_2D_GRID)
             hipLaunchKernelGGL(tab2d_row_norm_kernel, dim3((unsigned) ((n + 255) / 256)), dim3(256), RIM_DYN_LDS, st, pp, n, d_norm);
         else
             hipLaunchKernelGGL(norm_kernel<KIND>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pp, n, d_norm, queue, spill);
@@ -139,7 +137,8 @@ void rim_tab_launch_integrand(int tab_kind, unsigned grid, hipStream_t st, const
 {
     rim_with_tab_kind(tab_kind, [&](auto K) {
         constexpr int KIND = rim_tab_seam_kind(decltype(K)::value);
-        hipLaunchKernelGGL(integrand_kernel_n<KIND>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pa, d_norm, count, d_n, d_gamma, d_out);
+        if constexpr (KIND == DIST_TABULATED_2D_GRID) rim_tab_2d_grid_launch_integrand(grid, st, pa, d_norm, count, d_n, d_gamma, d_out);
+        else hipLaunchKernelGGL(integrand_kernel_n<KIND>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pa, d_norm, count, d_n, d_gamma, d_out);
     });
 }
 
@@ -148,6 +147,7 @@ void rim_tab_launch_gamma_integral(int tab_kind, unsigned grid, hipStream_t st, 
 {
     rim_with_tab_kind(tab_kind, [&](auto K) {
         constexpr int KIND = rim_tab_seam_kind(decltype(K)::value);
-        hipLaunchKernelGGL(gamma_integral_kernel<KIND>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pa, d_norm, count, d_n, d_out, spill);
+        if constexpr (KIND == DIST_TABULATED_2D_GRID) rim_tab_2d_grid_launch_gamma_integral(grid, st, pa, d_norm, count, d_n, d_out, spill);
+        else hipLaunchKernelGGL(gamma_integral_kernel<KIND>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pa, d_norm, count, d_n, d_out, spill);
     });
 }

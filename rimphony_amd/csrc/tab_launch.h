@@ -1,5 +1,6 @@
 // tab_launch.h -- what rimphony_hip.hip asks of rimphony_tab.hip and rimphony_tab_group.hip, the translation units that hold
-// the kernels of the tabulated distribution (coop_kernel.h and group_kernel.h say why they have units of their own).
+// the kernels of the tabulated distribution (coop_kernel.h and group_kernel.h say why they have units of their own), and what
+// those two ask of the units that hold the kernels of one form each.
 #ifndef RIM_TAB_LAUNCH_H
 #define RIM_TAB_LAUNCH_H
 
@@ -17,15 +18,18 @@ struct RimCoopKernelInfo {
 // Every function takes the form of the installed table set as its DIST_TABULATED* value (dev_symphony.h), `tab_kind`, which
 // chooses the instantiation K: DIST_TABULATED for a set with pitch rows, DIST_TABULATED_ISO for an isotropic one,
 // DIST_TABULATED_2D for a 2-D set, DIST_TABULATED_PITCHY for one with a sin^k xi prefactor (and pitch rows or none),
-// DIST_TABULATED_GRID for one on gamma nodes of its own (with both of those or neither).
+// DIST_TABULATED_GRID for one on gamma nodes of its own (with both of those or neither), DIST_TABULATED_2D_GRID for a 2-D set
+// on gamma nodes of its own.
 
 // coop_kernel<SymphonyProblem<K>> (problem 0) or coop_kernel<HeyvaertsProblem<K>> (1)
 RimCoopKernelInfo rim_tab_coop_kernel(int problem, int tab_kind);
 // group_kernel<SymGroupProblem<K>>: the Symphony coefficients of a point in lock-step.  Launched with the grid and the
 // arguments of the analytic kinds' (group_launch.h); the kind has no Faraday group.  Defined in rimphony_tab_group.hip, which
 // asks rimphony_tab_grid_group.hip for the instantiation of DIST_TABULATED_GRID: that one has a unit of its own.
+// DIST_TABULATED_2D_GRID's likewise: rimphony_tab_2d_grid_group.hip.
 const void *rim_tab_group_kernel(int tab_kind);
 const void *rim_tab_grid_group_kernel();
+const void *rim_tab_2d_grid_group_kernel();
 // norm_kernel, integrand_kernel_n and gamma_integral_kernel of the kind: enqueue only, the caller asks hipGetLastError().
 // An isotropic set runs their DIST_TABULATED instantiations (rimphony_internal.h: rim_tab_seam_kind).  (The rows of a 2-D set
 // read their table's normalisation, which rim_tab_launch_table_norms computed when the set came in: one wave per table,
@@ -40,5 +44,25 @@ void rim_tab_launch_table_norms(unsigned grid, hipStream_t st, double *d_set, do
 // P of every table of a sin^k set WITH pitch rows, into the tables' headers: one wave per table, as the line above.  (A set
 // on given nodes passes the header of its tail, which reads as such a set: dev_symphony.h, tab_grid_tail.)
 void rim_tab_launch_pitchy_p(unsigned grid, hipStream_t st, double *d_set, double *spill);
+
+// The kernels of a 2-D set on given gamma nodes (DIST_TABULATED_2D_GRID) live in rimphony_tab_2d_grid.hip: the functions above
+// hand that form on to these.  Its rows read their table's normalisation as those of a 2-D set do (tab2d_row_norm_kernel);
+// rim_tab_2d_grid_launch_table_norms is the form's rim_tab_launch_table_norms.
+RimCoopKernelInfo rim_tab_2d_grid_coop_kernel(int problem);
+void rim_tab_2d_grid_launch_integrand(unsigned grid, hipStream_t st, const PointArgs &pa, const double *d_norm, size_t count,
+                                      const double *d_n, const double *d_gamma, double *d_out);
+void rim_tab_2d_grid_launch_gamma_integral(unsigned grid, hipStream_t st, const PointArgs &pa, const double *d_norm, size_t count,
+                                           const double *d_n, double *d_out, double *spill);
+void rim_tab_2d_grid_launch_table_norms(unsigned grid, hipStream_t st, double *d_set, double *spill);
+
+// RimCoopKernelInfo of coop_kernel<P>, `fn`
+template <class P>
+RimCoopKernelInfo rim_coop_info(const void *fn)
+{
+    RimCoopKernelInfo k;
+    k.fn = fn;
+    k.waves = (int) P::WAVES; k.early_help = P::EARLY_HELP != 0; k.early_squad = (unsigned) P::EARLY_SQUAD;
+    return k;
+}
 
 #endif

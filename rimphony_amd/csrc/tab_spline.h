@@ -25,6 +25,10 @@
 // rim_log(gamma_j), from the Thomas sweep on the non-uniform system; the layout of dev_symphony.h's tab_grid_*, with the
 // guide that tells a sample where to look for its interval.
 //
+// A 2-D set may stand on given gamma nodes too (rim_tab_check_2d_grid, rim_tab_build_2d_grid): the same four words per node,
+// the sweeps along u on the non-uniform system, the guide of a set on given nodes and one array of u nodes per set
+// (dev_symphony.h: tab_2d_grid_*).
+//
 // Plain C++ with the elementary functions of detmath.h, so that the library (hipcc's host pass) and the tests' table
 // oracle (g++) produce the same bits from the same table.
 #ifndef RIM_TAB_SPLINE_H
@@ -220,11 +224,9 @@ inline void rim_tab_build_pitchy(size_t n_tables, size_t n_nodes, double gamma_l
         rim_tab_build_pitchy_table(blob.data() + base, t, sin_k[t], n_mu, log_g, h, cp.data(), dp.data());
 }
 
-// rim_tab_check_pitchy() for a set on given nodes: gamma [n_nodes], finite, 1 <= gamma[0], strictly increasing, and so
-// are their logarithms as the build forms them (two gamma a rounding apart may share one: h_j = 0).  log_g, n_mu as for
-// rim_tab_check_pitch; sin_k may be null (no prefactor).
-inline int rim_tab_check_grid(size_t n_tables, size_t n_nodes, const double *gamma, const double *log_n, size_t n_mu,
-                              const double *log_g, const double *sin_k)
+// the nodes of a set on given nodes: gamma [n_nodes], finite, 1 <= gamma[0], strictly increasing, and so are their
+// logarithms as the build forms them (two gamma a rounding apart may share one: h_j = 0)
+inline int rim_tab_check_gamma_nodes(size_t n_nodes, const double *gamma)
 {
     using namespace rim;
     if (!gamma || n_nodes < RIM_TAB_MIN_NODES || n_nodes > RIM_TAB_MAX_NODES) return -1;
@@ -235,6 +237,14 @@ inline int rim_tab_check_grid(size_t n_tables, size_t n_nodes, const double *gam
         if (!(gamma[j] < gamma[j + 1])) return -1;
         if (!(rim_log(gamma[j]) < rim_log(gamma[j + 1]))) return -1;
     }
+    return 0;
+}
+
+// rim_tab_check_pitchy() for a set on given nodes.  log_g, n_mu as for rim_tab_check_pitch; sin_k may be null (no prefactor).
+inline int rim_tab_check_grid(size_t n_tables, size_t n_nodes, const double *gamma, const double *log_n, size_t n_mu,
+                              const double *log_g, const double *sin_k)
+{
+    if (rim_tab_check_gamma_nodes(n_nodes, gamma)) return -1;
     if (rim_tab_check_pitch(n_tables, n_nodes, gamma[0], gamma[n_nodes - 1], log_n, n_mu, log_g)) return -1;
     return sin_k ? rim_tab_check_sin_k(n_tables, sin_k) : 0;
 }
@@ -258,6 +268,20 @@ inline void rim_tab_spline_row_grid(const double *y, size_t n, const double *h, 
     for (size_t j = last; j-- > 0;) m[j] = dp[j] - cp[j] * m[j + 1];
 }
 
+// the guide of a set on the nodes u[0 .. n_nodes-1] (dev_symphony.h: tab_grid_cell): word c = min(the last node in a cell
+// below c, n_nodes - 2), 0 where there is none; cells + 1 words
+inline void rim_tab_fill_guide(const double *u, size_t n_nodes, size_t cells, double inv_cell, uint32_t *guide)
+{
+    using namespace rim;
+    size_t j = 0;
+    for (size_t c = 0; c <= cells; c++) {
+        while (j < n_nodes && (size_t) tab_grid_cell(u[j], u[0], inv_cell, (double) (cells - 1)) < c) j++;
+        size_t w = j ? j - 1 : 0;
+        if (w > n_nodes - 2) w = n_nodes - 2;
+        guide[c] = (uint32_t) w;
+    }
+}
+
 // the set on given nodes as one block of doubles (dev_symphony.h: tab_grid_*); rim_tab_check_grid() has passed.  sin_k
 // null: k = 0 for every table.  P of a table with a pitch row is 0 as built and the caller fills it, as for a sin^k set.
 inline void rim_tab_build_grid(size_t n_tables, size_t n_nodes, const double *gamma, const double *log_n, size_t n_mu,
@@ -276,15 +300,7 @@ inline void rim_tab_build_grid(size_t n_tables, size_t n_nodes, const double *ga
     h[n_nodes - 1] = 0.; ih[n_nodes - 1] = 0.;
     const double inv_cell = (double) cells / (u[n_nodes - 1] - u[0]);
     rim_tab_set_header(blob.data(), n_tables, n_nodes, gamma[0], gamma[n_nodes - 1], u[0], inv_cell, (double) cells, (double) n_mu);
-    // the guide: word c = min(the last node in a cell below c, n_nodes - 2), 0 where there is none
-    uint32_t *guide = (uint32_t *) (blob.data() + TAB_HDR_DOUBLES);
-    size_t j = 0;
-    for (size_t c = 0; c <= cells; c++) {
-        while (j < n_nodes && (size_t) tab_grid_cell(u[j], u[0], inv_cell, (double) (cells - 1)) < c) j++;
-        size_t w = j ? j - 1 : 0;
-        if (w > n_nodes - 2) w = n_nodes - 2;
-        guide[c] = (uint32_t) w;
-    }
+    rim_tab_fill_guide(u.data(), n_nodes, cells, inv_cell, (uint32_t *) (blob.data() + TAB_HDR_DOUBLES));
     for (size_t t = 0; t < n_tables; t++) {
         const double *y = log_n + t * n_nodes;
         double *row = blob.data() + TAB_HDR_DOUBLES + tab_grid_guide_doubles(cells) + t * n_nodes * 4;
@@ -359,6 +375,63 @@ inline void rim_tab_build_2d(size_t n_tables, size_t n_nodes, double gamma_lo, d
             for (size_t i = 0; i < n_nodes; i++) y[i] = nodes[(i * n_mu + j) * 4 + 2];
             rim_tab_spline_row(y.data(), n_nodes, h, pairs.data(), cp.data(), dp.data());
             for (size_t i = 0; i < n_nodes; i++) nodes[(i * n_mu + j) * 4 + 3] = pairs[2 * i + 1];
+        }
+    }
+}
+
+// rim_tab_check_2d() for a 2-D set on given nodes: gamma [n_nodes] as rim_tab_check_grid demands it, log_n
+// [n_tables][n_nodes][n_mu] and n_mu within the 2-D form's limits
+inline int rim_tab_check_2d_grid(size_t n_tables, size_t n_nodes, const double *gamma, size_t n_mu, const double *log_n)
+{
+    if (rim_tab_check_gamma_nodes(n_nodes, gamma)) return -1;
+    return rim_tab_check_2d(n_tables, n_nodes, gamma[0], gamma[n_nodes - 1], n_mu, log_n);
+}
+
+// the 2-D set on given nodes as one block of doubles (dev_symphony.h: tab_2d_grid_*); rim_tab_check_2d_grid() has passed.
+// The three families of sweeps in rim_tab_build_2d's order, those along u through rim_tab_spline_row_grid on h_i = u_{i+1} -
+// u_i; the guide as rim_tab_build_grid fills it.  The normalisation of a table is 0 as built and the caller fills it.
+inline void rim_tab_build_2d_grid(size_t n_tables, size_t n_nodes, const double *gamma, size_t n_mu, const double *log_n,
+                                  std::vector<double> &blob)
+{
+    using namespace rim;
+    size_t cells = 8;
+    while (cells < n_nodes) cells *= 2;
+    const double hm = 2. / (double) (n_mu - 1);
+    const size_t per_table = n_nodes * n_mu * 4, nodes_at = tab_2d_grid_nodes_at(n_tables, n_nodes, cells);
+    blob.assign(nodes_at + n_tables * per_table, 0.);
+    const size_t longest = n_nodes > n_mu ? n_nodes : n_mu;
+    std::vector<double> u(n_nodes), h(n_nodes), ih(n_nodes), m(n_nodes), y(longest), pairs(2 * longest), cp(longest), dp(longest);
+    for (size_t j = 0; j < n_nodes; j++) u[j] = rim_log(gamma[j]);
+    for (size_t j = 0; j + 1 < n_nodes; j++) { h[j] = u[j + 1] - u[j]; ih[j] = 1. / h[j]; }
+    h[n_nodes - 1] = 0.; ih[n_nodes - 1] = 0.;
+    const double inv_cell = (double) cells / (u[n_nodes - 1] - u[0]);
+    rim_tab_set_header(blob.data(), n_tables, n_nodes, gamma[0], gamma[n_nodes - 1], u[0], inv_cell, (double) cells, -(double) n_mu);
+    rim_tab_fill_guide(u.data(), n_nodes, cells, inv_cell, (uint32_t *) (blob.data() + tab_2d_grid_guide_at(n_tables)));
+    double *un = blob.data() + tab_2d_grid_guide_at(n_tables) + tab_grid_guide_doubles(cells);
+    for (size_t i = 0; i < n_nodes; i++) { un[2 * i] = u[i]; un[2 * i + 1] = ih[i]; }
+    for (size_t t = 0; t < n_tables; t++) {
+        double *th = blob.data() + TAB_HDR_DOUBLES + t * TAB_2D_HDR;
+        th[TAB_2D_LAST] = (double) (n_mu - 2);
+        th[TAB_2D_INVH] = 1. / hm;
+        th[TAB_2D_H] = hm;
+        const double *src = log_n + t * n_nodes * n_mu;
+        double *nodes = blob.data() + nodes_at + t * per_table;
+        for (size_t j = 0; j < n_mu; j++) {
+            for (size_t i = 0; i < n_nodes; i++) y[i] = src[i * n_mu + j];
+            rim_tab_spline_row_grid(y.data(), n_nodes, h.data(), ih.data(), m.data(), cp.data(), dp.data());
+            for (size_t i = 0; i < n_nodes; i++) {
+                nodes[(i * n_mu + j) * 4] = y[i];
+                nodes[(i * n_mu + j) * 4 + 1] = m[i];
+            }
+        }
+        for (size_t i = 0; i < n_nodes; i++) {
+            rim_tab_spline_row(src + i * n_mu, n_mu, hm, pairs.data(), cp.data(), dp.data());
+            for (size_t j = 0; j < n_mu; j++) nodes[(i * n_mu + j) * 4 + 2] = pairs[2 * j + 1];
+        }
+        for (size_t j = 0; j < n_mu; j++) {
+            for (size_t i = 0; i < n_nodes; i++) y[i] = nodes[(i * n_mu + j) * 4 + 2];
+            rim_tab_spline_row_grid(y.data(), n_nodes, h.data(), ih.data(), m.data(), cp.data(), dp.data());
+            for (size_t i = 0; i < n_nodes; i++) nodes[(i * n_mu + j) * 4 + 3] = m[i];
         }
     }
 }

@@ -117,6 +117,16 @@ public:
         check(rimphony_ctx_set_tables_2d(ctx_, n_tables, n_nodes, gamma_lo, gamma_hi, n_mu, n_tables ? log_n.data() : nullptr),
               "rimphony_ctx_set_tables_2d");
     }
+    // A 2-D set on gamma nodes of the caller's choosing (rimphony_ctx_set_tables_2d_grid): gamma [n_nodes] strictly increasing
+    // from >= 1, shared by the tables; log_n [n_tables][n_nodes][n_mu], mu fastest, the mu nodes uniform from -1 to +1.
+    void set_tables_2d_grid(size_t n_tables, const std::vector<double> &gamma, size_t n_mu, const std::vector<double> &log_n) const
+    {
+        if (log_n.size() != n_tables * gamma.size() * n_mu)
+            throw std::runtime_error("set_tables_2d_grid: log_n must hold n_tables * n_nodes * n_mu values");
+        check(rimphony_ctx_set_tables_2d_grid(ctx_, n_tables, gamma.size(), n_tables ? gamma.data() : nullptr, n_mu,
+                                              n_tables ? log_n.data() : nullptr),
+              "rimphony_ctx_set_tables_2d_grid");
+    }
 private:
     rimphony_ctx *ctx_ = nullptr;
 };
@@ -397,6 +407,32 @@ public:
 private:
     double glo_, ghi_;
     size_t n_nodes_, n_mu_;
+    std::vector<double> log_n_;
+};
+
+// A distribution given as a surface on gamma nodes of its own: log_n [n_nodes][n_mu], mu fastest, = ln n(gamma_i, mu_j) at
+// the strictly increasing gamma [n_nodes] and at mu nodes uniform from -1 to +1 (include/rimphony_hip.h:
+// rimphony_ctx_set_tables_2d_grid): TabulatedDistribution2D on the nodes of TabulatedDistributionGrid.  Used as those are.
+class TabulatedDistribution2DGrid : public DistributionFunction {
+protected:
+    int abi_kind() const override { return RIMPHONY_TABULATED; }
+    std::vector<double> abi_params() const override { return {0.}; }      // the table index
+public:
+    TabulatedDistribution2DGrid(std::vector<double> gamma, size_t n_mu, std::vector<double> log_n)
+        : gamma_(std::move(gamma)), n_mu_(n_mu), log_n_(std::move(log_n)) {}
+    void install(const Context &ctx) const { ctx.set_tables_2d_grid(1, gamma_, n_mu_, log_n_); }
+    double calc_f(const Context &ctx, double gamma, double cos_xi) const
+    { install(ctx); return DistributionFunction::calc_f(ctx, gamma, cos_xi); }
+    std::array<double, 2> calc_f_derivatives(const Context &ctx, double gamma, double cos_xi) const
+    { install(ctx); return DistributionFunction::calc_f_derivatives(ctx, gamma, cos_xi); }
+    FullSynchrotronCalculator full_calculation(std::shared_ptr<Context> ctx) const
+    {
+        install(*ctx);
+        return FullSynchrotronCalculator(std::move(ctx), RIMPHONY_TABULATED, {0.});
+    }
+private:
+    std::vector<double> gamma_;
+    size_t n_mu_;
     std::vector<double> log_n_;
 };
 
