@@ -9,8 +9,9 @@ evaluates that coefficient three ways, CPU only:
      cut-off at 1e-8 of the running sum, 300 discrete harmonics), literal flavour -- does the rimphony ALGORITHM
      converge to its own default value or to Symphony-C's?
   3. an independent evaluation that shares nothing with the Leung expansions: the harmonic sum with scipy's exact
-     J_n, J'_n (integer orders; the n-integral replaced by the plain sum over n, each gamma-integral by scipy
-     quad at 1e-10) -- the mathematical value of the expression both codes approximate.
+     J_n, J'_n (the n-integral replaced by the plain sum over n, each gamma-integral by the composite Gauss-Legendre
+     rule of tests/exact_symphony.py) -- the mathematical value of the expression both codes approximate.
+Section 3 sums up to 200 000 harmonics: seconds for a row with small s, well over ten minutes for row 159.
 usage: python tools/row159.py [row] [slot]"""
 import ctypes, math, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -56,60 +57,12 @@ for eg, en, tail, nd in ((1e-6, 1e-6, 1e8, 30), (1e-8, 1e-8, 1e8, 30), (1e-6, 1e
     print("2. tightened: eps_gamma %g eps_n %g tail 1/%g discrete %3d:            %.16e  rel. to Symphony-C %+.4e   (%d samples)"
           % (eg, en, tail, nd, v, v / gold - 1, ne))
 
-# 3. independent: exact Bessel functions, plain harmonic sum
-from scipy import integrate, special
-sn, cs = math.sin(th), math.cos(th)
-_, _, dist = run(libm)
-norm = dist.norm
-ME, C, E = 9.1093826e-28, 2.99792458e10, 4.80320680e-10
-
-
-def f_and_df(g):
-    beta = math.sqrt(1 - 1 / (g * g))
-    f = norm * g ** (-p) * math.exp(-g / 1e10) / (g * g * beta)
-    dfdg = -norm * g ** (-(p + 1)) / math.sqrt(g * g - 1) * math.exp(-g / 1e10) * ((p + 1) / g + g / (g * g - 1) + 1e-10)
-    return f, dfdg
-
-
-def integrand(g, n):
-    beta = math.sqrt(1 - 1 / (g * g))
-    cos_xi = (s * g - n) / (s * g * beta * cs)
-    if abs(cos_xi) >= 1:
-        return 0.
-    sin_xi = math.sqrt(1 - cos_xi * cos_xi)
-    m = (cs - beta * cos_xi) / sn
-    bn = beta * sin_xi
-    z = s * g * beta * sn * sin_xi
-    jn, djn = special.jv(n, z), special.jvp(n, z)
-    mj, njp = m * jn, bn * djn
-    pol = mj * mj + njp * njp if stokes == 0 else (mj * mj - njp * njp if stokes == 1 else 2 * mj * njp)
-    f, dfdg = f_and_df(g)
-    return g * g * pol * (f if coeff == 0 else dfdg)
-
-
-def gamma_int(n):
-    nos = n / s
-    root = math.sqrt(nos * nos - sn * sn)
-    gm, gp = (nos - abs(cs) * root) / sn ** 2, (nos + abs(cs) * root) / sn ** 2
-    peak = 0.5 * (gm + gp)
-    v = 0.
-    for a, b in ((gm, peak), (peak, gp)):
-        r, _ = integrate.quad(integrand, a, b, args=(n,), epsabs=0, epsrel=1e-10, limit=2000)
-        v += r
-    return v
-
-
-n0 = int(math.floor(s * abs(sn) + 1))
-total, n, small = 0., n0, 0
-while small < 200 and n < n0 + 200000:
-    c = gamma_int(float(n))
-    total += c
-    small = small + 1 if abs(c) < 1e-12 * abs(total) else 0
-    n += 1
-tpe = 2 * math.pi * E
-pref = (tpe * tpe) / (C * abs(cs)) if coeff == 0 else -(tpe * tpe) / (2 * ME * C * abs(cs))
-truth = total * pref * scale
-print("3. exact J_n (scipy), plain sum over %d harmonics, quad 1e-10:                  %.16e  rel. to Symphony-C %+.4e"
-      % (n - n0, truth, truth / gold - 1))
+# 3. independent: exact Bessel functions, plain harmonic sum (tests/exact_symphony.py)
+import exact_symphony
+dist = exact_symphony.power_law(p, 1.0, 1e12, 1e10)
+values, errors, harmonics, _ = exact_symphony.coefficients(dist, s, th, max_harmonics=200000, allow_truncated=True)
+truth = values[slot] * scale
+print("3. exact J_n (scipy), plain sum over %d harmonics, error estimate %.1e:           %.16e  rel. to Symphony-C %+.4e"
+      % (harmonics, errors[slot] / abs(values[slot]), truth, truth / gold - 1))
 v, _, _ = run(libm)
 print("   rimphony default vs exact: %+.4e ; Symphony-C vs exact: %+.4e" % (v / truth - 1, gold / truth - 1))
