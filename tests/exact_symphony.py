@@ -42,7 +42,8 @@ def pitch_integral(k):
 
 class Distribution:
     """Any f(gamma, mu) with its two derivatives.  The callables take (gamma, mu, xp) with xp = numpy or mpmath.mp and
-    return f without its normalisation; `norm` multiplies all three.  [gamma_lo, gamma_hi] are hard limits outside which
+    return f without its normalisation; `norm` multiplies all three.  A caller that knows sin^2 xi = 1 - mu^2 without the
+    cancellation passes it as a fourth argument.  [gamma_lo, gamma_hi] are hard limits outside which
     f = 0: the integrals are split there, so the callables are never asked beyond them."""
 
     def __init__(self, f, dfdg, dfdmu, norm, gamma_lo=1., gamma_hi=math.inf, name="f"):
@@ -83,27 +84,31 @@ def _energy_norm(h, k, gamma_lo, gamma_hi):
     return 1. / (4. * math.pi * pitch_integral(k) * v)
 
 
+def _sin2(mu, sin2):
+    return 1. - mu * mu if sin2 is None else sin2
+
+
 def thermal_juettner(T):
     """f = exp(-gamma / T) / (4 pi T K_2(1/T))"""
-    f = lambda g, mu, xp: xp.exp(-g / T)
-    dfdg = lambda g, mu, xp: -xp.exp(-g / T) / T
-    dfdmu = lambda g, mu, xp: 0. * g
+    f = lambda g, mu, xp, sin2=None: xp.exp(-g / T)
+    dfdg = lambda g, mu, xp, sin2=None: -xp.exp(-g / T) / T
+    dfdmu = lambda g, mu, xp, sin2=None: 0. * g
     norm = 1. / (4. * math.pi * T * special.kve(2, 1. / T) * math.exp(-1. / T))
     return Distribution(f, dfdg, dfdmu, norm, name="thermal_juettner")
 
 
 def pitchy_power_law(p, k, gamma_min, gamma_max, gamma_cutoff, name="pitchy_pl"):
     """f = sin^k xi gamma^-p exp(-gamma / gamma_c) / (gamma sqrt(gamma^2 - 1)) on [gamma_min, gamma_max]"""
-    def f(g, mu, xp):
-        return (1. - mu * mu) ** (0.5 * k) * g ** (-p) * xp.exp(-g / gamma_cutoff) / (g * xp.sqrt(g * g - 1.))
+    def f(g, mu, xp, sin2=None):
+        return _sin2(mu, sin2) ** (0.5 * k) * g ** (-p) * xp.exp(-g / gamma_cutoff) / (g * xp.sqrt(g * g - 1.))
 
-    def dfdg(g, mu, xp):
-        return -f(g, mu, xp) * ((p + 1.) / g + g / (g * g - 1.) + 1. / gamma_cutoff)
+    def dfdg(g, mu, xp, sin2=None):
+        return -f(g, mu, xp, sin2) * ((p + 1.) / g + g / (g * g - 1.) + 1. / gamma_cutoff)
 
-    def dfdmu(g, mu, xp):
+    def dfdmu(g, mu, xp, sin2=None):
         if k == 0.:
             return 0. * g
-        return -k * mu * (1. - mu * mu) ** (0.5 * k - 1.) * g ** (-p) * xp.exp(-g / gamma_cutoff) / (g * xp.sqrt(g * g - 1.))
+        return -k * mu * _sin2(mu, sin2) ** (0.5 * k - 1.) * g ** (-p) * xp.exp(-g / gamma_cutoff) / (g * xp.sqrt(g * g - 1.))
 
     norm = _energy_norm(lambda g: g ** (-p) * math.exp(-g / gamma_cutoff), k, gamma_min, gamma_max)
     return Distribution(f, dfdg, dfdmu, norm, gamma_min, gamma_max, name)
@@ -118,16 +123,16 @@ def pitchy_kappa(kappa, width, k, gamma_cutoff):
     def e(g, xp):
         return (1. + (g - 1.) / (kappa * width)) ** (-(kappa + 1.)) * xp.exp(-g / gamma_cutoff)
 
-    def f(g, mu, xp):
-        return (1. - mu * mu) ** (0.5 * k) * e(g, xp)
+    def f(g, mu, xp, sin2=None):
+        return _sin2(mu, sin2) ** (0.5 * k) * e(g, xp)
 
-    def dfdg(g, mu, xp):
-        return -f(g, mu, xp) * ((kappa + 1.) / (kappa * width + g - 1.) + 1. / gamma_cutoff)
+    def dfdg(g, mu, xp, sin2=None):
+        return -f(g, mu, xp, sin2) * ((kappa + 1.) / (kappa * width + g - 1.) + 1. / gamma_cutoff)
 
-    def dfdmu(g, mu, xp):
+    def dfdmu(g, mu, xp, sin2=None):
         if k == 0.:
             return 0. * g
-        return -k * mu * (1. - mu * mu) ** (0.5 * k - 1.) * e(g, xp)
+        return -k * mu * _sin2(mu, sin2) ** (0.5 * k - 1.) * e(g, xp)
 
     norm = _energy_norm(lambda g: g * math.sqrt(g * g - 1.) * e(g, math), k, 1., math.inf)
     return Distribution(f, dfdg, dfdmu, norm, name="pitchy_kappa")
@@ -136,9 +141,9 @@ def pitchy_kappa(kappa, width, k, gamma_cutoff):
 def tilted_juettner(T, a, gamma_lo, gamma_hi):
     """A non-separable surface through the general entry: f = exp(-gamma / T + a (gamma - 1) mu) on [gamma_lo, gamma_hi],
     a cold Juettner core whose temperature depends on the pitch angle."""
-    f = lambda g, mu, xp: xp.exp(-g / T + a * (g - 1.) * mu)
-    dfdg = lambda g, mu, xp: f(g, mu, xp) * (a * mu - 1. / T)
-    dfdmu = lambda g, mu, xp: f(g, mu, xp) * a * (g - 1.)
+    f = lambda g, mu, xp, sin2=None: xp.exp(-g / T + a * (g - 1.) * mu)
+    dfdg = lambda g, mu, xp, sin2=None: f(g, mu, xp) * (a * mu - 1. / T)
+    dfdmu = lambda g, mu, xp, sin2=None: f(g, mu, xp) * a * (g - 1.)
     return Distribution(f, dfdg, dfdmu, normalisation(f, gamma_lo, gamma_hi), gamma_lo, gamma_hi, "tilted_juettner")
 
 
