@@ -86,7 +86,11 @@ struct GroupMember {
     int sk[RIM_STASH], sf[RIM_STASH];
     double sr1[RIM_STASH], se1[RIM_STASH], sr2[RIM_STASH], se2[RIM_STASH];
     int snext;                  // replacement cursor
+    // hand-over of a pass to the turn's booking (group_book_turn): the children's result / abserr of a member that picked
+    // the pass's interval wait in fb[cur][0..3] (dead once integral cur has started), their flags -- as sf[] -- here
+    int hf;
 };
+static_assert(sizeof(GroupMember) == 456, "the hand-over flags live in the record's padding: the LDS block must not grow");
 
 struct GroupParkBase {
     GroupMember mem[RIM_GROUP];
@@ -193,6 +197,139 @@ __device__ __forceinline__ bool group_book(GroupMember *M, const IStore &st, con
     return finished;
 }
 
+// Member m booked by group_book from sums on file: its stash slot `pos` (stash) or the hand-over record of the pass.
+// Every lane reads the same operands (lane 0's view on all lanes); lanes 0 and 32 file their own child.
+__device__ __forceinline__ bool group_book_filed(GroupParkBase *gp, const IStore &st, const GKLane &g, int cur, int m,
+                                                 bool stash, int pos, double epsrel, int limit)
+{
+    GroupMember *const M = gp->mem + m;
+    const int imax = uni(M->imax);
+    double area1, error1, area2, error2;
+    int fl;
+    if (stash) { area1 = M->sr1[pos]; error1 = M->se1[pos]; area2 = M->sr2[pos]; error2 = M->se2[pos]; fl = uni(M->sf[pos]); }
+    else { const double *h = M->fb[cur]; area1 = h[0]; error1 = h[1]; area2 = h[2]; error2 = h[3]; fl = uni(M->hf); }
+    const IEntry en = ist_entry(st, imax);
+    wv_sync();
+    if (stash && g.lane == 0) M->sk[pos] = -1;
+    return group_book(M, st, g, cur, imax, uni(en.a), uni(en.b), area1, error1, area2, error2, fl == 3,
+                      g.half ? area2 : area1, g.half ? error2 : error1, epsrel, limit);
+}
+
+// qag.c's loop body for all members of `set` in ONE execution: lane m (m < RIM_GROUP) is member m in child 1's view, lane
+// 32 + m the same member in child 2's view, the other lanes idle.  Every operand reaches its lane through LDS at a
+// per-lane address -- the member's record, the entry at its imax in its own list (the members may have picked different
+// intervals), the children's sums from the hand-over record or from stash slot (posp >> 4 m) & 7 -- and the arithmetic is
+// group_book's, operation for operation, with lane 0's ballots as per-lane predicates.  Lane m and lane 32 + m file their
+// own child, lane m writes the record back (and, for a finished member, its status).  Only for lists whose LDS part
+// holds the parent and both children; returns false, having changed nothing, if some member's list is longer.
+struct GroupBooked { unsigned finished, need_pick; };
+
+__device__ __forceinline__ bool group_book_lanes(GroupParkBase *gp, double *inner_lds, const GKLane &g, int cur, unsigned set,
+                                                 bool stash, unsigned posp, double epsrel, int limit, GroupBooked &out)
+{
+    // The lane's member and the addresses derived from it are rebuilt here in every call: as loop invariants of the
+    // kernel they would hold vector registers through every pass (here a register is worth more than an instruction).
+    int lane = g.lane;
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(RIM_WAVE_EMU)
+    asm volatile("" : "+v"(lane));
+#endif
+    const int ml = lane & (RIM_GROUP - 1);
+    const bool half = (lane & 32) != 0;
+    const bool valid = (lane & 31) < RIM_GROUP && ((set >> ml) & 1u) != 0;
+    GroupMember *const M = gp->mem + ml;
+    int iteration = M->iteration, size = M->size, rt1 = M->rt1, rt2 = M->rt2;
+    if (!inner_lds || wv_ballot(valid && size >= CAP_GINNER)) return false;
+    const int imax = valid ? M->imax : 0;
+    const IStore st = group_store(inner_lds, CAP_GINNER, nullptr, 0, ml);
+    const double a_i = st.a[imax], b_i = st.b[imax], r_i = st.r[imax], e_i = st.e[imax];
+    const int pos = (int) ((posp >> (4 * ml)) & (unsigned) (RIM_STASH - 1));
+    double area1, error1, area2, error2;
+    int fl;
+    if (stash) { area1 = M->sr1[pos]; error1 = M->se1[pos]; area2 = M->sr2[pos]; error2 = M->se2[pos]; fl = M->sf[pos]; }
+    else { const double *h = M->fb[cur]; area1 = h[0]; error1 = h[1]; area2 = h[2]; error2 = h[3]; fl = M->hf; }
+    const double mid = 0.5 * (a_i + b_i);
+    const double area12 = area1 + area2;
+    const double error12 = error1 + error2;
+    const double errsum = M->errsum + (error12 - e_i);
+    const double area = M->area + (area12 - r_i);
+    if (fl == 3) {
+        const double delta = r_i - area12;
+        if (rim_fabs(delta) <= 1.0e-5 * rim_fabs(area12) && error12 >= 0.99 * e_i) rt1++;
+        if (iteration >= 10 && error12 > e_i) rt2++;
+    }
+    const double tolerance = epsrel * rim_fabs(area);
+    const bool more = errsum > tolerance;
+    int error_type = 0;
+    if (more) {
+        if (rt1 >= 6 || rt2 >= 20) error_type = 2;
+        const double tmp = (1 + 100 * RIM_DBL_EPSILON) * (rim_fabs(mid) + 1000 * RIM_DBL_MIN);
+        if (rim_fabs(a_i) <= tmp && rim_fabs(b_i) <= tmp) error_type = 3;
+    }
+    const bool c2gt = error2 > error1;
+    const bool keep = (half) == c2gt;
+    const int slot = keep ? imax : size;
+    const int stamp = 2 * iteration + (keep ? 0 : 1);
+    size++;
+    iteration++;
+    const bool finished = !(iteration < limit && !error_type && more);
+    wv_sync();               // every lane has read the parent's entry and the member's sums
+    if (valid) {
+        st.a[slot] = half ? mid : a_i; st.b[slot] = half ? b_i : mid;
+        st.r[slot] = half ? area2 : area1; st.e[slot] = half ? error2 : error1;
+        st.stamp[slot] = stamp;
+        if (!half) {
+            M->area = area; M->errsum = errsum;
+            M->iteration = iteration; M->size = size; M->rt1 = rt1; M->rt2 = rt2;
+            M->samples += 62u;
+            if (stash) M->sk[pos] = -1;
+            if (finished)
+                M->qst[cur] = errsum <= tolerance ? QAG_SUCCESS : error_type == 2 ? QAG_EROUND : error_type == 3 ? QAG_ESING
+                            : iteration == limit ? QAG_EMAXITER : QAG_EFAILED;
+        }
+    }
+    const unsigned members = (1u << RIM_GROUP) - 1u;
+    out.finished = (unsigned) wv_ballot(valid && finished) & members;
+    out.need_pick = (unsigned) wv_ballot(valid && !finished) & members;
+    return true;
+}
+
+// The booking of a turn: the members of `set`, whose children's sums are on file -- all of them in their stash (places
+// posp) or all of them in the hand-over record of the turn's pass.  Side by side when every list stays within its LDS
+// part; a list that reaches the spill region or the store's capacity sends the turn's members through group_book one
+// by one.
+__device__ __forceinline__ GroupBooked group_book_turn(GroupParkBase *gp, double *inner_lds, double *inner_spill, const GKLane &g,
+                                                       int cur, unsigned set, bool stash, unsigned posp, double epsrel, int limit)
+{
+    GroupBooked bk;
+    bk.finished = 0; bk.need_pick = 0;
+    wv_sync();               // the hand-over records of the pass are visible to every lane
+    if (group_book_lanes(gp, inner_lds, g, cur, set, stash, posp, epsrel, limit, bk)) {
+        if (bk.finished) {
+            // the epilogue of a finished member: once per gamma-integral, in turn
+            wv_sync();
+            for (unsigned rem = bk.finished; rem; rem &= rem - 1) {
+                const int m = __builtin_ctz(rem);
+                GroupMember *const M = gp->mem + m;
+                const IStore st = group_store(inner_lds, CAP_GINNER, inner_spill, SPILL_GINNER, m);
+                const int size = uni(M->size);
+                double sum = 0;
+                for (int k = 0; k < size; k++) sum += st.r[k];
+                if (g.lane == 0) M->res[cur] = sum;
+                RIM_HIT(22);
+            }
+        }
+        return bk;
+    }
+    for (unsigned rem = set; rem; rem &= rem - 1) {
+        const int m = __builtin_ctz(rem);
+        const IStore st = group_store(inner_lds, CAP_GINNER, inner_spill, SPILL_GINNER, m);
+        if (group_book_filed(gp, st, g, cur, m, stash, (int) ((posp >> (4 * m)) & (unsigned) (RIM_STASH - 1)), epsrel, limit))
+            bk.finished |= 1u << m;
+        else bk.need_pick |= 1u << m;
+    }
+    return bk;
+}
+
 // Integral A on [a0, b0] for the members of maskA, integral B on [a1, b1] for those of maskB (maskB == 0: none); as in
 // wave_qag_pair the two share their first rule application (A on lanes 0..30, B on 32..62), then A's members run to
 // the end, then B's.  The integrand is a functor with two steps:
@@ -226,6 +363,7 @@ __device__ __forceinline__ void wave_qag_group(F &f, const GKLane &g, double *in
         unsigned serve = 0;             // members whose rule sums this turn's pass produces
         unsigned booknow = 0;           // ... of them, those that picked the pass's interval: booked from the registers
         unsigned from_stash = 0;        // members whose pick is on file: booked without a pass
+        unsigned posp = 0;              // ... and the places of their picks in their stashes, 4 bits per member
         // entry of the pass's interval in each served member's list: four 16-bit fields of one wave-uniform word (list
         // indices stay below the GSL limits, 5000 / 4096) -- as four ints indexed by the member they lived in a scratch
         // array and came back as vector registers
@@ -257,7 +395,10 @@ __device__ __forceinline__ void wave_qag_group(F &f, const GKLane &g, double *in
                     RIM_PROF_ADD(13, t_pick);
                 }
                 if (lane == 0) M->imax = imax;
-                if (((stashed >> m) & 1u) && stash_find(M, imax, lane) >= 0) from_stash |= 1u << m;
+                if ((stashed >> m) & 1u) {
+                    const int pos = stash_find(M, imax, lane);
+                    if (pos >= 0) { from_stash |= 1u << m; posp |= (unsigned) pos << (4 * m); }
+                }
             }
             if (need_pick) wv_sync();
             need_pick = 0;
@@ -347,15 +488,13 @@ __device__ __forceinline__ void wave_qag_group(F &f, const GKLane &g, double *in
                 } else {
                     const unsigned long long ne = wv_ballot(r.resasc != r.abserr);
                     if ((booknow >> m) & 1u) {
-                        RIM_PROF_T(t_ab);
-                        const IStore st = group_store(inner_lds, CAP_GINNER, inner_spill, SPILL_GINNER, m);
-                        const bool fin = group_book(M, st, g, cur, (int) ((idxp >> (16 * m)) & 0xffffull), a_i, b_i,
-                                                    r.result, r.abserr, readlane_d(r.result, 32), readlane_d(r.abserr, 32),
-                                                    (ne & 1ull) && ((ne >> 32) & 1ull), r.result, r.abserr, epsrel, limit);
-                        n_samp_all += 62u;
-                        n_member_pass += 1;
-                        if (fin) active &= ~(1u << m); else need_pick |= 1u << m;
-                        RIM_PROF_ADD(12, t_ab);
+                        // the member picked the pass's interval: lanes 0 and 32 hand their child's sums over to the
+                        // turn's booking
+                        if (g.j == 0) {
+                            double *h = M->fb[cur] + 2 * g.half;
+                            h[0] = r.result; h[1] = r.abserr;
+                            if (!g.half) M->hf = (int) (ne & 1ull) | (int) (((ne >> 32) & 1ull) << 1);
+                        }
                     } else {
                         // file the children's sums in the member's stash (a free place, else the next one in turn)
                         RIM_PROF_T(t_file);
@@ -378,28 +517,19 @@ __device__ __forceinline__ void wave_qag_group(F &f, const GKLane &g, double *in
             }
         }
 
-        if (from_stash) {
-            // ---- members whose pick has its children's sums on file: qag.c's loop body without a pass ----
-            RIM_PROF_T(t_fs);
-            for (unsigned rem = from_stash; rem; rem &= rem - 1) {
-                const int m = __builtin_ctz(rem);
-                GroupMember *const M = gp->mem + m;
-                const IStore st = group_store(inner_lds, CAP_GINNER, inner_spill, SPILL_GINNER, m);
-                const int imax = uni(M->imax);
-                const int pos = stash_find(M, imax, lane);
-                const double area1 = M->sr1[pos], error1 = M->se1[pos], area2 = M->sr2[pos], error2 = M->se2[pos];
-                const int sfl = uni(M->sf[pos]);
-                const IEntry en = ist_entry(st, imax);
-                wv_sync();
-                if (lane == 0) M->sk[pos] = -1;
-                const bool fin = group_book(M, st, g, cur, imax, uni(en.a), uni(en.b), area1, error1, area2, error2, sfl == 3,
-                                            g.half ? area2 : area1, g.half ? error2 : error1, epsrel, limit);
-                n_samp_all += 62u;
-                n_member_pass += 1;
-                n_used += 1;
-                if (fin) active &= ~(1u << m); else need_pick |= 1u << m;
-            }
-            RIM_PROF_ADD(22, t_fs);
+        if (booknow | from_stash) {
+            // ---- qag.c's loop body for the members that picked the pass's interval, or -- without a pass -- for those
+            // whose pick has its children's sums on file ----
+            RIM_PROF_T(t_ab);
+            const unsigned set = booknow | from_stash;
+            const GroupBooked bk = group_book_turn(gp, inner_lds, inner_spill, g, cur, set, from_stash != 0, posp, epsrel, limit);
+            const unsigned n_set = (unsigned) __builtin_popcount(set);
+            n_samp_all += 62u * n_set;
+            n_member_pass += n_set;
+            if (from_stash) n_used += n_set;
+            active &= ~bk.finished;
+            need_pick |= bk.need_pick;
+            RIM_PROF_ADD(12, t_ab);
         }
 
         // ---- the next integral, once the current one has no unfinished member ----

@@ -35,9 +35,9 @@ names = {0: "kernel (wave lifetime)",
          6: "    distribution terms (both)",
          20: "  member term",
          11: "  wave_gk31 per member",
-         12: "  group_book (picked members)",
+         12: "  booking of the turn (group_book_turn: picked members, or those whose pick was on file)",
          21: "  stash filing",
-         22: "  booking from the stash",
+         22: "  (booking from the stash: in region 12 since the side-by-side booking)",
          23: "  next integral / first-rule decisions",
          26: "consume (sym_consume of the members that posted)",
          10: "empty region (timer cost, once per sample pass)",
