@@ -203,7 +203,8 @@ int rimphony_ctx_set_tables_pitch(rimphony_ctx *ctx, size_t n_tables, size_t n_n
  * in other arithmetic (agreement to rounding, not to the bit).  A mu a rounding beyond +-1 extrapolates the end cell; a NaN
  * gives NaN.  The natural end condition (second derivative 0 across every edge of the grid) costs accuracy where the surface
  * is curved at an edge: there the error falls with the fourth power of the spacing only in the interior.  g -> 0 at mu = +-1
- * cannot be held in ln n: floor it, as for a pitch row.  A table that ends at a non-negligible n behaves like gamma limits.
+ * cannot be held in ln n: give it as a sin^k xi prefactor (rimphony_ctx_set_tables_2d_pitchy below), or floor it, as for a pitch
+ * row.  A table that ends at a non-negligible n behaves like gamma limits.
  * The normalisation is a property of a table, not of a row: the call integrates it once per table on the device (the
  * 31-point Kronrod rule on every mu cell inside an adaptive quadrature over gamma, eps_rel 1e-8) and keeps it beside the
  * table; rimphony_batch_norm* and the coefficient entries read it.  A table whose quadrature fails has a NaN
@@ -290,9 +291,35 @@ int rimphony_ctx_set_tables_grid(rimphony_ctx *ctx, size_t n_tables, size_t n_no
  * whose quadrature fails has a NaN normalisation and its rows are NaN with RIMPHONY_ST_NORM_FAIL, the other tables are
  * unaffected.  A row is still RIMPHONY_TABULATED with one parameter, the table index.  Everything else -- a bad index, the
  * precisions and closed forms refused, the _multi entries, RIMPHONY_TAB_GROUP (this form follows the 2-D form's default) -- is
- * as for rimphony_ctx_set_tables_2d.  Not offered: mu nodes of the caller's choosing, a grid per table, a sin^k prefactor. */
+ * as for rimphony_ctx_set_tables_2d.  Not offered: mu nodes of the caller's choosing, a grid per table. */
 int rimphony_ctx_set_tables_2d_grid(rimphony_ctx *ctx, size_t n_tables, size_t n_nodes, const double *gamma, size_t n_mu,
                                     const double *log_n);
+
+/* The two 2-D forms with a sin^k xi prefactor per table, for a distribution that vanishes along the field and whose
+ * anisotropy changes with energy -- a loss cone whose depth grows with gamma.  ln n of such a distribution diverges at mu =
+ * +-1 and no surface can hold it; the caller divides the histogram by sin^k xi and tabulates the smooth remainder:
+ * f(gamma, mu) = norm sin^k xi exp(S(ln gamma, mu)) / (gamma^2 beta) inside the table, +0 outside;
+ * df/dmu = f (S_mu - k mu / sin^2 xi), df/dgamma as for the 2-D form it extends;
+ * norm = 1 / (4 pi int nbar dgamma), nbar(gamma) = 1/2 int_{-1}^{+1} (1 - mu^2)^(k/2) exp(S) dmu.
+ *   sin_k   HOST, [n_tables]: the exponent k of each table, finite with 0 <= k <= 100 -- else RIMPHONY_EINVAL, checked on
+ *           the host, and the previous set stays;
+ *   everything else exactly as for rimphony_ctx_set_tables_2d and rimphony_ctx_set_tables_2d_grid: shapes, limits, n_nodes n_mu
+ *           <= 2^20, n_tables = 0 clearing the set, replacing a set of any form, RIMPHONY_ENOMEM leaving the previous set.
+ * sin_k == NULL is the entry without _pitchy exactly: the same form, the same kernels, the same bits.
+ * The factor is formed as the pitchy kinds and rimphony_ctx_set_tables_pitchy form it, pow(sqrt(1 - mu^2), k).  At |mu| = 1
+ * that form gives f = 0 and df/dmu = NaN (0 x inf) for k > 0; for k = 0 given explicitly the factor is 1 and the term 0 mu /
+ * 0 is NaN there too.  A mu a rounding beyond +-1 gives NaN (the square root of a negative number), where the plain 2-D
+ * forms extrapolate the end cell.
+ * The normalisation of each table is integrated once, on the device, when the set is installed: over gamma adaptively (eps_rel
+ * 1e-8, 1000 subintervals), nbar by the 31-point Kronrod rule on every mu cell, the two end cells under the substitution 1 -
+ * |mu| = h v^4, which takes the singular derivative of the factor at mu = +-1 out of the integrand for every k (DESIGN.md
+ * section 5).  A table whose quadrature fails has a NaN normalisation and its rows are NaN with RIMPHONY_ST_NORM_FAIL.
+ * A row is still RIMPHONY_TABULATED with one parameter, the table index; RIMPHONY_TAB_GROUP follows the 2-D form's default.
+ * Not offered: mu nodes of the caller's choosing, a grid per table, an exponent per row. */
+int rimphony_ctx_set_tables_2d_pitchy(rimphony_ctx *ctx, size_t n_tables, size_t n_nodes, double gamma_lo, double gamma_hi,
+                                      size_t n_mu, const double *log_n, const double *sin_k);
+int rimphony_ctx_set_tables_2d_grid_pitchy(rimphony_ctx *ctx, size_t n_tables, size_t n_nodes, const double *gamma, size_t n_mu,
+                                           const double *log_n, const double *sin_k);
 
 /* Work counters of the most recent batch call on this context (device-side
  * counts, read back synchronously): integrand samples, wave-wide evaluation

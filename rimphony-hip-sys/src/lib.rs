@@ -143,6 +143,25 @@ extern "C" {
         n_mu: usize,
         log_n: *const c_double,
     ) -> c_int;
+    pub fn rimphony_ctx_set_tables_2d_pitchy(
+        ctx: *mut rimphony_ctx,
+        n_tables: usize,
+        n_nodes: usize,
+        gamma_lo: c_double,
+        gamma_hi: c_double,
+        n_mu: usize,
+        log_n: *const c_double,
+        sin_k: *const c_double,
+    ) -> c_int;
+    pub fn rimphony_ctx_set_tables_2d_grid_pitchy(
+        ctx: *mut rimphony_ctx,
+        n_tables: usize,
+        n_nodes: usize,
+        gamma: *const c_double,
+        n_mu: usize,
+        log_n: *const c_double,
+        sin_k: *const c_double,
+    ) -> c_int;
 
     pub fn rimphony_last_work(ctx: *mut rimphony_ctx, out: *mut rimphony_work) -> c_int;
     pub fn rimphony_last_tail(ctx: *mut rimphony_ctx, out: *mut u64) -> c_int;
@@ -364,6 +383,42 @@ impl HipContext {
         let rc = unsafe {
             rimphony_ctx_set_tables_2d_grid(
                 self.raw, log_n.len() / (n_nodes * n_mu), n_nodes, gamma.as_ptr(), n_mu, log_n.as_ptr(),
+            )
+        };
+        if rc != RIMPHONY_OK {
+            return Err(error_text(rc));
+        }
+        Ok(())
+    }
+
+    /// The 2-D table set with a sin^k xi prefactor per table: `sin_k` holds one exponent in [0, 100] per surface, `log_n`
+    /// the smooth remainder ln(n / sin^k xi) (include/rimphony_hip.h: rimphony_ctx_set_tables_2d_pitchy).
+    pub fn set_tables_2d_pitchy(
+        &self, n_nodes: usize, gamma_lo: f64, gamma_hi: f64, n_mu: usize, log_n: &[f64], sin_k: &[f64],
+    ) -> Result<(), String> {
+        if n_nodes == 0 || n_mu == 0 || log_n.len() % (n_nodes * n_mu) != 0 || sin_k.len() != log_n.len() / (n_nodes * n_mu) {
+            return Err(error_text(RIMPHONY_EINVAL));
+        }
+        let rc = unsafe {
+            rimphony_ctx_set_tables_2d_pitchy(
+                self.raw, sin_k.len(), n_nodes, gamma_lo, gamma_hi, n_mu, log_n.as_ptr(), sin_k.as_ptr(),
+            )
+        };
+        if rc != RIMPHONY_OK {
+            return Err(error_text(rc));
+        }
+        Ok(())
+    }
+
+    /// The same on gamma nodes of the caller's choosing (include/rimphony_hip.h: rimphony_ctx_set_tables_2d_grid_pitchy).
+    pub fn set_tables_2d_grid_pitchy(&self, gamma: &[f64], n_mu: usize, log_n: &[f64], sin_k: &[f64]) -> Result<(), String> {
+        let n_nodes = gamma.len();
+        if n_nodes == 0 || n_mu == 0 || log_n.len() % (n_nodes * n_mu) != 0 || sin_k.len() != log_n.len() / (n_nodes * n_mu) {
+            return Err(error_text(RIMPHONY_EINVAL));
+        }
+        let rc = unsafe {
+            rimphony_ctx_set_tables_2d_grid_pitchy(
+                self.raw, sin_k.len(), n_nodes, gamma.as_ptr(), n_mu, log_n.as_ptr(), sin_k.as_ptr(),
             )
         };
         if rc != RIMPHONY_OK {

@@ -72,6 +72,9 @@ def build_hip(force=False, verbose=False):
                                     os.path.join(CSRC, "rimphony_tab.hip"), os.path.join(CSRC, "rimphony_tab_group.hip"),
                                     os.path.join(CSRC, "rimphony_tab_grid_group.hip"),
                                     os.path.join(CSRC, "rimphony_tab_2d_grid.hip"), os.path.join(CSRC, "rimphony_tab_2d_grid_group.hip"),
+                                    os.path.join(CSRC, "rimphony_tab_2d_pitchy.hip"), os.path.join(CSRC, "rimphony_tab_2d_pitchy_group.hip"),
+                                    os.path.join(CSRC, "rimphony_tab_2d_grid_pitchy.hip"),
+                                    os.path.join(CSRC, "rimphony_tab_2d_grid_pitchy_group.hip"),
                                     "-ldl", "-o", LIB]
     if verbose:
         print(" ".join(cmd))
@@ -174,3 +177,15 @@ def build_tab_grid_oracle():
 def build_tab2d_grid_oracle():
     """The same for 2-D table sets on given gamma nodes (tests/support/tab2d_grid_oracle.cpp)."""
     return _build_dist_oracle("tab2d_grid_oracle.cpp", "liboracle_tab2dgrid.so")
+
+
+def build_tab2d_pitchy_oracle():
+    """The same for 2-D table sets with a sin^k xi prefactor per table, on nodes uniform in ln gamma or given
+    (tests/support/tab2d_pitchy_oracle.cpp)."""
+    return _build_dist_oracle("tab2d_pitchy_oracle.cpp", "liboracle_tab2dpitchy.so")
+
+
+def build_pitchy_tilt_oracle():
+    """The CPU oracle of the analytic tilted power law times sin^k xi (tests/support/pitchy_tilt_oracle.cpp): what the 2-D
+    tables with a sin^k prefactor are compared with.  Tests only."""
+    return _build_dist_oracle("pitchy_tilt_oracle.cpp", "liboracle_pitchy_tilt.so")

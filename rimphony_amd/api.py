@@ -284,31 +284,48 @@ class Context:
                                                          None if k is None else k.ctypes.data_as(dp)),
                    "rimphony_ctx_set_tables_grid")
 
-    def set_tables_2d(self, gamma_lo, gamma_hi, log_n):
+    def set_tables_2d(self, gamma_lo, gamma_hi, log_n, sin_k=None):
         """The context's table set for kind TABULATED as surfaces: log_n [n_tables][n_nodes][n_mu] (a 2-D array is one
         table) = ln n(gamma, mu) at nodes uniform in ln gamma from gamma_lo to gamma_hi and uniform in mu = cos xi from -1
         to +1; f = norm exp(S) / (gamma^2 beta) with S the tensor-product natural cubic spline.  Replaces the previous set of
         any form; None clears it.  Synchronous: the normalisation of every table is integrated here, once
-        (include/rimphony_hip.h: rimphony_ctx_set_tables_2d)."""
+        (include/rimphony_hip.h: rimphony_ctx_set_tables_2d).
+        sin_k (a scalar, or one value per table, each in [0, 100]) multiplies each table by sin^k xi in closed form, f =
+        norm sin^k xi exp(S) / (gamma^2 beta): for a distribution that vanishes along the field, whose ln n no surface can
+        hold.  log_n is then the smooth remainder, ln(n / sin^k xi) (rimphony_ctx_set_tables_2d_pitchy)."""
         if log_n is None:
             capi.check(self.lib.rimphony_ctx_set_tables_2d(self.handle, 0, 0, 1.0, 2.0, 0, None), "rimphony_ctx_set_tables_2d")
             return
         t = check_tables_2d(gamma_lo, gamma_hi, log_n)
+        if sin_k is not None:
+            k = check_sin_k(sin_k, t.shape[0])
+            dp = ctypes.POINTER(ctypes.c_double)
+            capi.check(self.lib.rimphony_ctx_set_tables_2d_pitchy(self.handle, t.shape[0], t.shape[1], float(gamma_lo), float(gamma_hi),
+                                                                  t.shape[2], t.ctypes.data_as(dp), k.ctypes.data_as(dp)),
+                       "rimphony_ctx_set_tables_2d_pitchy")
+            return
         capi.check(self.lib.rimphony_ctx_set_tables_2d(self.handle, t.shape[0], t.shape[1], float(gamma_lo), float(gamma_hi),
                                                        t.shape[2], t.ctypes.data_as(ctypes.POINTER(ctypes.c_double))),
                    "rimphony_ctx_set_tables_2d")
 
-    def set_tables_2d_grid(self, gamma, log_n):
+    def set_tables_2d_grid(self, gamma, log_n, sin_k=None):
         """The context's table set as surfaces on gamma nodes of the caller's choosing: gamma [n_nodes] strictly increasing
         from >= 1, shared by the tables; log_n [n_tables][n_nodes][n_mu] (a 2-D array is one table) = ln n(gamma_i, mu_j),
         the mu nodes uniform from -1 to +1.  What set_tables_2d holds, on the nodes set_tables_grid takes: a cold core under
         an anisotropic tail.  Replaces the previous set of any form; log_n None clears it.  Synchronous: the normalisation of
-        every table is integrated here, once (include/rimphony_hip.h: rimphony_ctx_set_tables_2d_grid)."""
+        every table is integrated here, once (include/rimphony_hip.h: rimphony_ctx_set_tables_2d_grid).  sin_k as for
+        set_tables_2d (rimphony_ctx_set_tables_2d_grid_pitchy)."""
         if log_n is None:
             capi.check(self.lib.rimphony_ctx_set_tables_2d_grid(self.handle, 0, 0, None, 0, None), "rimphony_ctx_set_tables_2d_grid")
             return
         g, t = check_tables_2d_grid(gamma, log_n)
         dp = ctypes.POINTER(ctypes.c_double)
+        if sin_k is not None:
+            k = check_sin_k(sin_k, t.shape[0])
+            capi.check(self.lib.rimphony_ctx_set_tables_2d_grid_pitchy(self.handle, t.shape[0], t.shape[1], g.ctypes.data_as(dp),
+                                                                       t.shape[2], t.ctypes.data_as(dp), k.ctypes.data_as(dp)),
+                       "rimphony_ctx_set_tables_2d_grid_pitchy")
+            return
         capi.check(self.lib.rimphony_ctx_set_tables_2d_grid(self.handle, t.shape[0], t.shape[1], g.ctypes.data_as(dp), t.shape[2],
                                                             t.ctypes.data_as(dp)),
                    "rimphony_ctx_set_tables_2d_grid")
@@ -845,27 +862,29 @@ class TabulatedDistribution2D(TabulatedDistribution):
     """A distribution given as a surface: log_n [n_nodes][n_mu] = ln n(gamma, mu) at nodes uniform in ln gamma from
     gamma_lo to gamma_hi and uniform in mu = cos xi from -1 to +1; f = norm exp(S(ln gamma, mu)) / (gamma^2 beta) inside
     the table, 0 outside, S the tensor-product natural cubic spline (Context.set_tables_2d).  It need not be a product
-    n(gamma) g(mu).  Installs its table whenever it computes, as TabulatedDistribution does."""
+    n(gamma) g(mu).  sin_k, a number in [0, 100], multiplies it by sin^k xi in closed form: log_n is then the smooth
+    remainder ln(n / sin^k xi).  Installs its table whenever it computes, as TabulatedDistribution does."""
 
-    def __init__(self, gamma_lo, gamma_hi, log_n):
+    def __init__(self, gamma_lo, gamma_hi, log_n, sin_k=None):
         self.gamma_lo, self.gamma_hi = float(gamma_lo), float(gamma_hi)
         log_n = np.asarray(log_n, dtype=np.float64)
         if log_n.ndim != 2:
             raise ValueError("log_n: expected one table, [n_nodes][n_mu]")
         self.log_n = check_tables_2d(self.gamma_lo, self.gamma_hi, log_n)
+        self.sin_k = None if sin_k is None else check_sin_k(sin_k, 1)
 
     @classmethod
-    def from_function(cls, fn, gamma_lo, gamma_hi, n_nodes=512, n_mu=65):
+    def from_function(cls, fn, gamma_lo, gamma_hi, n_nodes=512, n_mu=65, sin_k=None):
         """Tabulate n(gamma, mu) = fn(gamma[:, None], mu[None, :]) (vectorised, positive) on n_nodes nodes uniform in
-        ln gamma and n_mu nodes uniform in mu from -1 to +1."""
+        ln gamma and n_mu nodes uniform in mu from -1 to +1.  With sin_k, fn gives the smooth remainder n / sin^k xi."""
         gamma = np.exp(np.linspace(math.log(gamma_lo), math.log(gamma_hi), int(n_nodes)))
         gamma[0], gamma[-1] = gamma_lo, gamma_hi
         mu = np.linspace(-1.0, 1.0, int(n_mu))
         n = np.broadcast_to(np.asarray(fn(gamma[:, None], mu[None, :]), dtype=np.float64), (int(n_nodes), int(n_mu)))
-        return cls(gamma_lo, gamma_hi, np.log(n))
+        return cls(gamma_lo, gamma_hi, np.log(n), sin_k)
 
     def _install(self, ctx):
-        ctx.set_tables_2d(self.gamma_lo, self.gamma_hi, self.log_n)
+        ctx.set_tables_2d(self.gamma_lo, self.gamma_hi, self.log_n, self.sin_k)
         return ctx
 
 
@@ -901,26 +920,28 @@ class TabulatedDistribution2DGrid(TabulatedDistribution):
     """A distribution given as a surface on gamma nodes of its own: log_n [n_nodes][n_mu] = ln n(gamma_i, mu_j) at the
     strictly increasing gamma [n_nodes] and at mu nodes uniform from -1 to +1 (Context.set_tables_2d_grid);
     f = norm exp(S(ln gamma, mu)) / (gamma^2 beta) between the end nodes, 0 outside, S the tensor-product natural cubic
-    spline on the given nodes.  Installs its table whenever it computes, as TabulatedDistribution does."""
+    spline on the given nodes.  sin_k as for TabulatedDistribution2D.  Installs its table whenever it computes, as
+    TabulatedDistribution does."""
 
-    def __init__(self, gamma, log_n):
+    def __init__(self, gamma, log_n, sin_k=None):
         log_n = np.asarray(log_n, dtype=np.float64)
         if log_n.ndim != 2:
             raise ValueError("log_n: expected one table, [n_nodes][n_mu]")
         self.gamma, self.log_n = check_tables_2d_grid(gamma, log_n)
         self.gamma_lo, self.gamma_hi = float(self.gamma[0]), float(self.gamma[-1])
+        self.sin_k = None if sin_k is None else check_sin_k(sin_k, 1)
 
     @classmethod
-    def from_function(cls, fn, gamma, n_mu=65):
+    def from_function(cls, fn, gamma, n_mu=65, sin_k=None):
         """Tabulate n(gamma, mu) = fn(gamma[:, None], mu[None, :]) (vectorised, positive) at the given gamma nodes and
-        n_mu nodes uniform in mu from -1 to +1."""
+        n_mu nodes uniform in mu from -1 to +1.  With sin_k, fn gives the smooth remainder n / sin^k xi."""
         gamma = np.asarray(gamma, dtype=np.float64)
         mu = np.linspace(-1.0, 1.0, int(n_mu))
         n = np.broadcast_to(np.asarray(fn(gamma[:, None], mu[None, :]), dtype=np.float64), (gamma.shape[0], int(n_mu)))
-        return cls(gamma, np.log(n))
+        return cls(gamma, np.log(n), sin_k)
 
     def _install(self, ctx):
-        ctx.set_tables_2d_grid(self.gamma, self.log_n)
+        ctx.set_tables_2d_grid(self.gamma, self.log_n, self.sin_k)
         return ctx
 
 

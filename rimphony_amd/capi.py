@@ -22,6 +22,7 @@ SYMBOLS = [
     "rimphony_rccl_comm_create", "rimphony_rccl_comm_destroy", "rimphony_rccl_gather_table",
     "rimphony_ctx_set_tables", "rimphony_ctx_set_tables_pitch", "rimphony_ctx_set_tables_2d", "rimphony_ctx_set_tables_pitchy",
     "rimphony_ctx_set_tables_grid", "rimphony_ctx_set_tables_2d_grid",
+    "rimphony_ctx_set_tables_2d_pitchy", "rimphony_ctx_set_tables_2d_grid_pitchy",
 ]
 
 
@@ -162,6 +163,12 @@ def load():
     if hasattr(lib, "rimphony_ctx_set_tables_2d_grid"):
         lib.rimphony_ctx_set_tables_2d_grid.restype = c_int
         lib.rimphony_ctx_set_tables_2d_grid.argtypes = [c_void_p, c_size_t, c_size_t, dp, c_size_t, dp]
+    if hasattr(lib, "rimphony_ctx_set_tables_2d_pitchy"):
+        lib.rimphony_ctx_set_tables_2d_pitchy.restype = c_int
+        lib.rimphony_ctx_set_tables_2d_pitchy.argtypes = [c_void_p, c_size_t, c_size_t, c_double, c_double, c_size_t, dp, dp]
+    if hasattr(lib, "rimphony_ctx_set_tables_2d_grid_pitchy"):
+        lib.rimphony_ctx_set_tables_2d_grid_pitchy.restype = c_int
+        lib.rimphony_ctx_set_tables_2d_grid_pitchy.argtypes = [c_void_p, c_size_t, c_size_t, dp, c_size_t, dp, dp]
     if hasattr(lib, "rimphony_ctx_set_tables_grid"):
         lib.rimphony_ctx_set_tables_grid.restype = c_int
         lib.rimphony_ctx_set_tables_grid.argtypes = [c_void_p, c_size_t, c_size_t, dp, dp, c_size_t, dp, dp]

@@ -34,12 +34,21 @@ enum { DIST_POWER_LAW = 0, DIST_THERMAL_JUETTNER = 1, DIST_PITCHY_PL = 2, DIST_P
        DIST_TABULATED_GRID = 8,
        // nor this one: the tabulated kind where the set is a 2-D one on given gamma nodes (rim_tab_build_2d_grid): the surface
        // of DIST_TABULATED_2D, the lookup of DIST_TABULATED_GRID.
-       DIST_TABULATED_2D_GRID = 9 };
+       DIST_TABULATED_2D_GRID = 9,
+       // nor these two: the 2-D forms where every table carries a sin^k xi prefactor (rim_tab_build_2d with sin_k), k a word
+       // of the table's header (TAB_2D_K): f = norm sin^k xi exp(S) / (gamma^2 beta).  The surface and the lookup of
+       // DIST_TABULATED_2D and of DIST_TABULATED_2D_GRID; those two keep the code they always ran.
+       DIST_TABULATED_2D_PITCHY = 10, DIST_TABULATED_2D_GRID_PITCHY = 11 };
 constexpr bool dist_is_tab(int kind)
 {
     return kind == DIST_TABULATED || kind == DIST_TABULATED_ISO || kind == DIST_TABULATED_2D || kind == DIST_TABULATED_PITCHY ||
-        kind == DIST_TABULATED_GRID || kind == DIST_TABULATED_2D_GRID;
+        kind == DIST_TABULATED_GRID || kind == DIST_TABULATED_2D_GRID || kind == DIST_TABULATED_2D_PITCHY ||
+        kind == DIST_TABULATED_2D_GRID_PITCHY;
 }
+// the 2-D forms: on nodes uniform in ln gamma, on given nodes, and which of them carry a sin^k prefactor
+constexpr bool tab_kind_2d_uniform(int kind) { return kind == DIST_TABULATED_2D || kind == DIST_TABULATED_2D_PITCHY; }
+constexpr bool tab_kind_2d_on_grid(int kind) { return kind == DIST_TABULATED_2D_GRID || kind == DIST_TABULATED_2D_GRID_PITCHY; }
+constexpr bool tab_kind_2d_pitchy(int kind) { return kind == DIST_TABULATED_2D_PITCHY || kind == DIST_TABULATED_2D_GRID_PITCHY; }
 enum { STOKES_I = 0, STOKES_Q = 1, STOKES_V = 2 };
 enum { COEFF_EMISSION = 0, COEFF_ABSORPTION = 1, COEFF_FARADAY = 2 };
 
@@ -68,8 +77,10 @@ enum { TAB_PITCH_LAST = 0, TAB_PITCH_INVH = 1, TAB_PITCH_H = 2, TAB_PITCH_P = 3,
 // come n_tables table headers of TAB_2D_HDR words {n_mu - 2, 1 / h_mu, h_mu, the table's normalisation, four spare words: a
 // table header is one 64-byte line and the node data stay aligned to one}, then [n_tables][n_nodes][n_mu][4] =
 // {S, S_u, S_mu, S_umu} of the tensor-product natural cubic spline S(u, mu) at the node, mu fastest: the nodes (i, j) and
-// (i, j + 1) are 64 contiguous bytes and a sample reads two such runs.
-enum { TAB_2D_LAST = 0, TAB_2D_INVH = 1, TAB_2D_H = 2, TAB_2D_NORM = 3, TAB_2D_HDR = 8 };
+// (i, j + 1) are 64 contiguous bytes and a sample reads two such runs.  A set with a sin^k xi prefactor keeps the table's k
+// in the first of the spare words, TAB_2D_K (0 as built without one: only DIST_TABULATED_2D_PITCHY and
+// DIST_TABULATED_2D_GRID_PITCHY read it).
+enum { TAB_2D_LAST = 0, TAB_2D_INVH = 1, TAB_2D_H = 2, TAB_2D_NORM = 3, TAB_2D_K = 4, TAB_2D_HDR = 8 };
 RIM_DEV bool tab_set_is_2d(const double *hdr) { return hdr[TAB_HDR_NMU] < 0.; }
 // A set with a sin^k xi prefactor (rim_tab_build_pitchy): header and gamma rows as ever, TAB_HDR_NMU = n_mu (0: no g), then
 // per table TAB_PITCHY_PRE words {k, n_mu, two spare} and, straight behind them, what a pitch row is: TAB_PITCH_HDR words
@@ -137,7 +148,7 @@ RIM_DEV void dist_prepare(DistParams &d, double norm)
         const bool ok = tab_row_ok(hdr, d.par[0]);
         const size_t nn = (size_t) hdr[TAB_HDR_NNODES];
         const size_t row = ok ? (size_t) d.par[0] : 0;
-        if (KIND == DIST_TABULATED_2D) {
+        if (tab_kind_2d_uniform(KIND)) {
             // a 2-D set: par[0] the address of the table's header (the mu geometry, as a pitch row's), par[1] that of its
             // node data; the rest as for the other two forms
             const size_t nt = (size_t) hdr[TAB_HDR_NTABLES], nmu2 = (size_t) -hdr[TAB_HDR_NMU];
@@ -152,7 +163,7 @@ RIM_DEV void dist_prepare(DistParams &d, double norm)
             d.norm = ok ? norm : RIM_NAN;
             return;
         }
-        if (KIND == DIST_TABULATED_2D_GRID) {
+        if (tab_kind_2d_on_grid(KIND)) {
             // a 2-D set on given nodes: par[0] the table's header and par[1] its node data, as for a 2-D set; par[2] the
             // address of the set's u nodes (u_0 is their first word), par[3] 1 / (cell width), par[4] the index of the last
             // guide cell; inv_gamma_cutoff the bit pattern of the guide's address, as for a set on given nodes
@@ -274,7 +285,7 @@ RIM_DEV bool tab_kind_has_pitch(const DistParams &d)
     // (a 2-D table and one with a sin^k prefactor always have a live d f / d mu: they take the general forms, as a pitch
     // row does)
     return KIND == DIST_TABULATED_2D || KIND == DIST_TABULATED_PITCHY || KIND == DIST_TABULATED_GRID ||
-        KIND == DIST_TABULATED_2D_GRID ||
+        KIND == DIST_TABULATED_2D_GRID || tab_kind_2d_pitchy(KIND) ||
         (KIND != DIST_TABULATED_ISO && tab_has_pitch(d));
 }
 
@@ -455,7 +466,13 @@ RIM_DEV void tab_bicubic_grid(const DistParams &d, double gamma, double mu, doub
 
 // nbar(gamma) = 1/2 int exp(S(ln gamma, mu)) dmu of a 2-D table: the integrand of its normalisation.  The 31-point Kronrod
 // rule (xgk, wgk: gk31_table.h) on every mu cell, summed in node order -- the rule P of a pitch row uses.  KIND: the form
-// of the set, DIST_TABULATED_2D or DIST_TABULATED_2D_GRID.
+// of the set, one of the four 2-D forms.
+//
+// With a sin^k prefactor nbar = 1/2 int (1 - mu^2)^(k/2) exp(S) dmu, and the derivative of the integrand is singular at mu =
+// +-1 for a non-integer k or k < 2: the plain rule on an end cell is left with 4e-6 at k = 0.5 on 8 nodes.  The two end
+// cells are integrated under 1 - |mu| = omega = h v^4, v in [0, 1] on the same 31 nodes, Jacobian 4 h v^3: the integrand in
+// v goes as v^(2k+3) and the rule is at rounding for every k.  omega travels next to the node, so that sin^2 xi = omega (2 -
+// omega) is formed without cancellation.  Interior cells keep the plain rule with the factor as tab_calc_f_both forms it.
 template <int KIND = DIST_TABULATED_2D>
 RIM_DEV double tab_2d_norm_integrand(const DistParams &d, double g, const double *xgk, const double *wgk)
 {
@@ -463,6 +480,38 @@ RIM_DEV double tab_2d_norm_integrand(const DistParams &d, double g, const double
     const long long cells = (long long) th[TAB_2D_LAST] + 1;
     const double h = th[TAB_2D_H];
     double sum = 0.;
+    if (tab_kind_2d_pitchy(KIND)) {
+        const double sk = th[TAB_2D_K];
+        for (long long j = 0; j < cells; j++) {
+            const double half = 0.5 * h, centre = -1. + ((double) j + 0.5) * h;
+#if defined(RIM_TAB_2D_PITCHY_PLAIN_ENDS)
+            const bool end = false;         // (a private build of the tests: what the plain rule leaves on the end cells)
+#else
+            const bool end = j == 0 || j == cells - 1;
+#endif
+            double acc = 0.;
+            for (int k = 0; k < 31; k++) {
+                double sval, dsdu, dsdmu, mu, sin2, jac;
+                if (end) {
+                    const double v = 0.5 + 0.5 * xgk[k];
+                    const double v2 = v * v;
+                    const double omega = h * (v2 * v2);
+                    mu = j == 0 ? -1. + omega : 1. - omega;
+                    sin2 = omega * (2. - omega);
+                    jac = 4. * (v2 * v);            // (times h / 2 below: dmu = 4 h v^3 dv, dv = 1/2 dx)
+                } else {
+                    mu = centre + half * xgk[k];
+                    sin2 = 1. - mu * mu;
+                    jac = 1.;
+                }
+                if (tab_kind_2d_on_grid(KIND)) tab_bicubic_grid(d, g, mu, sval, dsdu, dsdmu);
+                else tab_bicubic(d, g, mu, sval, dsdu, dsdmu);
+                acc += wgk[k] * (jac * (RimMath<0>::pow(rim_sqrt(sin2), sk) * rim_exp(sval)));
+            }
+            sum += half * acc;
+        }
+        return 0.5 * sum;
+    }
     for (long long j = 0; j < cells; j++) {
         const double half = 0.5 * h, centre = -1. + ((double) j + 0.5) * h;
         double acc = 0.;
@@ -494,6 +543,23 @@ RIM_DEV void tab_calc_f_both(const DistParams &d, double gamma, double cos_xi, d
         f = d.norm * rim_exp(sval) / (gamma * gamma * beta2);
         dfdg = f * (dsdu / gamma - 1. / gamma - gamma / (gamma * gamma - 1.));
         dfdcx = f * dsdmu;
+        return;
+    }
+    if (tab_kind_2d_pitchy(KIND)) {
+        // f = norm sin^k xi exp(S) / (gamma^2 beta), d f / d mu = f (S_mu - k mu / sin^2 xi): the factor and its term as the
+        // pitchy kinds and DIST_TABULATED_PITCHY form them, k a wave-uniform load from the table's header.  A mu a rounding
+        // beyond +-1 is a NaN here (the square root), where the plain 2-D forms extrapolate the end cell.
+        const double *th = (const double *) (uintptr_t) rim_bits(d.par[0]);
+        const double k = th[TAB_2D_K];
+        double sval, dsdu, dsdmu;
+        if (tab_kind_2d_on_grid(KIND)) tab_bicubic_grid(d, gamma, cos_xi, sval, dsdu, dsdmu);
+        else tab_bicubic(d, gamma, cos_xi, sval, dsdu, dsdmu);
+        const double sin_xi = rim_sqrt(1. - cos_xi * cos_xi);
+        const double pa_term = RimMath<0>::pow(sin_xi, k);
+        const double beta2 = rim_sqrt(1. - rim_div_moderate(1., gamma * gamma));
+        f = d.norm * pa_term * rim_exp(sval) / (gamma * gamma * beta2);
+        dfdg = f * (dsdu / gamma - 1. / gamma - gamma / (gamma * gamma - 1.));
+        dfdcx = f * (dsdmu - k * cos_xi / (sin_xi * sin_xi));
         return;
     }
     double hval, dhdu;

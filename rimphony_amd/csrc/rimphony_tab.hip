@@ -19,6 +19,8 @@
 // A 2-D set on given gamma nodes (DIST_TABULATED_2D_GRID) has its kernels in a unit of its own, rimphony_tab_2d_grid.hip, for the
 // reason the group kernels have theirs; the dispatches here hand the form on.  Its rows read their normalisation with
 // tab2d_row_norm_kernel, as a 2-D set's do.
+// The 2-D forms with a sin^k xi prefactor (DIST_TABULATED_2D_PITCHY, DIST_TABULATED_2D_GRID_PITCHY) likewise:
+// rimphony_tab_2d_pitchy.hip, rimphony_tab_2d_grid_pitchy.hip.
 #include <hip/hip_runtime.h>
 #include "coop_kernel.h"
 #include "tab_launch.h"
@@ -114,6 +116,8 @@ RimCoopKernelInfo rim_tab_coop_kernel(int problem, int tab_kind)
     return rim_with_tab_kind(tab_kind, [&](auto K) {
         constexpr int KIND = decltype(K)::value;
         if constexpr (KIND == DIST_TABULATED_2D_GRID) return rim_tab_2d_grid_coop_kernel(problem);
+        else if constexpr (KIND == DIST_TABULATED_2D_PITCHY) return rim_tab_2d_pitchy_coop_kernel(problem);
+        else if constexpr (KIND == DIST_TABULATED_2D_GRID_PITCHY) return rim_tab_2d_grid_pitchy_coop_kernel(problem);
         else return problem ? coop_info<HeyvaertsProblem<KIND>>() : coop_info<SymphonyProblem<KIND>>();
     });
 }
@@ -125,7 +129,7 @@ void rim_tab_launch_norm(int tab_kind, unsigned grid, hipStream_t st, const Para
 {
     rim_with_tab_kind(tab_kind, [&](auto K) {
         constexpr int KIND = rim_tab_seam_kind(decltype(K)::value);
-        if constexpr (KIND == DIST_TABULATED_2D || KIND == DIST_TABULATED_2D_GRID)
+        if constexpr (tab_kind_2d_uniform(KIND) || tab_kind_2d_on_grid(KIND))
             hipLaunchKernelGGL(tab2d_row_norm_kernel, dim3((unsigned) ((n + 255) / 256)), dim3(256), RIM_DYN_LDS, st, pp, n, d_norm);
         else
             hipLaunchKernelGGL(norm_kernel<KIND>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pp, n, d_norm, queue, spill);
@@ -138,6 +142,8 @@ void rim_tab_launch_integrand(int tab_kind, unsigned grid, hipStream_t st, const
     rim_with_tab_kind(tab_kind, [&](auto K) {
         constexpr int KIND = rim_tab_seam_kind(decltype(K)::value);
         if constexpr (KIND == DIST_TABULATED_2D_GRID) rim_tab_2d_grid_launch_integrand(grid, st, pa, d_norm, count, d_n, d_gamma, d_out);
+        else if constexpr (KIND == DIST_TABULATED_2D_PITCHY) rim_tab_2d_pitchy_launch_integrand(grid, st, pa, d_norm, count, d_n, d_gamma, d_out);
+        else if constexpr (KIND == DIST_TABULATED_2D_GRID_PITCHY) rim_tab_2d_grid_pitchy_launch_integrand(grid, st, pa, d_norm, count, d_n, d_gamma, d_out);
         else hipLaunchKernelGGL(integrand_kernel_n<KIND>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pa, d_norm, count, d_n, d_gamma, d_out);
     });
 }
@@ -148,6 +154,8 @@ void rim_tab_launch_gamma_integral(int tab_kind, unsigned grid, hipStream_t st, 
     rim_with_tab_kind(tab_kind, [&](auto K) {
         constexpr int KIND = rim_tab_seam_kind(decltype(K)::value);
         if constexpr (KIND == DIST_TABULATED_2D_GRID) rim_tab_2d_grid_launch_gamma_integral(grid, st, pa, d_norm, count, d_n, d_out, spill);
+        else if constexpr (KIND == DIST_TABULATED_2D_PITCHY) rim_tab_2d_pitchy_launch_gamma_integral(grid, st, pa, d_norm, count, d_n, d_out, spill);
+        else if constexpr (KIND == DIST_TABULATED_2D_GRID_PITCHY) rim_tab_2d_grid_pitchy_launch_gamma_integral(grid, st, pa, d_norm, count, d_n, d_out, spill);
         else hipLaunchKernelGGL(gamma_integral_kernel<KIND>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pa, d_norm, count, d_n, d_out, spill);
     });
 }

@@ -29,6 +29,9 @@
 // the sweeps along u on the non-uniform system, the guide of a set on given nodes and one array of u nodes per set
 // (dev_symphony.h: tab_2d_grid_*).
 //
+// A 2-D set of either form may carry a sin^k xi prefactor per table (rim_tab_check_2d_pitchy, rim_tab_build_2d_pitchy and
+// their _grid_ counterparts): the form's blob with k in a spare word of each table's header (TAB_2D_K).
+//
 // Plain C++ with the elementary functions of detmath.h, so that the library (hipcc's host pass) and the tests' table
 // oracle (g++) produce the same bits from the same table.
 #ifndef RIM_TAB_SPLINE_H
@@ -434,6 +437,43 @@ inline void rim_tab_build_2d_grid(size_t n_tables, size_t n_nodes, const double 
             for (size_t i = 0; i < n_nodes; i++) nodes[(i * n_mu + j) * 4 + 3] = m[i];
         }
     }
+}
+
+// A 2-D set of either form with a sin^k xi prefactor per table: the form's own check and sin_k as rim_tab_check_sin_k
+// demands it; the form's own blob with k in the word TAB_2D_K of each table's header, which is 0 as the form builds it (the
+// table headers of both forms start TAB_HDR_DOUBLES words into the set).  The normalisation is 0 as built, as ever.
+inline int rim_tab_check_2d_pitchy(size_t n_tables, size_t n_nodes, double gamma_lo, double gamma_hi, size_t n_mu, const double *log_n,
+                                   const double *sin_k)
+{
+    if (rim_tab_check_2d(n_tables, n_nodes, gamma_lo, gamma_hi, n_mu, log_n) || !sin_k) return -1;
+    return rim_tab_check_sin_k(n_tables, sin_k);
+}
+
+inline int rim_tab_check_2d_grid_pitchy(size_t n_tables, size_t n_nodes, const double *gamma, size_t n_mu, const double *log_n,
+                                        const double *sin_k)
+{
+    if (rim_tab_check_2d_grid(n_tables, n_nodes, gamma, n_mu, log_n) || !sin_k) return -1;
+    return rim_tab_check_sin_k(n_tables, sin_k);
+}
+
+inline void rim_tab_put_2d_sin_k(size_t n_tables, const double *sin_k, std::vector<double> &blob)
+{
+    using namespace rim;
+    for (size_t t = 0; t < n_tables; t++) blob[(size_t) TAB_HDR_DOUBLES + t * TAB_2D_HDR + TAB_2D_K] = sin_k[t];
+}
+
+inline void rim_tab_build_2d_pitchy(size_t n_tables, size_t n_nodes, double gamma_lo, double gamma_hi, size_t n_mu,
+                                    const double *log_n, const double *sin_k, std::vector<double> &blob)
+{
+    rim_tab_build_2d(n_tables, n_nodes, gamma_lo, gamma_hi, n_mu, log_n, blob);
+    rim_tab_put_2d_sin_k(n_tables, sin_k, blob);
+}
+
+inline void rim_tab_build_2d_grid_pitchy(size_t n_tables, size_t n_nodes, const double *gamma, size_t n_mu, const double *log_n,
+                                         const double *sin_k, std::vector<double> &blob)
+{
+    rim_tab_build_2d_grid(n_tables, n_nodes, gamma, n_mu, log_n, blob);
+    rim_tab_put_2d_sin_k(n_tables, sin_k, blob);
 }
 
 #endif

@@ -117,6 +117,18 @@ public:
         check(rimphony_ctx_set_tables_2d(ctx_, n_tables, n_nodes, gamma_lo, gamma_hi, n_mu, n_tables ? log_n.data() : nullptr),
               "rimphony_ctx_set_tables_2d");
     }
+    // The same with a sin^k xi prefactor per table: sin_k [n_tables], each in [0, 100] (rimphony_ctx_set_tables_2d_pitchy);
+    // f = norm sin^k xi exp(S) / (gamma^2 beta), log_n the smooth remainder ln(n / sin^k xi).
+    void set_tables_2d(size_t n_tables, size_t n_nodes, double gamma_lo, double gamma_hi, size_t n_mu,
+                       const std::vector<double> &log_n, const std::vector<double> &sin_k) const
+    {
+        if (log_n.size() != n_tables * n_nodes * n_mu)
+            throw std::runtime_error("set_tables_2d: log_n must hold n_tables * n_nodes * n_mu values");
+        if (sin_k.size() != n_tables) throw std::runtime_error("set_tables_2d: sin_k must hold n_tables values");
+        check(rimphony_ctx_set_tables_2d_pitchy(ctx_, n_tables, n_nodes, gamma_lo, gamma_hi, n_mu, n_tables ? log_n.data() : nullptr,
+                                                n_tables ? sin_k.data() : nullptr),
+              "rimphony_ctx_set_tables_2d_pitchy");
+    }
     // A 2-D set on gamma nodes of the caller's choosing (rimphony_ctx_set_tables_2d_grid): gamma [n_nodes] strictly increasing
     // from >= 1, shared by the tables; log_n [n_tables][n_nodes][n_mu], mu fastest, the mu nodes uniform from -1 to +1.
     void set_tables_2d_grid(size_t n_tables, const std::vector<double> &gamma, size_t n_mu, const std::vector<double> &log_n) const
@@ -126,6 +138,17 @@ public:
         check(rimphony_ctx_set_tables_2d_grid(ctx_, n_tables, gamma.size(), n_tables ? gamma.data() : nullptr, n_mu,
                                               n_tables ? log_n.data() : nullptr),
               "rimphony_ctx_set_tables_2d_grid");
+    }
+    // The same with a sin^k xi prefactor per table, sin_k [n_tables] (rimphony_ctx_set_tables_2d_grid_pitchy).
+    void set_tables_2d_grid(size_t n_tables, const std::vector<double> &gamma, size_t n_mu, const std::vector<double> &log_n,
+                            const std::vector<double> &sin_k) const
+    {
+        if (log_n.size() != n_tables * gamma.size() * n_mu)
+            throw std::runtime_error("set_tables_2d_grid: log_n must hold n_tables * n_nodes * n_mu values");
+        if (sin_k.size() != n_tables) throw std::runtime_error("set_tables_2d_grid: sin_k must hold n_tables values");
+        check(rimphony_ctx_set_tables_2d_grid_pitchy(ctx_, n_tables, gamma.size(), n_tables ? gamma.data() : nullptr, n_mu,
+                                                     n_tables ? log_n.data() : nullptr, n_tables ? sin_k.data() : nullptr),
+              "rimphony_ctx_set_tables_2d_grid_pitchy");
     }
 private:
     rimphony_ctx *ctx_ = nullptr;
@@ -394,7 +417,14 @@ protected:
 public:
     TabulatedDistribution2D(double gamma_lo, double gamma_hi, size_t n_nodes, size_t n_mu, std::vector<double> log_n)
         : glo_(gamma_lo), ghi_(gamma_hi), n_nodes_(n_nodes), n_mu_(n_mu), log_n_(std::move(log_n)) {}
-    void install(const Context &ctx) const { ctx.set_tables_2d(1, n_nodes_, glo_, ghi_, n_mu_, log_n_); }
+    // ... times sin^k xi in closed form, 0 <= sin_k <= 100: log_n is the smooth remainder ln(n / sin^k xi)
+    TabulatedDistribution2D(double gamma_lo, double gamma_hi, size_t n_nodes, size_t n_mu, std::vector<double> log_n, double sin_k)
+        : glo_(gamma_lo), ghi_(gamma_hi), n_nodes_(n_nodes), n_mu_(n_mu), log_n_(std::move(log_n)), sin_k_{sin_k} {}
+    void install(const Context &ctx) const
+    {
+        if (sin_k_.empty()) ctx.set_tables_2d(1, n_nodes_, glo_, ghi_, n_mu_, log_n_);
+        else ctx.set_tables_2d(1, n_nodes_, glo_, ghi_, n_mu_, log_n_, sin_k_);
+    }
     double calc_f(const Context &ctx, double gamma, double cos_xi) const
     { install(ctx); return DistributionFunction::calc_f(ctx, gamma, cos_xi); }
     std::array<double, 2> calc_f_derivatives(const Context &ctx, double gamma, double cos_xi) const
@@ -407,7 +437,7 @@ public:
 private:
     double glo_, ghi_;
     size_t n_nodes_, n_mu_;
-    std::vector<double> log_n_;
+    std::vector<double> log_n_, sin_k_;
 };
 
 // A distribution given as a surface on gamma nodes of its own: log_n [n_nodes][n_mu], mu fastest, = ln n(gamma_i, mu_j) at
@@ -420,7 +450,14 @@ protected:
 public:
     TabulatedDistribution2DGrid(std::vector<double> gamma, size_t n_mu, std::vector<double> log_n)
         : gamma_(std::move(gamma)), n_mu_(n_mu), log_n_(std::move(log_n)) {}
-    void install(const Context &ctx) const { ctx.set_tables_2d_grid(1, gamma_, n_mu_, log_n_); }
+    // ... times sin^k xi in closed form, as TabulatedDistribution2D takes it
+    TabulatedDistribution2DGrid(std::vector<double> gamma, size_t n_mu, std::vector<double> log_n, double sin_k)
+        : gamma_(std::move(gamma)), n_mu_(n_mu), log_n_(std::move(log_n)), sin_k_{sin_k} {}
+    void install(const Context &ctx) const
+    {
+        if (sin_k_.empty()) ctx.set_tables_2d_grid(1, gamma_, n_mu_, log_n_);
+        else ctx.set_tables_2d_grid(1, gamma_, n_mu_, log_n_, sin_k_);
+    }
     double calc_f(const Context &ctx, double gamma, double cos_xi) const
     { install(ctx); return DistributionFunction::calc_f(ctx, gamma, cos_xi); }
     std::array<double, 2> calc_f_derivatives(const Context &ctx, double gamma, double cos_xi) const
@@ -433,7 +470,7 @@ public:
 private:
     std::vector<double> gamma_;
     size_t n_mu_;
-    std::vector<double> log_n_;
+    std::vector<double> log_n_, sin_k_;
 };
 
 // A distribution given as a table on gamma nodes of its own: log_n [n_nodes] = ln n at the strictly increasing gamma
