@@ -291,7 +291,8 @@ int rimphony_ctx_set_tables_grid(rimphony_ctx *ctx, size_t n_tables, size_t n_no
  * whose quadrature fails has a NaN normalisation and its rows are NaN with RIMPHONY_ST_NORM_FAIL, the other tables are
  * unaffected.  A row is still RIMPHONY_TABULATED with one parameter, the table index.  Everything else -- a bad index, the
  * precisions and closed forms refused, the _multi entries, RIMPHONY_TAB_GROUP (this form follows the 2-D form's default) -- is
- * as for rimphony_ctx_set_tables_2d.  Not offered: mu nodes of the caller's choosing, a grid per table. */
+ * as for rimphony_ctx_set_tables_2d.  mu nodes of the caller's choosing: rimphony_ctx_set_tables_2d_nodes below.  Not offered:
+ * a grid per table. */
 int rimphony_ctx_set_tables_2d_grid(rimphony_ctx *ctx, size_t n_tables, size_t n_nodes, const double *gamma, size_t n_mu,
                                     const double *log_n);
 
@@ -315,11 +316,46 @@ int rimphony_ctx_set_tables_2d_grid(rimphony_ctx *ctx, size_t n_tables, size_t n
  * |mu| = h v^4, which takes the singular derivative of the factor at mu = +-1 out of the integrand for every k (DESIGN.md
  * section 5).  A table whose quadrature fails has a NaN normalisation and its rows are NaN with RIMPHONY_ST_NORM_FAIL.
  * A row is still RIMPHONY_TABULATED with one parameter, the table index; RIMPHONY_TAB_GROUP follows the 2-D form's default.
- * Not offered: mu nodes of the caller's choosing, a grid per table, an exponent per row. */
+ * mu nodes of the caller's choosing: rimphony_ctx_set_tables_2d_nodes below.  Not offered: a grid per table, an exponent per
+ * row. */
 int rimphony_ctx_set_tables_2d_pitchy(rimphony_ctx *ctx, size_t n_tables, size_t n_nodes, double gamma_lo, double gamma_hi,
                                       size_t n_mu, const double *log_n, const double *sin_k);
 int rimphony_ctx_set_tables_2d_grid_pitchy(rimphony_ctx *ctx, size_t n_tables, size_t n_nodes, const double *gamma, size_t n_mu,
                                            const double *log_n, const double *sin_k);
+
+/* Tabulated distributions as 2-D surfaces on gamma nodes AND mu nodes of the caller's choosing, with or without a sin^k xi
+ * prefactor: what the 2-D forms above hold, for an anisotropy that nodes uniform in mu cannot resolve within 1024 of them --
+ * a pitch-angle histogram with bins uniform in xi (finest at mu = +-1, where a uniform mu grid is coarsest in angle), a
+ * field-aligned beam, a ring at one pitch angle, the edge of a loss cone.
+ * f(gamma, mu) = norm sin^k xi exp(S(ln gamma, mu)) / (gamma^2 beta) inside [gamma[0], gamma[n_nodes - 1]], +0 outside;
+ * df/dgamma and df/dmu as for the 2-D forms.
+ *   gamma   HOST, [n_nodes]: exactly as for rimphony_ctx_set_tables_2d_grid (nodes uniform in ln gamma are simply passed in);
+ *   mu      HOST, [n_mu], shared by the tables of the set: 8 <= n_mu <= 1024, n_nodes n_mu <= 2^20, every value finite and
+ *           strictly increasing, mu[0] == -1.0 and mu[n_mu - 1] == +1.0 exactly -- the surface covers the whole range, and the
+ *           normalisation needs no extrapolation;
+ *   log_n   HOST, [n_tables][n_nodes][n_mu], mu fastest: ln n (with sin_k: of the smooth remainder n / sin^k xi) at (gamma_i,
+ *           mu_j), every value finite;
+ *   sin_k   NULL, or HOST [n_tables], each finite with 0 <= k <= 100, with the semantics of the _2d*_pitchy entries: a mu a
+ *           rounding beyond +-1 is NaN, df/dmu is NaN at |mu| = 1.  sin_k == NULL is the plain function: the end cell
+ *           extrapolates for a mu a rounding beyond +-1, a NaN gives NaN.
+ * Anything else -- a null pointer, a non-finite value, mu not strictly increasing, wrong end nodes, a bad n_mu, gamma, log_n or
+ * sin_k -- is RIMPHONY_EINVAL, checked on the host before any lock or HIP call, and the previous set stays; so it does when
+ * a device allocation fails (RIMPHONY_ENOMEM).  n_tables = 0 clears the set.  The call replaces a set of any form and a set
+ * of any form replaces it.
+ * S is the tensor-product natural cubic spline through the data at (rim_log(gamma_i), mu_j), solved on the host on both
+ * non-uniform node sets, evaluated as a bicubic on the cell with the cell's own widths.  A surface bilinear in (ln gamma, mu)
+ * comes back as itself on any node set; on mu nodes -1 + j 2 / (n_mu - 1) the form gives what rimphony_ctx_set_tables_2d_grid
+ * (and, with sin_k, rimphony_ctx_set_tables_2d_grid_pitchy) gives, in other arithmetic: agreement to rounding, not to the bit.
+ * A sample finds its mu interval as it finds its gamma interval: the largest j <= n_mu - 2 with mu_j <= mu (0 where there is
+ * none or mu is a NaN), through two words of a guide over cells uniform in mu and a bisection of at most 10 node words.
+ * The normalisation of each table is integrated once, on the device, when the set is installed: the 31-point Kronrod rule
+ * on every mu cell with that cell's centre and half width and, under sin^k, the two end cells under 1 - |mu| = h v^4 with h
+ * the end cell's own width.  A table whose quadrature fails has a NaN normalisation and its rows are NaN with
+ * RIMPHONY_ST_NORM_FAIL.  A row is still RIMPHONY_TABULATED with one parameter, the table index; a bad index, the refused
+ * precision, the refused closed forms and the _multi entries behave as for the 2-D forms; RIMPHONY_TAB_GROUP follows the 2-D
+ * form's default.  Not offered: a grid per table, an exponent per row. */
+int rimphony_ctx_set_tables_2d_nodes(rimphony_ctx *ctx, size_t n_tables, size_t n_nodes, const double *gamma, size_t n_mu,
+                                     const double *mu, const double *log_n, const double *sin_k);
 
 /* Work counters of the most recent batch call on this context (device-side
  * counts, read back synchronously): integrand samples, wave-wide evaluation

@@ -163,6 +163,17 @@ extern "C" {
         sin_k: *const c_double,
     ) -> c_int;
 
+    pub fn rimphony_ctx_set_tables_2d_nodes(
+        ctx: *mut rimphony_ctx,
+        n_tables: usize,
+        n_nodes: usize,
+        gamma: *const c_double,
+        n_mu: usize,
+        mu: *const c_double,
+        log_n: *const c_double,
+        sin_k: *const c_double,
+    ) -> c_int;
+
     pub fn rimphony_last_work(ctx: *mut rimphony_ctx, out: *mut rimphony_work) -> c_int;
     pub fn rimphony_last_tail(ctx: *mut rimphony_ctx, out: *mut u64) -> c_int;
     pub fn rimphony_last_symphony_ms(ctx: *mut rimphony_ctx, ms: *mut c_float) -> c_int;
@@ -420,6 +431,28 @@ impl HipContext {
             rimphony_ctx_set_tables_2d_grid_pitchy(
                 self.raw, sin_k.len(), n_nodes, gamma.as_ptr(), n_mu, log_n.as_ptr(), sin_k.as_ptr(),
             )
+        };
+        if rc != RIMPHONY_OK {
+            return Err(error_text(rc));
+        }
+        Ok(())
+    }
+
+    /// A 2-D table set on gamma nodes and mu nodes of the caller's choosing: `mu` holds the strictly increasing nodes from
+    /// exactly -1 to exactly +1, shared by the tables; `sin_k` is empty for the plain form or holds one exponent in [0, 100]
+    /// per surface (include/rimphony_hip.h: rimphony_ctx_set_tables_2d_nodes).
+    pub fn set_tables_2d_nodes(&self, gamma: &[f64], mu: &[f64], log_n: &[f64], sin_k: &[f64]) -> Result<(), String> {
+        let (n_nodes, n_mu) = (gamma.len(), mu.len());
+        if n_nodes == 0 || n_mu == 0 || log_n.len() % (n_nodes * n_mu) != 0 {
+            return Err(error_text(RIMPHONY_EINVAL));
+        }
+        let n_tables = log_n.len() / (n_nodes * n_mu);
+        if !sin_k.is_empty() && sin_k.len() != n_tables {
+            return Err(error_text(RIMPHONY_EINVAL));
+        }
+        let k = if sin_k.is_empty() { std::ptr::null() } else { sin_k.as_ptr() };
+        let rc = unsafe {
+            rimphony_ctx_set_tables_2d_nodes(self.raw, n_tables, n_nodes, gamma.as_ptr(), n_mu, mu.as_ptr(), log_n.as_ptr(), k)
         };
         if rc != RIMPHONY_OK {
             return Err(error_text(rc));

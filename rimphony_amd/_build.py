@@ -75,6 +75,9 @@ def build_hip(force=False, verbose=False):
                                     os.path.join(CSRC, "rimphony_tab_2d_pitchy.hip"), os.path.join(CSRC, "rimphony_tab_2d_pitchy_group.hip"),
                                     os.path.join(CSRC, "rimphony_tab_2d_grid_pitchy.hip"),
                                     os.path.join(CSRC, "rimphony_tab_2d_grid_pitchy_group.hip"),
+                                    os.path.join(CSRC, "rimphony_tab_2d_nodes.hip"), os.path.join(CSRC, "rimphony_tab_2d_nodes_group.hip"),
+                                    os.path.join(CSRC, "rimphony_tab_2d_nodes_pitchy.hip"),
+                                    os.path.join(CSRC, "rimphony_tab_2d_nodes_pitchy_group.hip"),
                                     "-ldl", "-o", LIB]
     if verbose:
         print(" ".join(cmd))
@@ -183,6 +186,12 @@ def build_tab2d_pitchy_oracle():
     """The same for 2-D table sets with a sin^k xi prefactor per table, on nodes uniform in ln gamma or given
     (tests/support/tab2d_pitchy_oracle.cpp)."""
     return _build_dist_oracle("tab2d_pitchy_oracle.cpp", "liboracle_tab2dpitchy.so")
+
+
+def build_tab2d_nodes_oracle():
+    """The same for 2-D table sets on gamma nodes and mu nodes of the caller's choosing, with or without a sin^k xi
+    prefactor (tests/support/tab2d_nodes_oracle.cpp)."""
+    return _build_dist_oracle("tab2d_nodes_oracle.cpp", "liboracle_tab2dnodes.so")
 
 
 def build_pitchy_tilt_oracle():

@@ -197,6 +197,35 @@ def check_tables_2d_grid(gamma, log_n):
     return g, t
 
 
+def mu_nodes_uniform_in_xi(n):
+    """n mu nodes uniform in the pitch angle xi, mu_j = -cos(pi j / (n - 1)), the ends exactly -1 and +1: the nodes of a
+    pitch-angle histogram with bins uniform in xi, densest where a grid uniform in mu is coarsest in angle
+    (Context.set_tables_2d_nodes)."""
+    n = int(n)
+    if n < 2:
+        raise ValueError("mu_nodes_uniform_in_xi: expected at least two nodes")
+    mu = -np.cos(np.pi * np.arange(n) / (n - 1))
+    mu[0], mu[-1] = -1.0, 1.0
+    return mu
+
+
+def check_tables_2d_nodes(gamma, mu, log_n):
+    """A 2-D table set on given gamma and mu nodes as rimphony_ctx_set_tables_2d_nodes accepts it -> (gamma, mu, log_n),
+    contiguous float64 [n_nodes], [n_mu] and [n_tables][n_nodes][n_mu] (a 2-D array is one table); ValueError for what the
+    library refuses with RIMPHONY_EINVAL."""
+    m = np.ascontiguousarray(np.asarray(mu, dtype=np.float64))
+    if m.ndim != 1 or not TAB_2D_MIN_MU <= m.shape[0] <= TAB_2D_MAX_MU:
+        raise ValueError("mu: expected %d to %d nodes, got shape %r" % (TAB_2D_MIN_MU, TAB_2D_MAX_MU, m.shape))
+    if not np.isfinite(m).all() or not (np.diff(m) > 0.0).all():
+        raise ValueError("mu: the nodes must be finite and strictly increasing")
+    if m[0] != -1.0 or m[-1] != 1.0:
+        raise ValueError("mu: the first node must be -1 and the last +1 exactly")
+    g, t = check_tables_2d_grid(gamma, log_n)
+    if t.shape[2] != m.shape[0]:
+        raise ValueError("log_n: expected rows of %d values, one per mu node, got %d" % (m.shape[0], t.shape[2]))
+    return g, m, t
+
+
 class Context:
     """Owns a rimphony_ctx bound to one GPU."""
 
@@ -331,6 +360,25 @@ class Context:
                    "rimphony_ctx_set_tables_2d_grid")
 
     # -- batched compute() -------------------------------------------------------
+    def set_tables_2d_nodes(self, gamma, mu, log_n, sin_k=None):
+        """The context's table set as surfaces on gamma nodes AND mu nodes of the caller's choosing: gamma [n_nodes] strictly
+        increasing from >= 1 and mu [n_mu] strictly increasing from exactly -1 to exactly +1, both shared by the tables;
+        log_n [n_tables][n_nodes][n_mu] (a 2-D array is one table) = ln n(gamma_i, mu_j).  What set_tables_2d_grid holds, on
+        mu nodes graded towards a beam, a ring or the edge of a loss cone, or uniform in xi (mu_nodes_uniform_in_xi).
+        sin_k as for set_tables_2d.  Replaces the previous set of any form; log_n None clears it.  Synchronous: the
+        normalisation of every table is integrated here, once (include/rimphony_hip.h: rimphony_ctx_set_tables_2d_nodes)."""
+        if log_n is None:
+            capi.check(self.lib.rimphony_ctx_set_tables_2d_nodes(self.handle, 0, 0, None, 0, None, None, None),
+                       "rimphony_ctx_set_tables_2d_nodes")
+            return
+        g, m, t = check_tables_2d_nodes(gamma, mu, log_n)
+        k = None if sin_k is None else check_sin_k(sin_k, t.shape[0])
+        dp = ctypes.POINTER(ctypes.c_double)
+        capi.check(self.lib.rimphony_ctx_set_tables_2d_nodes(self.handle, t.shape[0], t.shape[1], g.ctypes.data_as(dp), t.shape[2],
+                                                             m.ctypes.data_as(dp), t.ctypes.data_as(dp),
+                                                             None if k is None else k.ctypes.data_as(dp)),
+                   "rimphony_ctx_set_tables_2d_nodes")
+
     def _check_input(self, name, t, n):
         """The C ABI takes raw device pointers and cannot see what they point to: refuse anything but a contiguous
         float64 tensor of n elements on this context's GPU (a strided view, a float32 tensor, a tensor on another
@@ -942,6 +990,35 @@ class TabulatedDistribution2DGrid(TabulatedDistribution):
 
     def _install(self, ctx):
         ctx.set_tables_2d_grid(self.gamma, self.log_n, self.sin_k)
+        return ctx
+
+
+class TabulatedDistribution2DNodes(TabulatedDistribution):
+    """A distribution given as a surface on gamma nodes and mu nodes of its own: log_n [n_nodes][n_mu] = ln n(gamma_i,
+    mu_j) at the strictly increasing gamma [n_nodes] and mu [n_mu], mu from exactly -1 to exactly +1
+    (Context.set_tables_2d_nodes); f = norm exp(S(ln gamma, mu)) / (gamma^2 beta) between the end gamma nodes, 0 outside,
+    S the tensor-product natural cubic spline on the given nodes.  sin_k as for TabulatedDistribution2D.  Installs its
+    table whenever it computes, as TabulatedDistribution does."""
+
+    def __init__(self, gamma, mu, log_n, sin_k=None):
+        log_n = np.asarray(log_n, dtype=np.float64)
+        if log_n.ndim != 2:
+            raise ValueError("log_n: expected one table, [n_nodes][n_mu]")
+        self.gamma, self.mu, self.log_n = check_tables_2d_nodes(gamma, mu, log_n)
+        self.gamma_lo, self.gamma_hi = float(self.gamma[0]), float(self.gamma[-1])
+        self.sin_k = None if sin_k is None else check_sin_k(sin_k, 1)
+
+    @classmethod
+    def from_function(cls, fn, gamma, mu, sin_k=None):
+        """Tabulate n(gamma, mu) = fn(gamma[:, None], mu[None, :]) (vectorised, positive) at the given gamma and mu nodes.
+        With sin_k, fn gives the smooth remainder n / sin^k xi."""
+        gamma = np.asarray(gamma, dtype=np.float64)
+        mu = np.asarray(mu, dtype=np.float64)
+        n = np.broadcast_to(np.asarray(fn(gamma[:, None], mu[None, :]), dtype=np.float64), (gamma.shape[0], mu.shape[0]))
+        return cls(gamma, mu, np.log(n), sin_k)
+
+    def _install(self, ctx):
+        ctx.set_tables_2d_nodes(self.gamma, self.mu, self.log_n, self.sin_k)
         return ctx
 
 

@@ -22,7 +22,7 @@ SYMBOLS = [
     "rimphony_rccl_comm_create", "rimphony_rccl_comm_destroy", "rimphony_rccl_gather_table",
     "rimphony_ctx_set_tables", "rimphony_ctx_set_tables_pitch", "rimphony_ctx_set_tables_2d", "rimphony_ctx_set_tables_pitchy",
     "rimphony_ctx_set_tables_grid", "rimphony_ctx_set_tables_2d_grid",
-    "rimphony_ctx_set_tables_2d_pitchy", "rimphony_ctx_set_tables_2d_grid_pitchy",
+    "rimphony_ctx_set_tables_2d_pitchy", "rimphony_ctx_set_tables_2d_grid_pitchy", "rimphony_ctx_set_tables_2d_nodes",
 ]
 
 
@@ -169,6 +169,9 @@ def load():
     if hasattr(lib, "rimphony_ctx_set_tables_2d_grid_pitchy"):
         lib.rimphony_ctx_set_tables_2d_grid_pitchy.restype = c_int
         lib.rimphony_ctx_set_tables_2d_grid_pitchy.argtypes = [c_void_p, c_size_t, c_size_t, dp, c_size_t, dp, dp]
+    if hasattr(lib, "rimphony_ctx_set_tables_2d_nodes"):
+        lib.rimphony_ctx_set_tables_2d_nodes.restype = c_int
+        lib.rimphony_ctx_set_tables_2d_nodes.argtypes = [c_void_p, c_size_t, c_size_t, dp, c_size_t, dp, dp, dp]
     if hasattr(lib, "rimphony_ctx_set_tables_grid"):
         lib.rimphony_ctx_set_tables_grid.restype = c_int
         lib.rimphony_ctx_set_tables_grid.argtypes = [c_void_p, c_size_t, c_size_t, dp, dp, c_size_t, dp, dp]

@@ -38,17 +38,26 @@ enum { DIST_POWER_LAW = 0, DIST_THERMAL_JUETTNER = 1, DIST_PITCHY_PL = 2, DIST_P
        // nor these two: the 2-D forms where every table carries a sin^k xi prefactor (rim_tab_build_2d with sin_k), k a word
        // of the table's header (TAB_2D_K): f = norm sin^k xi exp(S) / (gamma^2 beta).  The surface and the lookup of
        // DIST_TABULATED_2D and of DIST_TABULATED_2D_GRID; those two keep the code they always ran.
-       DIST_TABULATED_2D_PITCHY = 10, DIST_TABULATED_2D_GRID_PITCHY = 11 };
+       DIST_TABULATED_2D_PITCHY = 10, DIST_TABULATED_2D_GRID_PITCHY = 11,
+       // nor these two: the 2-D form on gamma nodes AND mu nodes of the caller's choosing (rim_tab_build_2d_nodes), without
+       // and with a sin^k xi prefactor.  The surface of the other 2-D forms, the gamma lookup of DIST_TABULATED_2D_GRID and the
+       // same kind of lookup along mu (tab_2d_nodes_mu_interval); the older forms keep the code they always ran.
+       DIST_TABULATED_2D_NODES = 12, DIST_TABULATED_2D_NODES_PITCHY = 13 };
 constexpr bool dist_is_tab(int kind)
 {
     return kind == DIST_TABULATED || kind == DIST_TABULATED_ISO || kind == DIST_TABULATED_2D || kind == DIST_TABULATED_PITCHY ||
         kind == DIST_TABULATED_GRID || kind == DIST_TABULATED_2D_GRID || kind == DIST_TABULATED_2D_PITCHY ||
-        kind == DIST_TABULATED_2D_GRID_PITCHY;
+        kind == DIST_TABULATED_2D_GRID_PITCHY || kind == DIST_TABULATED_2D_NODES || kind == DIST_TABULATED_2D_NODES_PITCHY;
 }
-// the 2-D forms: on nodes uniform in ln gamma, on given nodes, and which of them carry a sin^k prefactor
+// the 2-D forms: on nodes uniform in ln gamma, on given gamma nodes (mu uniform), on given gamma and mu nodes, and which of
+// them carry a sin^k prefactor
 constexpr bool tab_kind_2d_uniform(int kind) { return kind == DIST_TABULATED_2D || kind == DIST_TABULATED_2D_PITCHY; }
 constexpr bool tab_kind_2d_on_grid(int kind) { return kind == DIST_TABULATED_2D_GRID || kind == DIST_TABULATED_2D_GRID_PITCHY; }
-constexpr bool tab_kind_2d_pitchy(int kind) { return kind == DIST_TABULATED_2D_PITCHY || kind == DIST_TABULATED_2D_GRID_PITCHY; }
+constexpr bool tab_kind_2d_nodes(int kind) { return kind == DIST_TABULATED_2D_NODES || kind == DIST_TABULATED_2D_NODES_PITCHY; }
+constexpr bool tab_kind_2d_pitchy(int kind)
+{
+    return kind == DIST_TABULATED_2D_PITCHY || kind == DIST_TABULATED_2D_GRID_PITCHY || kind == DIST_TABULATED_2D_NODES_PITCHY;
+}
 enum { STOKES_I = 0, STOKES_Q = 1, STOKES_V = 2 };
 enum { COEFF_EMISSION = 0, COEFF_ABSORPTION = 1, COEFF_FARADAY = 2 };
 
@@ -78,9 +87,10 @@ enum { TAB_PITCH_LAST = 0, TAB_PITCH_INVH = 1, TAB_PITCH_H = 2, TAB_PITCH_P = 3,
 // table header is one 64-byte line and the node data stay aligned to one}, then [n_tables][n_nodes][n_mu][4] =
 // {S, S_u, S_mu, S_umu} of the tensor-product natural cubic spline S(u, mu) at the node, mu fastest: the nodes (i, j) and
 // (i, j + 1) are 64 contiguous bytes and a sample reads two such runs.  A set with a sin^k xi prefactor keeps the table's k
-// in the first of the spare words, TAB_2D_K (0 as built without one: only DIST_TABULATED_2D_PITCHY and
-// DIST_TABULATED_2D_GRID_PITCHY read it).
-enum { TAB_2D_LAST = 0, TAB_2D_INVH = 1, TAB_2D_H = 2, TAB_2D_NORM = 3, TAB_2D_K = 4, TAB_2D_HDR = 8 };
+// in the first of the spare words, TAB_2D_K (0 as built without one: only the kinds with a prefactor read it).  A set on
+// given mu nodes (tab_2d_nodes_* below) uses two more, TAB_2D_MU_GUIDE and TAB_2D_MU_NODES.
+enum { TAB_2D_LAST = 0, TAB_2D_INVH = 1, TAB_2D_H = 2, TAB_2D_NORM = 3, TAB_2D_K = 4, TAB_2D_MU_GUIDE = 5, TAB_2D_MU_NODES = 6,
+       TAB_2D_HDR = 8 };
 RIM_DEV bool tab_set_is_2d(const double *hdr) { return hdr[TAB_HDR_NMU] < 0.; }
 // A set with a sin^k xi prefactor (rim_tab_build_pitchy): header and gamma rows as ever, TAB_HDR_NMU = n_mu (0: no g), then
 // per table TAB_PITCHY_PRE words {k, n_mu, two spare} and, straight behind them, what a pitch row is: TAB_PITCH_HDR words
@@ -128,6 +138,30 @@ RIM_DEV size_t tab_2d_grid_nodes_at(size_t n_tables, size_t n_nodes, size_t cell
     return tab_2d_grid_guide_at(n_tables) + tab_grid_guide_doubles(cells) + tab_2d_grid_unode_doubles(n_nodes);
 }
 
+// A 2-D set on given gamma nodes and given mu nodes (rim_tab_build_2d_nodes): the layout of a 2-D set on given gamma nodes up
+// to and including the u nodes.  Then, where that form's node data begin, the mu guide -- M + 1 32-bit words padded to a
+// multiple of 64 bytes, M the smallest power of two >= n_mu (at least 8), the guide cells uniform in mu over [-1, +1], filled
+// and read as the u guide is (tab_grid_cell with u_0 = -1) -- and straight behind it the mu nodes of the set, [n_mu][2] =
+// {mu_j, 1 / h_j} (h_j = mu_{j+1} - mu_j; 0 at the last node), padded likewise.  Then [n_tables][n_nodes][n_mu][4] as in every
+// 2-D set.  A table header says TAB_2D_LAST = n_mu - 2 as ever, TAB_2D_INVH = 1 / (the width of a mu guide cell) = M / 2,
+// TAB_2D_H = M, and in TAB_2D_MU_GUIDE / TAB_2D_MU_NODES the distance in doubles from the header itself to the mu guide and
+// to the mu nodes: a row carries the address of its table's header and needs no further field.
+RIM_DEV size_t tab_2d_nodes_munode_doubles(size_t n_mu) { return (2 * n_mu + 7) & ~(size_t) 7; }
+RIM_DEV size_t tab_2d_nodes_mu_guide_at(size_t n_tables, size_t n_nodes, size_t cells)
+{
+    return tab_2d_grid_nodes_at(n_tables, n_nodes, cells);
+}
+RIM_DEV size_t tab_2d_nodes_nodes_at(size_t n_tables, size_t n_nodes, size_t cells, size_t n_mu, size_t mu_cells)
+{
+    return tab_2d_nodes_mu_guide_at(n_tables, n_nodes, cells) + tab_grid_guide_doubles(mu_cells) + tab_2d_nodes_munode_doubles(n_mu);
+}
+// (the tests' oracle counts the node words a mu search reads: RIM_TAB_2D_NODES_COUNT names its counter)
+#if defined(RIM_TAB_2D_NODES_COUNT)
+#define RIM_TAB_2D_NODES_READ() ((void) ++RIM_TAB_2D_NODES_COUNT)
+#else
+#define RIM_TAB_2D_NODES_READ() ((void) 0)
+#endif
+
 // is `idx` (par[0] of a row) the index of a table of the set?
 RIM_DEV bool tab_row_ok(const double *hdr, double idx)
 {
@@ -163,14 +197,20 @@ RIM_DEV void dist_prepare(DistParams &d, double norm)
             d.norm = ok ? norm : RIM_NAN;
             return;
         }
-        if (tab_kind_2d_on_grid(KIND)) {
+        if (tab_kind_2d_on_grid(KIND) || tab_kind_2d_nodes(KIND)) {
             // a 2-D set on given nodes: par[0] the table's header and par[1] its node data, as for a 2-D set; par[2] the
             // address of the set's u nodes (u_0 is their first word), par[3] 1 / (cell width), par[4] the index of the last
-            // guide cell; inv_gamma_cutoff the bit pattern of the guide's address, as for a set on given nodes
+            // guide cell; inv_gamma_cutoff the bit pattern of the guide's address, as for a set on given nodes.  (On given mu
+            // nodes too: the mu guide and the mu nodes lie before the node data, and the table's header says where.)
             const size_t nt = (size_t) hdr[TAB_HDR_NTABLES], cells = (size_t) hdr[TAB_HDR_H], nmu9 = (size_t) -hdr[TAB_HDR_NMU];
             const double *guide = hdr + tab_2d_grid_guide_at(nt);
             d.par[0] = rim_frombits((uint64_t) (uintptr_t) (hdr + TAB_HDR_DOUBLES + row * TAB_2D_HDR));
-            d.par[1] = rim_frombits((uint64_t) (uintptr_t) (hdr + tab_2d_grid_nodes_at(nt, nn, cells) + row * nn * nmu9 * 4));
+            if (tab_kind_2d_nodes(KIND)) {
+                const size_t at = tab_2d_nodes_nodes_at(nt, nn, cells, nmu9, (size_t) hdr[TAB_HDR_DOUBLES + TAB_2D_H]);
+                d.par[1] = rim_frombits((uint64_t) (uintptr_t) (hdr + at + row * nn * nmu9 * 4));
+            } else {
+                d.par[1] = rim_frombits((uint64_t) (uintptr_t) (hdr + tab_2d_grid_nodes_at(nt, nn, cells) + row * nn * nmu9 * 4));
+            }
             d.par[2] = rim_frombits((uint64_t) (uintptr_t) (guide + tab_grid_guide_doubles(cells)));
             d.par[3] = hdr[TAB_HDR_INVH];
             d.par[4] = hdr[TAB_HDR_H] - 1.;
@@ -285,7 +325,7 @@ RIM_DEV bool tab_kind_has_pitch(const DistParams &d)
     // (a 2-D table and one with a sin^k prefactor always have a live d f / d mu: they take the general forms, as a pitch
     // row does)
     return KIND == DIST_TABULATED_2D || KIND == DIST_TABULATED_PITCHY || KIND == DIST_TABULATED_GRID ||
-        KIND == DIST_TABULATED_2D_GRID || tab_kind_2d_pitchy(KIND) ||
+        KIND == DIST_TABULATED_2D_GRID || tab_kind_2d_pitchy(KIND) || KIND == DIST_TABULATED_2D_NODES ||
         (KIND != DIST_TABULATED_ISO && tab_has_pitch(d));
 }
 
@@ -464,15 +504,71 @@ RIM_DEV void tab_bicubic_grid(const DistParams &d, double gamma, double mu, doub
     dsdmu = dsdtm * minvh;
 }
 
+// The interval of mu in a 2-D set on given mu nodes (th: the table's header, mn: the set's mu nodes): the largest j <= n_mu - 2
+// with mu_j <= mu, 0 where there is none or mu is a NaN.  The data alone define it, as tab_grid_interval says for gamma; the
+// guide only says where to look.  Reads: the two guide words, then ceil(log2(guide[c + 1] - guide[c] + 1)) node words, 10
+// at the most (n_mu <= 1024: no two guide words are further apart than 1022).  mu_0 = -1 by the check of the set.
+RIM_DEV long long tab_2d_nodes_mu_interval(const double *th, const double *mn, double mu)
+{
+    const unsigned *guide = (const unsigned *) (th + (long long) th[TAB_2D_MU_GUIDE]);
+    const long long c = tab_grid_cell(mu, -1., th[TAB_2D_INVH], th[TAB_2D_H] - 1.);
+    long long lo = (long long) guide[c], hi = (long long) guide[c + 1];
+    while (lo < hi) {
+        const long long mid = (lo + hi + 1) >> 1;
+        RIM_TAB_2D_NODES_READ();
+        if (mn[2 * mid] <= mu) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+
+// tab_bicubic_grid for a 2-D set on given mu nodes as well: the same bicubic on the cell found by tab_2d_grid_interval and
+// tab_2d_nodes_mu_interval.  Along mu the four Hermite steps use the cell's own h_j = mu_{j+1} - mu_j, formed from the two node
+// words as the host formed it; t_mu = (mu - mu_j) (1 / h_j), dS/dmu = dS/dt_mu (1 / h_j).  A mu a rounding beyond +-1
+// extrapolates the end cell; a NaN gives NaN from cell 0; every read stays inside the set.  Only rim_log, explicit rim_fma
+// and + - * /.
+RIM_DEV void tab_bicubic_nodes(const DistParams &d, double gamma, double mu, double &sval, double &dsdu, double &dsdmu)
+{
+    const double *th = (const double *) (uintptr_t) rim_bits(d.par[0]);
+    const double *nodes = (const double *) (uintptr_t) rim_bits(d.par[1]);
+    const double *un = (const double *) (uintptr_t) rim_bits(d.par[2]);
+    const double *mn = th + (long long) th[TAB_2D_MU_NODES];
+    const double u = rim_log(gamma);
+    const long long i = tab_2d_grid_interval(d, u);
+    const double *q = un + 2 * i;
+    const double uinvh = q[1], uh = q[2] - q[0];
+    const double tu = (u - q[0]) * uinvh;
+    const long long j = tab_2d_nodes_mu_interval(th, mn, mu);
+    const double *r = mn + 2 * j;
+    const double minvh = r[1], mh = r[2] - r[0];
+    const double tm = (mu - r[0]) * minvh;
+    const long long nmu = (long long) th[TAB_2D_LAST] + 2;
+    const double *a = nodes + (i * nmu + j) * 4;        // nodes (i, j), (i, j + 1)
+    const double *b = a + nmu * 4;                      // nodes (i + 1, j), (i + 1, j + 1)
+    double va, dva, wa, dwa, vb, dvb, wb, dwb;
+    tab_hermite4(a[0], a[2], a[4], a[6], mh, tm, va, dva);
+    tab_hermite4(a[1], a[3], a[5], a[7], mh, tm, wa, dwa);
+    tab_hermite4(b[0], b[2], b[4], b[6], mh, tm, vb, dvb);
+    tab_hermite4(b[1], b[3], b[5], b[7], mh, tm, wb, dwb);
+    double dsdtu, dsdtm, unused;
+    tab_hermite4(va, wa, vb, wb, uh, tu, sval, dsdtu);
+    tab_hermite4(dva, dwa, dvb, dwb, uh, tu, dsdtm, unused);
+    dsdu = dsdtu * uinvh;
+    dsdmu = dsdtm * minvh;
+}
+
 // nbar(gamma) = 1/2 int exp(S(ln gamma, mu)) dmu of a 2-D table: the integrand of its normalisation.  The 31-point Kronrod
 // rule (xgk, wgk: gk31_table.h) on every mu cell, summed in node order -- the rule P of a pitch row uses.  KIND: the form
-// of the set, one of the four 2-D forms.
+// of the set, one of the six 2-D forms.
 //
 // With a sin^k prefactor nbar = 1/2 int (1 - mu^2)^(k/2) exp(S) dmu, and the derivative of the integrand is singular at mu =
 // +-1 for a non-integer k or k < 2: the plain rule on an end cell is left with 4e-6 at k = 0.5 on 8 nodes.  The two end
 // cells are integrated under 1 - |mu| = omega = h v^4, v in [0, 1] on the same 31 nodes, Jacobian 4 h v^3: the integrand in
 // v goes as v^(2k+3) and the rule is at rounding for every k.  omega travels next to the node, so that sin^2 xi = omega (2 -
 // omega) is formed without cancellation.  Interior cells keep the plain rule with the factor as tab_calc_f_both forms it.
+//
+// On given mu nodes every cell has its own centre and half width, from its two node words, and h of the substitution is the
+// end cell's own width: a graded set may make that cell 1e-5 wide, and the singular derivative is inside it all the same.
 template <int KIND = DIST_TABULATED_2D>
 RIM_DEV double tab_2d_norm_integrand(const DistParams &d, double g, const double *xgk, const double *wgk)
 {
@@ -480,6 +576,39 @@ RIM_DEV double tab_2d_norm_integrand(const DistParams &d, double g, const double
     const long long cells = (long long) th[TAB_2D_LAST] + 1;
     const double h = th[TAB_2D_H];
     double sum = 0.;
+    if (tab_kind_2d_nodes(KIND)) {
+        const double *mn = th + (long long) th[TAB_2D_MU_NODES];
+        const double sk = tab_kind_2d_pitchy(KIND) ? th[TAB_2D_K] : 0.;
+        for (long long j = 0; j < cells; j++) {
+            const double w = mn[2 * j + 2] - mn[2 * j];
+            const double half = 0.5 * w, centre = mn[2 * j] + half;
+#if defined(RIM_TAB_2D_PITCHY_PLAIN_ENDS)
+            const bool end = false;
+#else
+            const bool end = tab_kind_2d_pitchy(KIND) && (j == 0 || j == cells - 1);
+#endif
+            double acc = 0.;
+            for (int k = 0; k < 31; k++) {
+                double sval, dsdu, dsdmu, mu, sin2 = 1., jac = 1.;
+                if (end) {
+                    const double v = 0.5 + 0.5 * xgk[k];
+                    const double v2 = v * v;
+                    const double omega = w * (v2 * v2);
+                    mu = j == 0 ? -1. + omega : 1. - omega;
+                    sin2 = omega * (2. - omega);
+                    jac = 4. * (v2 * v);
+                } else {
+                    mu = centre + half * xgk[k];
+                    if (tab_kind_2d_pitchy(KIND)) sin2 = 1. - mu * mu;
+                }
+                tab_bicubic_nodes(d, g, mu, sval, dsdu, dsdmu);
+                if (tab_kind_2d_pitchy(KIND)) acc += wgk[k] * (jac * (RimMath<0>::pow(rim_sqrt(sin2), sk) * rim_exp(sval)));
+                else acc += wgk[k] * rim_exp(sval);
+            }
+            sum += half * acc;
+        }
+        return 0.5 * sum;
+    }
     if (tab_kind_2d_pitchy(KIND)) {
         const double sk = th[TAB_2D_K];
         for (long long j = 0; j < cells; j++) {
@@ -534,10 +663,11 @@ RIM_DEV void tab_calc_f_both(const DistParams &d, double gamma, double cos_xi, d
 {
     f = 0.; dfdg = 0.; dfdcx = 0.;
     if (gamma < d.inv_kappa_width || gamma > d.neg_inverse_t) return;
-    if (KIND == DIST_TABULATED_2D || KIND == DIST_TABULATED_2D_GRID) {
+    if (KIND == DIST_TABULATED_2D || KIND == DIST_TABULATED_2D_GRID || KIND == DIST_TABULATED_2D_NODES) {
         // f = norm exp(S(ln gamma, mu)) / (gamma^2 beta), d f / d mu = f S_mu: one exponential per sample
         double sval, dsdu, dsdmu;
-        if (KIND == DIST_TABULATED_2D_GRID) tab_bicubic_grid(d, gamma, cos_xi, sval, dsdu, dsdmu);
+        if (KIND == DIST_TABULATED_2D_NODES) tab_bicubic_nodes(d, gamma, cos_xi, sval, dsdu, dsdmu);
+        else if (KIND == DIST_TABULATED_2D_GRID) tab_bicubic_grid(d, gamma, cos_xi, sval, dsdu, dsdmu);
         else tab_bicubic(d, gamma, cos_xi, sval, dsdu, dsdmu);
         const double beta2 = rim_sqrt(1. - rim_div_moderate(1., gamma * gamma));
         f = d.norm * rim_exp(sval) / (gamma * gamma * beta2);
@@ -552,7 +682,8 @@ RIM_DEV void tab_calc_f_both(const DistParams &d, double gamma, double cos_xi, d
         const double *th = (const double *) (uintptr_t) rim_bits(d.par[0]);
         const double k = th[TAB_2D_K];
         double sval, dsdu, dsdmu;
-        if (tab_kind_2d_on_grid(KIND)) tab_bicubic_grid(d, gamma, cos_xi, sval, dsdu, dsdmu);
+        if (tab_kind_2d_nodes(KIND)) tab_bicubic_nodes(d, gamma, cos_xi, sval, dsdu, dsdmu);
+        else if (tab_kind_2d_on_grid(KIND)) tab_bicubic_grid(d, gamma, cos_xi, sval, dsdu, dsdmu);
         else tab_bicubic(d, gamma, cos_xi, sval, dsdu, dsdmu);
         const double sin_xi = rim_sqrt(1. - cos_xi * cos_xi);
         const double pa_term = RimMath<0>::pow(sin_xi, k);

@@ -334,9 +334,9 @@ struct rimphony_ctx {
     unsigned long long hb_task;
     // what hipOccupancyMaxActiveBlocksPerMultiprocessor answered (-1: the query failed), asked once per context
     // (= per device) and instantiation: coop_kernel<P> by problem (0 Symphony, 1 Heyvaerts) and distribution kind,
-    int resident[2][12];            // (kind 4 eight times: the cell of a table set is its DIST_TABULATED* value, tab_kind below)
+    int resident[2][14];            // (kind 4 ten times: the cell of a table set is its DIST_TABULATED* value, tab_kind below)
     int resident_f32[4];            // ... the Symphony kernels' fp32-integrand variants,
-    int resident_group[2][12];      // ... group_kernel<P> [Symphony groups / Faraday pair][kind] (kind 4: the cells of `resident`; no Faraday pair)
+    int resident_group[2][14];      // ... group_kernel<P> [Symphony groups / Faraday pair][kind] (kind 4: the cells of `resident`; no Faraday pair)
     // 0: this context has the GPU to itself (it holds the device's lock file); 1: another context or process had
     // the device first -- smaller persistent grids, no cooperative tail (see rimphony_ctx_create)
     int shared_mode;
@@ -607,7 +607,7 @@ static int install_tables(rimphony_ctx *c, const std::vector<double> &blob, int 
     return RIMPHONY_OK;
 }
 
-// The eight entries: check, build, install; n_tables = 0 clears through any of them.  A set of energy tables, each with a
+// The nine entries: check, build, install; n_tables = 0 clears through any of them.  A set of energy tables, each with a
 // pitch row (log_g) or none with one (log_g null and n_mu = 0: the isotropic form).
 extern "C" int rimphony_ctx_set_tables_pitch(rimphony_ctx *c, size_t n_tables, size_t n_nodes, double gamma_lo, double gamma_hi,
                                              const double *log_n, size_t n_mu, const double *log_g)
@@ -723,6 +723,23 @@ extern "C" int rimphony_ctx_set_tables_2d_grid_pitchy(rimphony_ctx *c, size_t n_
         catch (const std::bad_alloc &) { return RIMPHONY_ENOMEM; }
     }
     return install_tables(c, blob, DIST_TABULATED_2D_GRID_PITCHY, rim_tab_2d_grid_pitchy_launch_table_norms);
+}
+
+// A 2-D set on gamma nodes and mu nodes of the caller's choosing, with a sin^k xi prefactor per table or (sin_k null) without:
+// the gamma lookup of the form above and the same kind of lookup along mu (rimphony_tab_2d_nodes.hip,
+// rimphony_tab_2d_nodes_pitchy.hip).
+extern "C" int rimphony_ctx_set_tables_2d_nodes(rimphony_ctx *c, size_t n_tables, size_t n_nodes, const double *gamma, size_t n_mu,
+                                                const double *mu, const double *log_n, const double *sin_k)
+{
+    if (!c) return RIMPHONY_EINVAL;
+    std::vector<double> blob;
+    if (n_tables) {
+        if (rim_tab_check_2d_nodes(n_tables, n_nodes, gamma, n_mu, mu, log_n, sin_k)) return RIMPHONY_EINVAL;
+        try { rim_tab_build_2d_nodes(n_tables, n_nodes, gamma, n_mu, mu, log_n, sin_k, blob); }
+        catch (const std::bad_alloc &) { return RIMPHONY_ENOMEM; }
+    }
+    if (sin_k) return install_tables(c, blob, DIST_TABULATED_2D_NODES_PITCHY, rim_tab_2d_nodes_pitchy_launch_table_norms);
+    return install_tables(c, blob, DIST_TABULATED_2D_NODES, rim_tab_2d_nodes_launch_table_norms);
 }
 
 static int rim_precision_check(const rimphony_ctx *c, int kind, int precision);
@@ -953,7 +970,7 @@ static int launch_group(rimphony_ctx *c, int kind, const SymArgs &a, uint32_t co
 
 // Where the Symphony slots of the tabulated distribution run when RIMPHONY_TAB_GROUP does not say: on the group kernel or
 // one wave per coefficient, per form of the installed set; a 2-D set on given nodes (DIST_TABULATED_2D_GRID) has no line of
-// its own and takes the 2-D form's, as do the 2-D forms with a sin^k prefactor.  NOT MEASURED yet: every form says "group" until the file its line names has figures --
+// its own and takes the 2-D form's, as do the 2-D forms with a sin^k prefactor and those on given mu nodes.  NOT MEASURED yet: every form says "group" until the file its line names has figures --
 // profiles/tabulated_group_times.txt, profiles/tabulated_grid_times.txt for a set on given gamma nodes.
 static const bool RIM_TAB_GROUP_DEFAULT[5] = {      // [tab_kind - DIST_TABULATED]
     true,       // DIST_TABULATED, pitch rows   NOT MEASURED (profiles/tabulated_group_times.txt)

@@ -1,7 +1,9 @@
 // tab_2d_pitchy_unit.h -- the text of the two units that hold the kernels of a 2-D table set with a sin^k xi prefactor
 // (rimphony_tab_2d_pitchy.hip: DIST_TABULATED_2D_PITCHY; rimphony_tab_2d_grid_pitchy.hip: DIST_TABULATED_2D_GRID_PITCHY).  The
 // unit defines RIM_T2P_KIND, the name of its norm kernel and the names of its four host functions (tab_launch.h), then
-// includes this: the two differ in the form alone.
+// includes this: the two differ in the form alone.  The units of the 2-D form on given gamma and mu nodes include it too
+// (rimphony_tab_2d_nodes.hip: DIST_TABULATED_2D_NODES, whose nbar has no factor and no end-cell treatment;
+// rimphony_tab_2d_nodes_pitchy.hip: DIST_TABULATED_2D_NODES_PITCHY): nothing below depends on the prefactor.
 //
 // The normalisation of every table, one wave per table: norm = 1 / (4 pi int nbar dgamma) over the table's range with the
 // settings of norm_kernel (eps_rel 1e-8, 1000 subintervals), nbar(gamma) = 1/2 int (1 - mu^2)^(k/2) exp(S) dmu by the Kronrod

@@ -19,7 +19,8 @@ struct RimCoopKernelInfo {
 // chooses the instantiation K: DIST_TABULATED for a set with pitch rows, DIST_TABULATED_ISO for an isotropic one,
 // DIST_TABULATED_2D for a 2-D set, DIST_TABULATED_PITCHY for one with a sin^k xi prefactor (and pitch rows or none),
 // DIST_TABULATED_GRID for one on gamma nodes of its own (with both of those or neither), DIST_TABULATED_2D_GRID for a 2-D set
-// on gamma nodes of its own, DIST_TABULATED_2D_PITCHY and DIST_TABULATED_2D_GRID_PITCHY for those two with a sin^k xi prefactor.
+// on gamma nodes of its own, DIST_TABULATED_2D_PITCHY and DIST_TABULATED_2D_GRID_PITCHY for those two with a sin^k xi prefactor,
+// DIST_TABULATED_2D_NODES and DIST_TABULATED_2D_NODES_PITCHY for a 2-D set on gamma and mu nodes of its own, without and with one.
 
 // coop_kernel<SymphonyProblem<K>> (problem 0) or coop_kernel<HeyvaertsProblem<K>> (1)
 RimCoopKernelInfo rim_tab_coop_kernel(int problem, int tab_kind);
@@ -32,6 +33,8 @@ const void *rim_tab_grid_group_kernel();
 const void *rim_tab_2d_grid_group_kernel();
 const void *rim_tab_2d_pitchy_group_kernel();           // rimphony_tab_2d_pitchy_group.hip
 const void *rim_tab_2d_grid_pitchy_group_kernel();      // rimphony_tab_2d_grid_pitchy_group.hip
+const void *rim_tab_2d_nodes_group_kernel();            // rimphony_tab_2d_nodes_group.hip
+const void *rim_tab_2d_nodes_pitchy_group_kernel();     // rimphony_tab_2d_nodes_pitchy_group.hip
 // norm_kernel, integrand_kernel_n and gamma_integral_kernel of the kind: enqueue only, the caller asks hipGetLastError().
 // An isotropic set runs their DIST_TABULATED instantiations (rimphony_internal.h: rim_tab_seam_kind).  (The rows of a 2-D set
 // read their table's normalisation, which rim_tab_launch_table_norms computed when the set came in: one wave per table,
@@ -71,6 +74,21 @@ void rim_tab_2d_grid_pitchy_launch_integrand(unsigned grid, hipStream_t st, cons
 void rim_tab_2d_grid_pitchy_launch_gamma_integral(unsigned grid, hipStream_t st, const PointArgs &pa, const double *d_norm, size_t count,
                                                   const double *d_n, double *d_out, double *spill);
 void rim_tab_2d_grid_pitchy_launch_table_norms(unsigned grid, hipStream_t st, double *d_set, double *spill);
+
+// The same for the 2-D form on given gamma and mu nodes: DIST_TABULATED_2D_NODES in rimphony_tab_2d_nodes.hip,
+// DIST_TABULATED_2D_NODES_PITCHY in rimphony_tab_2d_nodes_pitchy.hip (the same text).
+RimCoopKernelInfo rim_tab_2d_nodes_coop_kernel(int problem);
+void rim_tab_2d_nodes_launch_integrand(unsigned grid, hipStream_t st, const PointArgs &pa, const double *d_norm, size_t count,
+                                       const double *d_n, const double *d_gamma, double *d_out);
+void rim_tab_2d_nodes_launch_gamma_integral(unsigned grid, hipStream_t st, const PointArgs &pa, const double *d_norm, size_t count,
+                                            const double *d_n, double *d_out, double *spill);
+void rim_tab_2d_nodes_launch_table_norms(unsigned grid, hipStream_t st, double *d_set, double *spill);
+RimCoopKernelInfo rim_tab_2d_nodes_pitchy_coop_kernel(int problem);
+void rim_tab_2d_nodes_pitchy_launch_integrand(unsigned grid, hipStream_t st, const PointArgs &pa, const double *d_norm, size_t count,
+                                              const double *d_n, const double *d_gamma, double *d_out);
+void rim_tab_2d_nodes_pitchy_launch_gamma_integral(unsigned grid, hipStream_t st, const PointArgs &pa, const double *d_norm, size_t count,
+                                                   const double *d_n, double *d_out, double *spill);
+void rim_tab_2d_nodes_pitchy_launch_table_norms(unsigned grid, hipStream_t st, double *d_set, double *spill);
 
 // RimCoopKernelInfo of coop_kernel<P>, `fn`
 template <class P>

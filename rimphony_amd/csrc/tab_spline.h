@@ -32,6 +32,10 @@
 // A 2-D set of either form may carry a sin^k xi prefactor per table (rim_tab_check_2d_pitchy, rim_tab_build_2d_pitchy and
 // their _grid_ counterparts): the form's blob with k in a spare word of each table's header (TAB_2D_K).
 //
+// A 2-D set may stand on mu nodes of the caller's choosing as well (rim_tab_check_2d_nodes, rim_tab_build_2d_nodes): the 2-D
+// set on given gamma nodes with the sweeps along mu on the non-uniform system too, a mu guide and one array of mu nodes per
+// set (dev_symphony.h: tab_2d_nodes_*), with or without a sin^k xi prefactor.
+//
 // Plain C++ with the elementary functions of detmath.h, so that the library (hipcc's host pass) and the tests' table
 // oracle (g++) produce the same bits from the same table.
 #ifndef RIM_TAB_SPLINE_H
@@ -474,6 +478,92 @@ inline void rim_tab_build_2d_grid_pitchy(size_t n_tables, size_t n_nodes, const 
 {
     rim_tab_build_2d_grid(n_tables, n_nodes, gamma, n_mu, log_n, blob);
     rim_tab_put_2d_sin_k(n_tables, sin_k, blob);
+}
+
+// the mu nodes of a 2-D set on given mu nodes: mu [n_mu], n_mu within the 2-D form's limits, every value finite, strictly
+// increasing, mu[0] == -1 and mu[n_mu - 1] == +1 exactly (the surface covers the whole range: no extrapolation in the
+// normalisation, and the guide's cells are exact)
+inline int rim_tab_check_mu_nodes(size_t n_mu, const double *mu)
+{
+    if (!mu || n_mu < RIM_TAB_2D_MIN_MU || n_mu > RIM_TAB_2D_MAX_MU) return -1;
+    for (size_t j = 0; j < n_mu; j++)
+        if (!rim_isfinite(mu[j])) return -1;
+    if (mu[0] != -1. || mu[n_mu - 1] != 1.) return -1;
+    for (size_t j = 0; j + 1 < n_mu; j++)
+        if (!(mu[j] < mu[j + 1])) return -1;
+    return 0;
+}
+
+// rim_tab_check_2d_grid() for a set on given mu nodes too; sin_k may be null (no prefactor)
+inline int rim_tab_check_2d_nodes(size_t n_tables, size_t n_nodes, const double *gamma, size_t n_mu, const double *mu,
+                                  const double *log_n, const double *sin_k)
+{
+    if (rim_tab_check_mu_nodes(n_mu, mu)) return -1;
+    if (rim_tab_check_2d_grid(n_tables, n_nodes, gamma, n_mu, log_n)) return -1;
+    return sin_k ? rim_tab_check_sin_k(n_tables, sin_k) : 0;
+}
+
+// the 2-D set on given gamma and mu nodes as one block of doubles (dev_symphony.h: tab_2d_nodes_*); rim_tab_check_2d_nodes()
+// has passed.  The three families of sweeps in rim_tab_build_2d's order, all of them through rim_tab_spline_row_grid: along u
+// on h_i = u_{i+1} - u_i, along mu on h_j = mu_{j+1} - mu_j, each with its 1 / h formed once per set.  Both guides as
+// rim_tab_build_grid fills its one.  sin_k null: TAB_2D_K stays 0.  The normalisation of a table is 0 as built.
+inline void rim_tab_build_2d_nodes(size_t n_tables, size_t n_nodes, const double *gamma, size_t n_mu, const double *mu,
+                                   const double *log_n, const double *sin_k, std::vector<double> &blob)
+{
+    using namespace rim;
+    size_t cells = 8, mu_cells = 8;
+    while (cells < n_nodes) cells *= 2;
+    while (mu_cells < n_mu) mu_cells *= 2;
+    const size_t per_table = n_nodes * n_mu * 4;
+    const size_t mu_guide_at = tab_2d_nodes_mu_guide_at(n_tables, n_nodes, cells);
+    const size_t mu_nodes_at = mu_guide_at + tab_grid_guide_doubles(mu_cells);
+    const size_t nodes_at = tab_2d_nodes_nodes_at(n_tables, n_nodes, cells, n_mu, mu_cells);
+    blob.assign(nodes_at + n_tables * per_table, 0.);
+    const size_t longest = n_nodes > n_mu ? n_nodes : n_mu;
+    std::vector<double> u(n_nodes), h(n_nodes), ih(n_nodes), hm(n_mu), ihm(n_mu), col(longest), m(longest), cp(longest), dp(longest);
+    for (size_t j = 0; j < n_nodes; j++) u[j] = rim_log(gamma[j]);
+    for (size_t j = 0; j + 1 < n_nodes; j++) { h[j] = u[j + 1] - u[j]; ih[j] = 1. / h[j]; }
+    h[n_nodes - 1] = 0.; ih[n_nodes - 1] = 0.;
+    for (size_t j = 0; j + 1 < n_mu; j++) { hm[j] = mu[j + 1] - mu[j]; ihm[j] = 1. / hm[j]; }
+    hm[n_mu - 1] = 0.; ihm[n_mu - 1] = 0.;
+    const double inv_cell = (double) cells / (u[n_nodes - 1] - u[0]);
+    const double inv_mu_cell = (double) mu_cells / (mu[n_mu - 1] - mu[0]);
+    rim_tab_set_header(blob.data(), n_tables, n_nodes, gamma[0], gamma[n_nodes - 1], u[0], inv_cell, (double) cells, -(double) n_mu);
+    rim_tab_fill_guide(u.data(), n_nodes, cells, inv_cell, (uint32_t *) (blob.data() + tab_2d_grid_guide_at(n_tables)));
+    double *un = blob.data() + tab_2d_grid_guide_at(n_tables) + tab_grid_guide_doubles(cells);
+    for (size_t i = 0; i < n_nodes; i++) { un[2 * i] = u[i]; un[2 * i + 1] = ih[i]; }
+    rim_tab_fill_guide(mu, n_mu, mu_cells, inv_mu_cell, (uint32_t *) (blob.data() + mu_guide_at));
+    double *mn = blob.data() + mu_nodes_at;
+    for (size_t j = 0; j < n_mu; j++) { mn[2 * j] = mu[j]; mn[2 * j + 1] = ihm[j]; }
+    for (size_t t = 0; t < n_tables; t++) {
+        const size_t th_at = (size_t) TAB_HDR_DOUBLES + t * TAB_2D_HDR;
+        double *th = blob.data() + th_at;
+        th[TAB_2D_LAST] = (double) (n_mu - 2);
+        th[TAB_2D_INVH] = inv_mu_cell;
+        th[TAB_2D_H] = (double) mu_cells;
+        th[TAB_2D_K] = sin_k ? sin_k[t] : 0.;
+        th[TAB_2D_MU_GUIDE] = (double) (mu_guide_at - th_at);
+        th[TAB_2D_MU_NODES] = (double) (mu_nodes_at - th_at);
+        const double *src = log_n + t * n_nodes * n_mu;
+        double *nodes = blob.data() + nodes_at + t * per_table;
+        for (size_t j = 0; j < n_mu; j++) {
+            for (size_t i = 0; i < n_nodes; i++) col[i] = src[i * n_mu + j];
+            rim_tab_spline_row_grid(col.data(), n_nodes, h.data(), ih.data(), m.data(), cp.data(), dp.data());
+            for (size_t i = 0; i < n_nodes; i++) {
+                nodes[(i * n_mu + j) * 4] = col[i];
+                nodes[(i * n_mu + j) * 4 + 1] = m[i];
+            }
+        }
+        for (size_t i = 0; i < n_nodes; i++) {
+            rim_tab_spline_row_grid(src + i * n_mu, n_mu, hm.data(), ihm.data(), m.data(), cp.data(), dp.data());
+            for (size_t j = 0; j < n_mu; j++) nodes[(i * n_mu + j) * 4 + 2] = m[j];
+        }
+        for (size_t j = 0; j < n_mu; j++) {
+            for (size_t i = 0; i < n_nodes; i++) col[i] = nodes[(i * n_mu + j) * 4 + 2];
+            rim_tab_spline_row_grid(col.data(), n_nodes, h.data(), ih.data(), m.data(), cp.data(), dp.data());
+            for (size_t i = 0; i < n_nodes; i++) nodes[(i * n_mu + j) * 4 + 3] = m[i];
+        }
+    }
 }
 
 #endif

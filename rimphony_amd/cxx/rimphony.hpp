@@ -150,6 +150,21 @@ public:
                                                      n_tables ? log_n.data() : nullptr, n_tables ? sin_k.data() : nullptr),
               "rimphony_ctx_set_tables_2d_grid_pitchy");
     }
+    // A 2-D set on gamma nodes and mu nodes of the caller's choosing (rimphony_ctx_set_tables_2d_nodes): gamma as for
+    // set_tables_2d_grid; mu [n_mu] strictly increasing from exactly -1 to exactly +1, shared by the tables; log_n
+    // [n_tables][n_nodes][n_mu], mu fastest; sin_k empty (the plain form) or [n_tables], each in [0, 100].
+    void set_tables_2d_nodes(size_t n_tables, const std::vector<double> &gamma, const std::vector<double> &mu,
+                             const std::vector<double> &log_n, const std::vector<double> &sin_k = {}) const
+    {
+        if (log_n.size() != n_tables * gamma.size() * mu.size())
+            throw std::runtime_error("set_tables_2d_nodes: log_n must hold n_tables * n_nodes * n_mu values");
+        if (!sin_k.empty() && sin_k.size() != n_tables)
+            throw std::runtime_error("set_tables_2d_nodes: sin_k must be empty or hold n_tables values");
+        check(rimphony_ctx_set_tables_2d_nodes(ctx_, n_tables, gamma.size(), n_tables ? gamma.data() : nullptr, mu.size(),
+                                               n_tables ? mu.data() : nullptr, n_tables ? log_n.data() : nullptr,
+                                               sin_k.empty() ? nullptr : sin_k.data()),
+              "rimphony_ctx_set_tables_2d_nodes");
+    }
 private:
     rimphony_ctx *ctx_ = nullptr;
 };
@@ -471,6 +486,34 @@ private:
     std::vector<double> gamma_;
     size_t n_mu_;
     std::vector<double> log_n_, sin_k_;
+};
+
+// A distribution given as a surface on gamma nodes and mu nodes of its own: log_n [n_nodes][n_mu], mu fastest, = ln n(gamma_i,
+// mu_j) at the strictly increasing gamma [n_nodes] and mu [n_mu], mu from exactly -1 to exactly +1 (include/rimphony_hip.h:
+// rimphony_ctx_set_tables_2d_nodes): TabulatedDistribution2DGrid on mu nodes graded towards a beam, a ring or the edge of a
+// loss cone, or uniform in xi.  Used as that one is.
+class TabulatedDistribution2DNodes : public DistributionFunction {
+protected:
+    int abi_kind() const override { return RIMPHONY_TABULATED; }
+    std::vector<double> abi_params() const override { return {0.}; }      // the table index
+public:
+    TabulatedDistribution2DNodes(std::vector<double> gamma, std::vector<double> mu, std::vector<double> log_n)
+        : gamma_(std::move(gamma)), mu_(std::move(mu)), log_n_(std::move(log_n)) {}
+    // ... times sin^k xi in closed form, as TabulatedDistribution2D takes it
+    TabulatedDistribution2DNodes(std::vector<double> gamma, std::vector<double> mu, std::vector<double> log_n, double sin_k)
+        : gamma_(std::move(gamma)), mu_(std::move(mu)), log_n_(std::move(log_n)), sin_k_{sin_k} {}
+    void install(const Context &ctx) const { ctx.set_tables_2d_nodes(1, gamma_, mu_, log_n_, sin_k_); }
+    double calc_f(const Context &ctx, double gamma, double cos_xi) const
+    { install(ctx); return DistributionFunction::calc_f(ctx, gamma, cos_xi); }
+    std::array<double, 2> calc_f_derivatives(const Context &ctx, double gamma, double cos_xi) const
+    { install(ctx); return DistributionFunction::calc_f_derivatives(ctx, gamma, cos_xi); }
+    FullSynchrotronCalculator full_calculation(std::shared_ptr<Context> ctx) const
+    {
+        install(*ctx);
+        return FullSynchrotronCalculator(std::move(ctx), RIMPHONY_TABULATED, {0.});
+    }
+private:
+    std::vector<double> gamma_, mu_, log_n_, sin_k_;
 };
 
 // A distribution given as a table on gamma nodes of its own: log_n [n_nodes] = ln n at the strictly increasing gamma

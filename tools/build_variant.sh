@@ -4,4 +4,4 @@
 out="$1"; shift
 cd "$(dirname "$0")/.." && mkdir -p "$(dirname "$out")" && hipcc -O3 --offload-arch=gfx950 -std=c++17 -fPIC -shared -ffp-contract=off \
   -mllvm -disable-machine-licm -Xarch_host -mfma "$@" -Iinclude -Irimphony_amd/csrc \
-  rimphony_amd/csrc/rimphony_hip.hip rimphony_amd/csrc/rimphony_diag.hip rimphony_amd/csrc/rimphony_group.hip rimphony_amd/csrc/rimphony_multi.hip rimphony_amd/csrc/rimphony_tab.hip rimphony_amd/csrc/rimphony_tab_group.hip rimphony_amd/csrc/rimphony_tab_grid_group.hip rimphony_amd/csrc/rimphony_tab_2d_grid.hip rimphony_amd/csrc/rimphony_tab_2d_grid_group.hip rimphony_amd/csrc/rimphony_tab_2d_pitchy.hip rimphony_amd/csrc/rimphony_tab_2d_pitchy_group.hip rimphony_amd/csrc/rimphony_tab_2d_grid_pitchy.hip rimphony_amd/csrc/rimphony_tab_2d_grid_pitchy_group.hip -ldl -o "$out"
+  rimphony_amd/csrc/rimphony_hip.hip rimphony_amd/csrc/rimphony_diag.hip rimphony_amd/csrc/rimphony_group.hip rimphony_amd/csrc/rimphony_multi.hip rimphony_amd/csrc/rimphony_tab.hip rimphony_amd/csrc/rimphony_tab_group.hip rimphony_amd/csrc/rimphony_tab_grid_group.hip rimphony_amd/csrc/rimphony_tab_2d_grid.hip rimphony_amd/csrc/rimphony_tab_2d_grid_group.hip rimphony_amd/csrc/rimphony_tab_2d_pitchy.hip rimphony_amd/csrc/rimphony_tab_2d_pitchy_group.hip rimphony_amd/csrc/rimphony_tab_2d_grid_pitchy.hip rimphony_amd/csrc/rimphony_tab_2d_grid_pitchy_group.hip rimphony_amd/csrc/rimphony_tab_2d_nodes.hip rimphony_amd/csrc/rimphony_tab_2d_nodes_group.hip rimphony_amd/csrc/rimphony_tab_2d_nodes_pitchy.hip rimphony_amd/csrc/rimphony_tab_2d_nodes_pitchy_group.hip -ldl -o "$out"
