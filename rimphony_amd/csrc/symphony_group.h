@@ -21,6 +21,12 @@
 //     quadrature asks for it, and every member sees exactly the arithmetic of a solo run (its own rule sums from its
 //     own integrand values in the same reduction tree, its own bisection sequence, its own round-off counters), so
 //     results, status words and the per-coefficient work counters are the reference's, bit for bit.
+//   * what a member needs twice -- for child 1 and for child 2 -- and not 64 times runs side by side, lane m for member m
+//     and lane 32 + m for its second child: qag.c's loop body of a turn (group_book_lanes) and the tail of the rule of a
+//     pass (group_rule_sums: the scalings and rescale_error's division and root, once per pass instead of once per served
+//     member; the rule's reductions, which need all 64 samples of a member, stay per member).  The same operations on the
+//     same operands in another lane.  The picks stay in turn: two lists per execution, one per half-wave, was built and
+//     measured slower (profiles/group_rule_tails_ab.txt).
 //
 // Nothing here changes a rounding: tests/test_gpu_parity.py compares group runs with the oracle's per-coefficient
 // values and with solo runs (coefficient masks that leave a member alone).
@@ -330,6 +336,159 @@ __device__ __forceinline__ GroupBooked group_book_turn(GroupParkBase *gp, double
     return bk;
 }
 
+// The members' part of a pass: the served members' integrand values and rule sums, and where the sums go.  The
+// REDUCTIONS of the rule (wave_gk31_sums) run per member, as they must: 64 samples of that member in, four sums out, the
+// same four in every lane of a half-wave.  The TAIL of the rule (wave_gk31_tail: the scalings, rescale_error's division
+// and root) needs two distinct results per member -- child 1's and child 2's -- and used to run on all 64 lanes for them,
+// once per served member.  Here member m's four sums are routed into lanes m and 32 + m as they come (a select under a
+// scalar lane mask), four doubles stay live across the loop, and after the loop ONE tail serves all members: lane m ends
+// with member m's child-1 result, lane 32 + m with its child-2 result -- the same operations on the same operands as
+// before, in another lane.  One ballot of resasc != abserr then holds every member's flag pair (bits m and 32 + m), and
+// lanes m / 32 + m file what lanes 0 / 32 filed member by member: the first-rule sums (cur < 0; lane m for integral A,
+// lane 32 + m for B), the hand-over record of a member that picked the pass's interval, the stash entry of a served
+// member that did not (its place -- a free one, else the next in turn -- stays a scalar decision per member).  The
+// lane's member and the addresses derived from it are rebuilt at their use, as in group_book_lanes.  A pass that serves
+// one member keeps the member-by-member form behind a scalar branch.  (Numbers: profiles/group_rule_tails_ab.txt.)
+template <class F>
+__device__ __forceinline__ void group_rule_sums(F &f, const GKLane &g, GroupParkBase *gp, int cur, unsigned serve, unsigned booknow,
+                                                unsigned long long idxp, unsigned maskA, unsigned maskB, double hl,
+                                                unsigned &stashed, unsigned &n_samp_all, unsigned &n_member_pass,
+                                                unsigned &n_qags, unsigned &n_filed)
+{
+    if ((serve & (serve - 1u)) == 0) {
+        // A pass that serves ONE member has nothing to run side by side, and the per-lane member index and addresses below
+        // cost it more than they save (measured: +2 % on a lone member's launch): the rule whole, lanes 0 and 32 filing.
+        const int m = __builtin_ctz(serve);
+        GroupMember *const M = gp->mem + m;
+        const bool inA = ((maskA >> m) & 1u) != 0, inB = ((maskB >> m) & 1u) != 0;
+        const bool act_m = cur < 0 ? (g.node && (g.half == 0 ? inA : inB)) : g.node;
+        RIM_PROF_T(t_mem);
+        const double fv = f.member(m, act_m);
+        RIM_PROF_ADD(20, t_mem);
+        RIM_PROF_T(t_gk);
+        const GKRes r = wave_gk31(fv, hl, g);
+        RIM_PROF_ADD(11, t_gk);
+        if (cur < 0) {
+            if ((g.lane == 0 && inA) || (g.lane == 32 && inB)) {
+                double *fb = M->fb[g.half];
+                fb[0] = r.result; fb[1] = r.abserr; fb[2] = r.resabs; fb[3] = r.resasc;
+            }
+            const unsigned ns = (inA ? 31u : 0u) + (inB ? 31u : 0u);
+            if (g.lane == 0) M->samples = ns;
+            n_samp_all += ns;
+            n_member_pass += 1;
+            n_qags += (inA ? 1u : 0u) + (inB ? 1u : 0u);
+            return;
+        }
+        const unsigned long long ne = wv_ballot(r.resasc != r.abserr);
+        if (booknow) {
+            if (g.j == 0) {
+                double *h = M->fb[cur] + 2 * g.half;
+                h[0] = r.result; h[1] = r.abserr;
+                if (!g.half) M->hf = (int) (ne & 1ull) | (int) (((ne >> 32) & 1ull) << 1);
+            }
+        } else {
+            RIM_PROF_T(t_file);
+            const int idx = (int) ((idxp >> (16 * m)) & 0xffffull);
+            const unsigned long long freep = wv_ballot(g.lane < RIM_STASH && M->sk[g.lane & (RIM_STASH - 1)] < 0);
+            const int pos = freep ? __builtin_ffsll((long long) freep) - 1 : uni(M->snext);
+            wv_sync();
+            if (g.lane == 0) {
+                M->sk[pos] = idx;
+                M->sf[pos] = (int) (ne & 1ull) | (int) (((ne >> 32) & 1ull) << 1);
+                M->sr1[pos] = r.result; M->se1[pos] = r.abserr;
+                if (!freep) M->snext = (pos + 1) & (RIM_STASH - 1);
+            }
+            if (g.lane == 32) { M->sr2[pos] = r.result; M->se2[pos] = r.abserr; }
+            stashed |= 1u << m;
+            n_filed += 1;
+            RIM_PROF_ADD(21, t_file);
+        }
+        return;
+    }
+
+    GKSums q;                           // per lane: lanes m and 32 + m hold member m's sums
+    q.rk = 0.; q.rg = 0.; q.ra = 0.; q.rasc = 0.;
+    for (unsigned rem = serve; rem; rem &= rem - 1) {
+        const int m = __builtin_ctz(rem);
+        const bool inA = ((maskA >> m) & 1u) != 0, inB = ((maskB >> m) & 1u) != 0;
+        const bool act_m = cur < 0 ? (g.node && (g.half == 0 ? inA : inB)) : g.node;
+        RIM_PROF_T(t_mem);
+        const double fv = f.member(m, act_m);
+        RIM_PROF_ADD(20, t_mem);
+        RIM_PROF_T(t_gk);
+        const GKSums s = wave_gk31_sums(fv, g);
+        const unsigned long long pair = 0x0000000100000001ull << m;               // lanes m and 32 + m
+        q.rk = wv_put_lanes(q.rk, s.rk, pair, g.lane); q.rg = wv_put_lanes(q.rg, s.rg, pair, g.lane);
+        q.ra = wv_put_lanes(q.ra, s.ra, pair, g.lane); q.rasc = wv_put_lanes(q.rasc, s.rasc, pair, g.lane);
+        RIM_PROF_ADD(11, t_gk);
+    }
+    RIM_PROF_T(t_gk);
+    const GKRes r = wave_gk31_tail(q, hl);
+    RIM_PROF_ADD(11, t_gk);
+
+    int lane = g.lane;
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(RIM_WAVE_EMU)
+    asm volatile("" : "+v"(lane));
+#endif
+    const int ml = lane & (RIM_GROUP - 1);
+    const bool half = (lane & 32) != 0;
+    const bool mine = (lane & 31) < RIM_GROUP && ((serve >> ml) & 1u) != 0;
+    GroupMember *const M = gp->mem + ml;
+    if (cur < 0) {
+        // the joint first application: file the first-rule sums of the members' integral(s)
+        const bool inA = ((maskA >> ml) & 1u) != 0, inB = ((maskB >> ml) & 1u) != 0;
+        if (mine && (half ? inB : inA)) {
+            double *fb = M->fb[half ? 1 : 0];
+            fb[0] = r.result; fb[1] = r.abserr; fb[2] = r.resabs; fb[3] = r.resasc;
+        }
+        if (mine && !half) M->samples = (inA ? 31u : 0u) + (inB ? 31u : 0u);
+        const unsigned nq = (unsigned) (__builtin_popcount(maskA) + __builtin_popcount(maskB));      // serve == maskA | maskB
+        n_samp_all += 31u * nq;
+        n_member_pass += (unsigned) __builtin_popcount(serve);
+        n_qags += nq;
+        return;
+    }
+    const unsigned long long ne = wv_ballot(r.resasc != r.abserr);
+    // the places of the sums that go to a stash (a free place, else the next one in turn): 4 bits per member in posw,
+    // bit m of turnw: member m's place came from its cursor
+    const unsigned filed = serve & ~booknow;
+    unsigned posw = 0, turnw = 0;
+    if (filed) {
+        RIM_PROF_T(t_file);
+        for (unsigned rem = filed; rem; rem &= rem - 1) {
+            const int m = __builtin_ctz(rem);
+            const GroupMember *const Mm = gp->mem + m;
+            const unsigned long long freep = wv_ballot(g.lane < RIM_STASH && Mm->sk[g.lane & (RIM_STASH - 1)] < 0);
+            const int pos = freep ? __builtin_ffsll((long long) freep) - 1 : uni(Mm->snext);
+            posw |= (unsigned) pos << (4 * m);
+            if (!freep) turnw |= 1u << m;
+        }
+        wv_sync();
+        stashed |= filed;
+        n_filed += (unsigned) __builtin_popcount(filed);
+        RIM_PROF_ADD(21, t_file);
+    }
+    if (mine) {
+        const int fl = (int) ((ne >> ml) & 1ull) | (int) (((ne >> (32 + ml)) & 1ull) << 1);
+        if ((booknow >> ml) & 1u) {
+            // the member picked the pass's interval: its two lanes hand their child's sums over to the turn's booking
+            double *h = M->fb[cur] + (half ? 2 : 0);
+            h[0] = r.result; h[1] = r.abserr;
+            if (!half) M->hf = fl;
+        } else {
+            // the children's sums of a member that holds the interval as an entry: to its stash
+            const int pos = (int) ((posw >> (4 * ml)) & (unsigned) (RIM_STASH - 1));
+            if (!half) {
+                M->sk[pos] = (int) ((idxp >> (16 * ml)) & 0xffffull);
+                M->sf[pos] = fl;
+                M->sr1[pos] = r.result; M->se1[pos] = r.abserr;
+                if ((turnw >> ml) & 1u) M->snext = (pos + 1) & (RIM_STASH - 1);
+            } else { M->sr2[pos] = r.result; M->se2[pos] = r.abserr; }
+        }
+    }
+}
+
 // Integral A on [a0, b0] for the members of maskA, integral B on [a1, b1] for those of maskB (maskB == 0: none); as in
 // wave_qag_pair the two share their first rule application (A on lanes 0..30, B on 32..62), then A's members run to
 // the end, then B's.  The integrand is a functor with two steps:
@@ -463,58 +622,8 @@ __device__ __forceinline__ void wave_qag_group(F &f, const GKLane &g, double *in
             if (lane == 0) { extern unsigned long long g_emu_hist[64]; g_emu_hist[(cur < 0 ? 0 : 8) + __builtin_popcount(cur < 0 ? serve : booknow)]++;
                              if (cur >= 0) g_emu_hist[16 + __builtin_popcount(active)]++; }
 #endif
-            for (unsigned rem = serve; rem; rem &= rem - 1) {
-                const int m = __builtin_ctz(rem);
-                GroupMember *const M = gp->mem + m;
-                const bool inA = ((maskA >> m) & 1u) != 0, inB = ((maskB >> m) & 1u) != 0;
-                const bool act_m = cur < 0 ? (g.node && (g.half == 0 ? inA : inB)) : g.node;
-                RIM_PROF_T(t_mem);
-                const double fv = f.member(m, act_m);
-                RIM_PROF_ADD(20, t_mem);
-                RIM_PROF_T(t_gk);
-                const GKRes r = wave_gk31(fv, hl, g);
-                RIM_PROF_ADD(11, t_gk);
-                if (cur < 0) {
-                    // the joint first application: file the first-rule sums of the member's integral(s)
-                    if ((lane == 0 && inA) || (lane == 32 && inB)) {
-                        double *fb = M->fb[g.half];
-                        fb[0] = r.result; fb[1] = r.abserr; fb[2] = r.resabs; fb[3] = r.resasc;
-                    }
-                    const unsigned ns = (inA ? 31u : 0u) + (inB ? 31u : 0u);
-                    if (lane == 0) M->samples = ns;
-                    n_samp_all += ns;
-                    n_member_pass += 1;
-                    n_qags += (inA ? 1u : 0u) + (inB ? 1u : 0u);
-                } else {
-                    const unsigned long long ne = wv_ballot(r.resasc != r.abserr);
-                    if ((booknow >> m) & 1u) {
-                        // the member picked the pass's interval: lanes 0 and 32 hand their child's sums over to the
-                        // turn's booking
-                        if (g.j == 0) {
-                            double *h = M->fb[cur] + 2 * g.half;
-                            h[0] = r.result; h[1] = r.abserr;
-                            if (!g.half) M->hf = (int) (ne & 1ull) | (int) (((ne >> 32) & 1ull) << 1);
-                        }
-                    } else {
-                        // file the children's sums in the member's stash (a free place, else the next one in turn)
-                        RIM_PROF_T(t_file);
-                        const int idx = (int) ((idxp >> (16 * m)) & 0xffffull);
-                        const unsigned long long freep = wv_ballot(lane < RIM_STASH && M->sk[lane & (RIM_STASH - 1)] < 0);
-                        const int pos = freep ? __builtin_ffsll((long long) freep) - 1 : uni(M->snext);
-                        wv_sync();
-                        if (lane == 0) {
-                            M->sk[pos] = idx;
-                            M->sf[pos] = (int) (ne & 1ull) | (int) (((ne >> 32) & 1ull) << 1);
-                            M->sr1[pos] = r.result; M->se1[pos] = r.abserr;
-                            if (!freep) M->snext = (pos + 1) & (RIM_STASH - 1);
-                        }
-                        if (lane == 32) { M->sr2[pos] = r.result; M->se2[pos] = r.abserr; }
-                        stashed |= 1u << m;
-                        n_filed += 1;
-                        RIM_PROF_ADD(21, t_file);
-                    }
-                }
-            }
+            group_rule_sums(f, g, gp, cur, serve, booknow, idxp, maskA, maskB, hl, stashed, n_samp_all, n_member_pass,
+                            n_qags, n_filed);
         }
 
         if (booknow | from_stash) {

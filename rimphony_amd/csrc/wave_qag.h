@@ -196,20 +196,33 @@ __device__ __forceinline__ double rescale_error(double err, double result_abs, d
     return err;
 }
 
-// Apply the rule to the samples fv (one per lane; 0 on padding/inactive lanes).
-// half_length is the lane's interval half-length (uniform within a half-wave).
-__device__ __forceinline__ GKRes wave_gk31(double fv, double half_length, const GKLane &g)
+// The rule in two pieces.  The REDUCTIONS: the four sums (Kronrod, Gauss, |f|, |f - mean|) of the samples fv (one per
+// lane; 0 on padding/inactive lanes) before the interval's length enters; every lane of a half-wave ends with the same
+// four values.  The TAIL: the scalings by the half-length and rescale_error -- a division, a root, compares and selects
+// on values that are uniform within a half-wave.  wave_gk31 is the one after the other; the group quadrature
+// (symphony_group.h) runs the reductions per member and ONE tail for all members of a pass, lane m doing member m's.
+struct GKSums { double rk, rg, ra, rasc; };
+
+__device__ __forceinline__ GKSums wave_gk31_sums(double fv, const GKLane &g)
 {
+    GKSums s;
     const double wk = gk_wk(g);
     const double fsum = pair_sum(fv);                                  // qk.c: fsum = fval1 + fval2 (centre: fc + 0)
-    double rk = sum16(wk * fsum);
-    const double rg = sum16(gk_wg(g) * fsum);
-    double ra = sum16(wk * pair_sum(rim_fabs(fv)));
-    const double mean = rk * 0.5;
+    s.rk = sum16(wk * fsum);
+    s.rg = sum16(gk_wg(g) * fsum);
+    s.ra = sum16(wk * pair_sum(rim_fabs(fv)));
+    const double mean = s.rk * 0.5;
     const double dev = g.node ? rim_fabs(fv - mean) : 0.;              // the padding lane holds 0, not |0 - mean|
-    double rasc = sum16(wk * pair_sum(dev));
+    s.rasc = sum16(wk * pair_sum(dev));
+    return s;
+}
+
+// half_length is the lane's interval half-length (uniform within a half-wave).
+__device__ __forceinline__ GKRes wave_gk31_tail(const GKSums &s, double half_length)
+{
+    double rk = s.rk, ra = s.ra, rasc = s.rasc;
     const double ahl = rim_fabs(half_length);
-    const double err = (rk - rg) * half_length;
+    const double err = (rk - s.rg) * half_length;
     rk *= half_length;
     ra *= ahl;
     rasc *= ahl;
@@ -219,6 +232,28 @@ __device__ __forceinline__ GKRes wave_gk31(double fv, double half_length, const 
     r.resasc = rasc;
     r.abserr = rescale_error(err, ra, rasc);
     return r;
+}
+
+// Apply the rule to the samples fv (one per lane; 0 on padding/inactive lanes).
+__device__ __forceinline__ GKRes wave_gk31(double fv, double half_length, const GKLane &g)
+{
+    return wave_gk31_tail(wave_gk31_sums(fv, g), half_length);
+}
+
+// v on the lanes of `lanes` (a wave-uniform lane mask), `keep` on the others: the mask is a scalar operand of the
+// select, one instruction per half of the double and no per-lane compare.
+__device__ __forceinline__ double wv_put_lanes(double keep, double v, unsigned long long lanes, int lane)
+{
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(RIM_WAVE_EMU)
+    const unsigned long long k = rim_bits(keep), u = rim_bits(v);
+    unsigned lo, hi;
+    asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(lo) : "v"((unsigned) k), "v"((unsigned) u), "s"(lanes));
+    asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(hi) : "v"((unsigned) (k >> 32)), "v"((unsigned) (u >> 32)), "s"(lanes));
+    (void) lane;
+    return rim_frombits(((unsigned long long) hi << 32) | lo);
+#else
+    return ((lanes >> lane) & 1ull) ? v : keep;
+#endif
 }
 
 // ---- subinterval store ------------------------------------------------------
