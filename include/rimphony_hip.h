@@ -357,6 +357,39 @@ int rimphony_ctx_set_tables_2d_grid_pitchy(rimphony_ctx *ctx, size_t n_tables, s
 int rimphony_ctx_set_tables_2d_nodes(rimphony_ctx *ctx, size_t n_tables, size_t n_nodes, const double *gamma, size_t n_mu,
                                      const double *mu, const double *log_n, const double *sin_k);
 
+/* Any of the six 2-D forms above from ln n in DEVICE memory: for a caller whose ln n(gamma, mu) is made on the GPU (a PIC or
+ * Fokker-Planck post-processing step) and who would otherwise copy it to the host, wait for the host's serial spline solve
+ * and have four times as much copied back.
+ *   gamma     NULL: nodes uniform in ln gamma from gamma_lo to gamma_hi; or HOST [n_nodes], as for
+ *             rimphony_ctx_set_tables_2d_grid (gamma_lo and gamma_hi are then not read);
+ *   mu        NULL: nodes uniform in mu from -1 to +1; or HOST [n_mu], as for rimphony_ctx_set_tables_2d_nodes.  mu without
+ *             gamma is no form: RIMPHONY_EINVAL;
+ *   d_log_n   DEVICE, on the context's GPU, [n_tables][n_nodes][n_mu], mu fastest, every value finite;
+ *   sin_k     NULL, or HOST [n_tables], as for the entries with a prefactor;
+ *   stream    the stream that produced d_log_n: the install runs on it, behind that work.
+ * So gamma == NULL, mu == NULL installs what rimphony_ctx_set_tables_2d (sin_k: _2d_pitchy) installs, gamma alone what
+ * rimphony_ctx_set_tables_2d_grid (_2d_grid_pitchy) installs, both what rimphony_ctx_set_tables_2d_nodes installs: the set on
+ * the device is that entry's set from the same numbers WORD FOR WORD -- headers, guides, node words, the four words per node
+ * and the normalisations -- so everything said of that form above holds unchanged.  The headers, guides and node words are
+ * built on the host as ever; the node data are solved on the device, one lane per spline line, with the swept diagonals of the
+ * two axes formed once on the host and every operation in the host solver's form; the normalisations are integrated by the
+ * form's own kernel.
+ * Refused with RIMPHONY_EINVAL, the previous set staying in place: the geometry the form's host entry refuses; a null
+ * d_log_n; a d_log_n that the runtime does not report as memory of the context's GPU holding the whole array (a host pointer,
+ * another GPU's memory); a non-finite value anywhere in d_log_n, which a kernel looks for before anything is built.
+ * RIMPHONY_ENOMEM likewise.  n_tables = 0 clears the set.  Synchronous like the host entries: `stream` has been synchronised
+ * when the call returns.  For the length of the call the new set, the previous one and d_log_n are all resident.  Not
+ * offered: the 1-D forms (their sets are small), an asynchronous install. */
+int rimphony_ctx_set_tables_2d_device(rimphony_ctx *ctx, size_t n_tables, size_t n_nodes, const double *gamma, double gamma_lo,
+                                      double gamma_hi, size_t n_mu, const double *mu, const double *d_log_n, const double *sin_k,
+                                      void *stream);
+
+/* Diagnostics: the installed table set as the kernels read it, copied to `out` (HOST, `cap` doubles).  *n_doubles is the
+ * size of the set in doubles, 0 (and nothing copied) where the context has none; RIMPHONY_EINVAL, with *n_doubles still set,
+ * where cap is smaller.  The set holds offsets, never addresses, so two installs of the same numbers -- through a host entry
+ * and through rimphony_ctx_set_tables_2d_device, say -- compare word for word. */
+int rimphony_debug_tables(rimphony_ctx *ctx, double *out, size_t cap, size_t *n_doubles);
+
 /* Work counters of the most recent batch call on this context (device-side
  * counts, read back synchronously): integrand samples, wave-wide evaluation
  * passes, inner QAG calls. */

@@ -174,6 +174,25 @@ extern "C" {
         sin_k: *const c_double,
     ) -> c_int;
 
+    /// Any of the six 2-D forms from ln n in device memory: `gamma` null for nodes uniform in ln gamma from `gamma_lo` to
+    /// `gamma_hi`, `mu` null for nodes uniform in mu, `sin_k` null for no prefactor; `d_log_n` a device pointer on the
+    /// context's GPU, `stream` the hipStream_t that produced it.
+    pub fn rimphony_ctx_set_tables_2d_device(
+        ctx: *mut rimphony_ctx,
+        n_tables: usize,
+        n_nodes: usize,
+        gamma: *const c_double,
+        gamma_lo: c_double,
+        gamma_hi: c_double,
+        n_mu: usize,
+        mu: *const c_double,
+        d_log_n: *const c_double,
+        sin_k: *const c_double,
+        stream: *mut c_void,
+    ) -> c_int;
+    /// The installed table set copied to the host: `n_doubles` receives its size, RIMPHONY_EINVAL where `cap` is smaller.
+    pub fn rimphony_debug_tables(ctx: *mut rimphony_ctx, out: *mut c_double, cap: usize, n_doubles: *mut usize) -> c_int;
+
     pub fn rimphony_last_work(ctx: *mut rimphony_ctx, out: *mut rimphony_work) -> c_int;
     pub fn rimphony_last_tail(ctx: *mut rimphony_ctx, out: *mut u64) -> c_int;
     pub fn rimphony_last_symphony_ms(ctx: *mut rimphony_ctx, ms: *mut c_float) -> c_int;

@@ -78,6 +78,7 @@ def build_hip(force=False, verbose=False):
                                     os.path.join(CSRC, "rimphony_tab_2d_nodes.hip"), os.path.join(CSRC, "rimphony_tab_2d_nodes_group.hip"),
                                     os.path.join(CSRC, "rimphony_tab_2d_nodes_pitchy.hip"),
                                     os.path.join(CSRC, "rimphony_tab_2d_nodes_pitchy_group.hip"),
+                                    os.path.join(CSRC, "rimphony_tab_install.hip"),
                                     "-ldl", "-o", LIB]
     if verbose:
         print(" ".join(cmd))

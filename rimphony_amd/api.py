@@ -182,15 +182,34 @@ def check_tables_2d(gamma_lo, gamma_hi, log_n):
     return t
 
 
-def check_tables_2d_grid(gamma, log_n):
-    """A 2-D table set on given nodes as rimphony_ctx_set_tables_2d_grid accepts it -> (gamma, log_n), contiguous float64
-    [n_nodes] and [n_tables][n_nodes][n_mu] (a 2-D array is one table); ValueError for what the library refuses with
-    RIMPHONY_EINVAL (the library itself judges whether the nodes' logarithms increase)."""
+def check_gamma_nodes(gamma):
+    """The gamma nodes of a 2-D set on given nodes -> contiguous float64 [n_nodes]; ValueError for what the library refuses
+    (it judges itself whether the nodes' logarithms increase)."""
     g = np.ascontiguousarray(np.asarray(gamma, dtype=np.float64))
     if g.ndim != 1 or not TAB_MIN_NODES <= g.shape[0] <= TAB_MAX_NODES:
         raise ValueError("gamma: expected %d to %d nodes, got shape %r" % (TAB_MIN_NODES, TAB_MAX_NODES, g.shape))
     if not np.isfinite(g).all() or not g[0] >= 1.0 or not (np.diff(g) > 0.0).all():
         raise ValueError("gamma: the nodes must be finite and strictly increasing from gamma[0] >= 1")
+    return g
+
+
+def check_mu_nodes(mu):
+    """The mu nodes of a 2-D set on given mu nodes -> contiguous float64 [n_mu]; ValueError for what the library refuses."""
+    m = np.ascontiguousarray(np.asarray(mu, dtype=np.float64))
+    if m.ndim != 1 or not TAB_2D_MIN_MU <= m.shape[0] <= TAB_2D_MAX_MU:
+        raise ValueError("mu: expected %d to %d nodes, got shape %r" % (TAB_2D_MIN_MU, TAB_2D_MAX_MU, m.shape))
+    if not np.isfinite(m).all() or not (np.diff(m) > 0.0).all():
+        raise ValueError("mu: the nodes must be finite and strictly increasing")
+    if m[0] != -1.0 or m[-1] != 1.0:
+        raise ValueError("mu: the first node must be -1 and the last +1 exactly")
+    return m
+
+
+def check_tables_2d_grid(gamma, log_n):
+    """A 2-D table set on given nodes as rimphony_ctx_set_tables_2d_grid accepts it -> (gamma, log_n), contiguous float64
+    [n_nodes] and [n_tables][n_nodes][n_mu] (a 2-D array is one table); ValueError for what the library refuses with
+    RIMPHONY_EINVAL (the library itself judges whether the nodes' logarithms increase)."""
+    g = check_gamma_nodes(gamma)
     t = check_tables_2d(float(g[0]), float(g[-1]), log_n)
     if t.shape[1] != g.shape[0]:
         raise ValueError("log_n: expected %d rows of mu nodes per table, one per gamma node, got %d" % (g.shape[0], t.shape[1]))
@@ -213,13 +232,7 @@ def check_tables_2d_nodes(gamma, mu, log_n):
     """A 2-D table set on given gamma and mu nodes as rimphony_ctx_set_tables_2d_nodes accepts it -> (gamma, mu, log_n),
     contiguous float64 [n_nodes], [n_mu] and [n_tables][n_nodes][n_mu] (a 2-D array is one table); ValueError for what the
     library refuses with RIMPHONY_EINVAL."""
-    m = np.ascontiguousarray(np.asarray(mu, dtype=np.float64))
-    if m.ndim != 1 or not TAB_2D_MIN_MU <= m.shape[0] <= TAB_2D_MAX_MU:
-        raise ValueError("mu: expected %d to %d nodes, got shape %r" % (TAB_2D_MIN_MU, TAB_2D_MAX_MU, m.shape))
-    if not np.isfinite(m).all() or not (np.diff(m) > 0.0).all():
-        raise ValueError("mu: the nodes must be finite and strictly increasing")
-    if m[0] != -1.0 or m[-1] != 1.0:
-        raise ValueError("mu: the first node must be -1 and the last +1 exactly")
+    m = check_mu_nodes(mu)
     g, t = check_tables_2d_grid(gamma, log_n)
     if t.shape[2] != m.shape[0]:
         raise ValueError("log_n: expected rows of %d values, one per mu node, got %d" % (m.shape[0], t.shape[2]))
@@ -325,6 +338,11 @@ class Context:
         if log_n is None:
             capi.check(self.lib.rimphony_ctx_set_tables_2d(self.handle, 0, 0, 1.0, 2.0, 0, None), "rimphony_ctx_set_tables_2d")
             return
+        if isinstance(log_n, torch.Tensor) and log_n.is_cuda:
+            if not (math.isfinite(gamma_lo) and math.isfinite(gamma_hi) and 1.0 <= gamma_lo < gamma_hi):
+                raise ValueError("expected 1 <= gamma_lo < gamma_hi, got %r, %r" % (gamma_lo, gamma_hi))
+            self._set_tables_2d_device(None, float(gamma_lo), float(gamma_hi), None, log_n, sin_k)
+            return
         t = check_tables_2d(gamma_lo, gamma_hi, log_n)
         if sin_k is not None:
             k = check_sin_k(sin_k, t.shape[0])
@@ -346,6 +364,9 @@ class Context:
         set_tables_2d (rimphony_ctx_set_tables_2d_grid_pitchy)."""
         if log_n is None:
             capi.check(self.lib.rimphony_ctx_set_tables_2d_grid(self.handle, 0, 0, None, 0, None), "rimphony_ctx_set_tables_2d_grid")
+            return
+        if isinstance(log_n, torch.Tensor) and log_n.is_cuda:
+            self._set_tables_2d_device(check_gamma_nodes(gamma), 1.0, 2.0, None, log_n, sin_k)
             return
         g, t = check_tables_2d_grid(gamma, log_n)
         dp = ctypes.POINTER(ctypes.c_double)
@@ -371,6 +392,9 @@ class Context:
             capi.check(self.lib.rimphony_ctx_set_tables_2d_nodes(self.handle, 0, 0, None, 0, None, None, None),
                        "rimphony_ctx_set_tables_2d_nodes")
             return
+        if isinstance(log_n, torch.Tensor) and log_n.is_cuda:
+            self._set_tables_2d_device(check_gamma_nodes(gamma), 1.0, 2.0, check_mu_nodes(mu), log_n, sin_k)
+            return
         g, m, t = check_tables_2d_nodes(gamma, mu, log_n)
         k = None if sin_k is None else check_sin_k(sin_k, t.shape[0])
         dp = ctypes.POINTER(ctypes.c_double)
@@ -378,6 +402,50 @@ class Context:
                                                              m.ctypes.data_as(dp), t.ctypes.data_as(dp),
                                                              None if k is None else k.ctypes.data_as(dp)),
                    "rimphony_ctx_set_tables_2d_nodes")
+
+    def _set_tables_2d_device(self, gamma, gamma_lo, gamma_hi, mu, log_n, sin_k):
+        """set_tables_2d, set_tables_2d_grid and set_tables_2d_nodes for a log_n that is a CUDA tensor: the same set, word for
+        word, solved on the GPU from where the tensor lies, on the current stream (include/rimphony_hip.h:
+        rimphony_ctx_set_tables_2d_device).  gamma, mu: validated host arrays or None; the tensor is held to the rules of
+        _check_input, [n_nodes][n_mu] or [n_tables][n_nodes][n_mu] within the form's limits.  The library itself looks for a
+        non-finite value.  Synchronous."""
+        if log_n.dim() not in (2, 3):
+            raise ValueError("log_n: expected [n_nodes][n_mu] or [n_tables][n_nodes][n_mu]")
+        self._check_input("log_n", log_n, log_n.numel())
+        nt, nn, nmu = (1,) + tuple(log_n.shape) if log_n.dim() == 2 else tuple(log_n.shape)
+        if nt < 1:
+            raise ValueError("log_n: expected [n_nodes][n_mu] or [n_tables][n_nodes][n_mu]")
+        if not TAB_MIN_NODES <= nn <= TAB_MAX_NODES:
+            raise ValueError("log_n: %d gamma nodes, expected %d .. %d" % (nn, TAB_MIN_NODES, TAB_MAX_NODES))
+        if not TAB_2D_MIN_MU <= nmu <= TAB_2D_MAX_MU:
+            raise ValueError("log_n: %d mu nodes, expected %d .. %d" % (nmu, TAB_2D_MIN_MU, TAB_2D_MAX_MU))
+        if nn * nmu > TAB_2D_MAX_CELLS:
+            raise ValueError("log_n: %d x %d nodes per table, at most %d" % (nn, nmu, TAB_2D_MAX_CELLS))
+        if gamma is not None and gamma.shape[0] != nn:
+            raise ValueError("log_n: expected %d rows of mu nodes per table, one per gamma node, got %d" % (gamma.shape[0], nn))
+        if mu is not None and mu.shape[0] != nmu:
+            raise ValueError("log_n: expected rows of %d values, one per mu node, got %d" % (mu.shape[0], nmu))
+        k = None if sin_k is None else check_sin_k(sin_k, nt)
+        dp = ctypes.POINTER(ctypes.c_double)
+        rc = self.lib.rimphony_ctx_set_tables_2d_device(
+            self.handle, nt, nn, None if gamma is None else gamma.ctypes.data_as(dp), gamma_lo, gamma_hi, nmu,
+            None if mu is None else mu.ctypes.data_as(dp), ctypes.c_void_p(log_n.data_ptr()),
+            None if k is None else k.ctypes.data_as(dp), self._stream())
+        capi.check(rc, "rimphony_ctx_set_tables_2d_device")
+
+    def tables_blob(self):
+        """The installed table set as the kernels read it, a float64 numpy array (empty without a set): headers, guides,
+        node words, spline words and normalisations, offsets instead of addresses -- two installs of the same numbers are
+        equal word for word (include/rimphony_hip.h: rimphony_debug_tables)."""
+        n = ctypes.c_size_t(0)
+        rc = self.lib.rimphony_debug_tables(self.handle, None, 0, ctypes.byref(n))
+        if n.value == 0:
+            capi.check(rc, "rimphony_debug_tables")
+            return np.zeros(0, dtype=np.float64)
+        out = np.empty(n.value, dtype=np.float64)
+        capi.check(self.lib.rimphony_debug_tables(self.handle, out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), n.value,
+                                                  ctypes.byref(n)), "rimphony_debug_tables")
+        return out
 
     def _check_input(self, name, t, n):
         """The C ABI takes raw device pointers and cannot see what they point to: refuse anything but a contiguous

@@ -23,6 +23,7 @@ SYMBOLS = [
     "rimphony_ctx_set_tables", "rimphony_ctx_set_tables_pitch", "rimphony_ctx_set_tables_2d", "rimphony_ctx_set_tables_pitchy",
     "rimphony_ctx_set_tables_grid", "rimphony_ctx_set_tables_2d_grid",
     "rimphony_ctx_set_tables_2d_pitchy", "rimphony_ctx_set_tables_2d_grid_pitchy", "rimphony_ctx_set_tables_2d_nodes",
+    "rimphony_ctx_set_tables_2d_device", "rimphony_debug_tables",
 ]
 
 
@@ -172,6 +173,12 @@ def load():
     if hasattr(lib, "rimphony_ctx_set_tables_2d_nodes"):
         lib.rimphony_ctx_set_tables_2d_nodes.restype = c_int
         lib.rimphony_ctx_set_tables_2d_nodes.argtypes = [c_void_p, c_size_t, c_size_t, dp, c_size_t, dp, dp, dp]
+    if hasattr(lib, "rimphony_ctx_set_tables_2d_device"):
+        lib.rimphony_ctx_set_tables_2d_device.restype = c_int
+        lib.rimphony_ctx_set_tables_2d_device.argtypes = [c_void_p, c_size_t, c_size_t, dp, c_double, c_double, c_size_t, dp,
+                                                          c_void_p, dp, c_void_p]
+        lib.rimphony_debug_tables.restype = c_int
+        lib.rimphony_debug_tables.argtypes = [c_void_p, dp, c_size_t, POINTER(c_size_t)]
     if hasattr(lib, "rimphony_ctx_set_tables_grid"):
         lib.rimphony_ctx_set_tables_grid.restype = c_int
         lib.rimphony_ctx_set_tables_grid.argtypes = [c_void_p, c_size_t, c_size_t, dp, dp, c_size_t, dp, dp]

@@ -571,10 +571,25 @@ static int check_tables(const rimphony_ctx *c, int kind)
 // prefactor and pitch rows (rim_tab_launch_pitchy_p), whose header is `fill_at` doubles into the set.  The new set is
 // complete on the device before the previous one is let go: a refusal or a failed allocation leaves the previous set in
 // place, and for the length of the call both are resident.
+//
+// With `dev`, `blob` is only the front of a 2-D set -- everything before its node data -- and the node data are solved on the
+// device from dev->d_log_n (rimphony_tab_install.hip), on dev->st, the stream that produced them; the whole install runs on
+// that stream.  This is the one path that sees values the host has not seen: a kernel looks for a non-finite one first, and
+// such a set is refused (RIMPHONY_EINVAL) like any other, before anything is built.
 typedef void (*RimTabFill)(unsigned grid, hipStream_t st, double *d_set, double *spill);
-static int install_tables(rimphony_ctx *c, const std::vector<double> &blob, int tab_kind, RimTabFill fill = nullptr, size_t fill_at = 0)
+struct RimTabDeviceNodes {
+    const double *d_log_n;
+    size_t n_tables, n_nodes, n_mu;
+    std::vector<double> axes;       // the axis block along u, then the one along mu (tab_install.h: rim_tab_install_axis)
+    double hu, hmu;
+    int grid_u, grid_mu;
+    hipStream_t st;
+};
+static int install_tables(rimphony_ctx *c, const std::vector<double> &blob, int tab_kind, RimTabFill fill = nullptr, size_t fill_at = 0,
+                          const RimTabDeviceNodes *dev = nullptr)
 {
-    RimCtxScope scope(c, nullptr);
+    const hipStream_t st = dev ? dev->st : nullptr;
+    RimCtxScope scope(c, st);
     int rc = scope.enter();
     if (rc) return rc;
     // the previous set may still be read by the context's earlier work
@@ -584,18 +599,56 @@ static int install_tables(rimphony_ctx *c, const std::vector<double> &blob, int 
         c->tab_kind = DIST_TABULATED_ISO;
         return RIMPHONY_OK;
     }
-    RimDevBuf<double> fresh = { nullptr, 0 };
-    rc = fresh.grow(blob.size(), blob.size() * sizeof(double), "the distribution tables");
-    if (rc) return rc;
+    const size_t node_doubles = dev ? dev->n_tables * dev->n_nodes * dev->n_mu * 4 : 0;
+    const size_t total = blob.size() + node_doubles;
+    RimDevBuf<double> fresh = { nullptr, 0 }, aux = { nullptr, 0 };
+    if (dev) {
+        // the axis blocks and, behind them, the word of the finiteness flag
+        rc = aux.grow(dev->axes.size() + 1, (dev->axes.size() + 1) * sizeof(double), "the spline axes of the distribution tables");
+        if (rc) return rc;
+        unsigned *d_flag = (unsigned *) (aux.p + dev->axes.size()), bad = 0;
+        hipError_t e = hipMemsetAsync(d_flag, 0, sizeof(double), st);
+        if (e == hipSuccess) {
+            rim_tab_install_launch_finite(st, dev->d_log_n, node_doubles / 4, d_flag);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipMemcpyAsync(&bad, d_flag, sizeof bad, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) {
+            rim_set_last_error("checking the distribution tables", hipGetErrorString(e));
+            aux.release();
+            return RIMPHONY_EHIP;
+        }
+        if (bad) { aux.release(); return RIMPHONY_EINVAL; }
+    }
+    rc = fresh.grow(total, total * sizeof(double), "the distribution tables");
+    if (rc) { aux.release(); return rc; }
     const unsigned grid = persistent_grid(c, (unsigned long long) blob[TAB_HDR_NTABLES], 16);
     rc = ensure_spill(c, grid);
-    if (rc) { fresh.release(); return rc; }
-    hipError_t e = hipMemcpy(fresh.p, blob.data(), blob.size() * sizeof(double), hipMemcpyHostToDevice);
+    if (rc) { fresh.release(); aux.release(); return rc; }
+    hipError_t e;
+    if (dev) {
+        e = hipMemcpyAsync(fresh.p, blob.data(), blob.size() * sizeof(double), hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(aux.p, dev->axes.data(), dev->axes.size() * sizeof(double), hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) {
+            RimTabInstall s;
+            s.log_n = dev->d_log_n;
+            s.nodes = fresh.p + blob.size();
+            s.n_tables = dev->n_tables; s.n_nodes = dev->n_nodes; s.n_mu = dev->n_mu;
+            s.au = rim_tab_axis_of(aux.p, dev->n_nodes, dev->hu, dev->grid_u);
+            s.amu = rim_tab_axis_of(aux.p + rim_tab_axis_doubles(dev->n_nodes), dev->n_mu, dev->hmu, dev->grid_mu);
+            rim_tab_install_launch_sweeps(st, s);
+            e = hipGetLastError();
+        }
+    } else {
+        e = hipMemcpy(fresh.p, blob.data(), blob.size() * sizeof(double), hipMemcpyHostToDevice);
+    }
     if (e == hipSuccess && fill) {
-        fill(grid, nullptr, fresh.p + fill_at, c->d_spill.p);
+        fill(grid, st, fresh.p + fill_at, c->d_spill.p);
         e = hipGetLastError();
     }
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    aux.release();
     if (e != hipSuccess) {
         rim_set_last_error("installing the distribution tables", hipGetErrorString(e));
         fresh.release();
@@ -740,6 +793,87 @@ extern "C" int rimphony_ctx_set_tables_2d_nodes(rimphony_ctx *c, size_t n_tables
     }
     if (sin_k) return install_tables(c, blob, DIST_TABULATED_2D_NODES_PITCHY, rim_tab_2d_nodes_pitchy_launch_table_norms);
     return install_tables(c, blob, DIST_TABULATED_2D_NODES, rim_tab_2d_nodes_launch_table_norms);
+}
+
+// 0 where [p, p + bytes) is device memory of `device` as the runtime knows it.  An error the queries leave behind is cleared:
+// it is this answer, not a failure of the install that follows.
+static int check_device_range(const void *p, size_t bytes, int device)
+{
+    hipPointerAttribute_t attr;
+    memset(&attr, 0, sizeof attr);
+    if (hipPointerGetAttributes(&attr, p) != hipSuccess) { (void) hipGetLastError(); return -1; }
+    if (attr.type != hipMemoryTypeDevice || attr.device != device) return -1;
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t) p) != hipSuccess) { (void) hipGetLastError(); return -1; }
+    const size_t off = (size_t) ((const char *) p - (const char *) base);
+    return (off <= size && bytes <= size - off) ? 0 : -1;
+}
+
+// Any of the six 2-D forms from ln n in device memory: gamma null, the nodes uniform in ln gamma; mu null, uniform in mu;
+// sin_k null, no prefactor.  The front of the set -- headers, guides, node words -- is the host entry's own
+// (tab_spline.h: rim_tab_front_2d*); the node data are solved on the device (install_tables), to the host entry's bits.
+extern "C" int rimphony_ctx_set_tables_2d_device(rimphony_ctx *c, size_t n_tables, size_t n_nodes, const double *gamma, double gamma_lo,
+                                                 double gamma_hi, size_t n_mu, const double *mu, const double *d_log_n,
+                                                 const double *sin_k, void *stream)
+{
+    if (!c) return RIMPHONY_EINVAL;
+    std::vector<double> blob;
+    if (!n_tables) return install_tables(c, blob, DIST_TABULATED_ISO);
+    if (!gamma && mu) return RIMPHONY_EINVAL;
+    if (!d_log_n) return RIMPHONY_EINVAL;
+    if (mu ? rim_tab_check_2d_nodes_geometry(n_tables, n_nodes, gamma, n_mu, mu, sin_k)
+           : gamma ? rim_tab_check_2d_grid_geometry(n_tables, n_nodes, gamma, n_mu)
+                   : rim_tab_check_2d_geometry(n_tables, n_nodes, gamma_lo, gamma_hi, n_mu))
+        return RIMPHONY_EINVAL;
+    if (sin_k && rim_tab_check_sin_k(n_tables, sin_k)) return RIMPHONY_EINVAL;
+    if (check_device_range(d_log_n, n_tables * n_nodes * n_mu * sizeof(double), c->device)) return RIMPHONY_EINVAL;
+    RimTabDeviceNodes dev;
+    dev.d_log_n = d_log_n;
+    dev.n_tables = n_tables; dev.n_nodes = n_nodes; dev.n_mu = n_mu;
+    dev.hu = 0.; dev.hmu = 0.;
+    dev.grid_u = gamma != nullptr; dev.grid_mu = mu != nullptr;
+    dev.st = (hipStream_t) stream;
+    int tab_kind;
+    RimTabFill fill;
+    try {
+        std::vector<double> h, ih, hm, ihm;
+        if (mu) {
+            rim_tab_front_2d_nodes(n_tables, n_nodes, gamma, n_mu, mu, sin_k, blob, h, ih, hm, ihm);
+            tab_kind = sin_k ? DIST_TABULATED_2D_NODES_PITCHY : DIST_TABULATED_2D_NODES;
+            fill = sin_k ? rim_tab_2d_nodes_pitchy_launch_table_norms : rim_tab_2d_nodes_launch_table_norms;
+        } else if (gamma) {
+            rim_tab_front_2d_grid(n_tables, n_nodes, gamma, n_mu, blob, h, ih, dev.hmu);
+            tab_kind = sin_k ? DIST_TABULATED_2D_GRID_PITCHY : DIST_TABULATED_2D_GRID;
+            fill = sin_k ? rim_tab_2d_grid_pitchy_launch_table_norms : rim_tab_2d_grid_launch_table_norms;
+        } else {
+            rim_tab_front_2d(n_tables, n_nodes, gamma_lo, gamma_hi, n_mu, blob, dev.hu, dev.hmu);
+            tab_kind = sin_k ? DIST_TABULATED_2D_PITCHY : DIST_TABULATED_2D;
+            fill = sin_k ? rim_tab_2d_pitchy_launch_table_norms : rim_tab_launch_table_norms;
+        }
+        if (sin_k && !mu) rim_tab_put_2d_sin_k(n_tables, sin_k, blob);
+        dev.axes.assign(rim_tab_axis_doubles(n_nodes) + rim_tab_axis_doubles(n_mu), 0.);
+        rim_tab_install_axis(n_nodes, dev.hu, gamma ? h.data() : nullptr, gamma ? ih.data() : nullptr, dev.axes.data());
+        rim_tab_install_axis(n_mu, dev.hmu, mu ? hm.data() : nullptr, mu ? ihm.data() : nullptr,
+                             dev.axes.data() + rim_tab_axis_doubles(n_nodes));
+    } catch (const std::bad_alloc &) { return RIMPHONY_ENOMEM; }
+    return install_tables(c, blob, tab_kind, fill, 0, &dev);
+}
+
+// The installed set as the kernels read it, copied to the host (diagnostics and tests).  It holds offsets, never addresses,
+// so two installs of the same numbers compare word for word.  *n_doubles: the size of the set, 0 for none; RIMPHONY_EINVAL
+// where `cap` doubles at `out` cannot hold it.
+extern "C" int rimphony_debug_tables(rimphony_ctx *c, double *out, size_t cap, size_t *n_doubles)
+{
+    if (!c || !n_doubles) return RIMPHONY_EINVAL;
+    RimCtxScope scope(c, nullptr);
+    int rc = scope.enter();
+    if (rc) return rc;
+    *n_doubles = c->d_tab.p ? c->d_tab.cap : 0;
+    if (!*n_doubles) return RIMPHONY_OK;
+    if (!out || cap < *n_doubles) return RIMPHONY_EINVAL;
+    HIP_TRY(hipMemcpy(out, c->d_tab.p, *n_doubles * sizeof(double), hipMemcpyDeviceToHost));
+    return RIMPHONY_OK;
 }
 
 static int rim_precision_check(const rimphony_ctx *c, int kind, int precision);

@@ -6,6 +6,7 @@
 
 #include "rimphony_internal.h"
 #include "coop_common.h"
+#include "tab_install.h"
 
 // what the persistent launch needs to know about a coop_kernel<P> instantiation
 struct RimCoopKernelInfo {
@@ -89,6 +90,12 @@ void rim_tab_2d_nodes_pitchy_launch_integrand(unsigned grid, hipStream_t st, con
 void rim_tab_2d_nodes_pitchy_launch_gamma_integral(unsigned grid, hipStream_t st, const PointArgs &pa, const double *d_norm, size_t count,
                                                    const double *d_n, double *d_out, double *spill);
 void rim_tab_2d_nodes_pitchy_launch_table_norms(unsigned grid, hipStream_t st, double *d_set, double *spill);
+
+// A 2-D set installed from device memory (rimphony_tab_install.hip, tab_install.h): *d_flag, zeroed by the caller, becomes 1
+// where one of the `count` values at d_log_n is not finite; the three families of sweeps that fill the node data of `s`, in
+// order on `st`.  Enqueue only, as everything here.
+void rim_tab_install_launch_finite(hipStream_t st, const double *d_log_n, size_t count, unsigned *d_flag);
+void rim_tab_install_launch_sweeps(hipStream_t st, const RimTabInstall &s);
 
 // RimCoopKernelInfo of coop_kernel<P>, `fn`
 template <class P>

@@ -36,6 +36,11 @@
 // set on given gamma nodes with the sweeps along mu on the non-uniform system too, a mu guide and one array of mu nodes per
 // set (dev_symphony.h: tab_2d_nodes_*), with or without a sin^k xi prefactor.
 //
+// The three 2-D builders begin with the FRONT of their set -- header, table headers, guides, node words: everything that does
+// not depend on log_n (rim_tab_front_2d, rim_tab_front_2d_grid, rim_tab_front_2d_nodes) -- and the three 2-D checks with a
+// geometry-only part (rim_tab_check_2d_geometry and its _grid_ and _nodes_ counterparts).  A set whose log_n lies in device
+// memory uses those parts alone and solves the node data on the device, to the same bits (tab_install.h).
+//
 // Plain C++ with the elementary functions of detmath.h, so that the library (hipcc's host pass) and the tests' table
 // oracle (g++) produce the same bits from the same table.
 #ifndef RIM_TAB_SPLINE_H
@@ -332,16 +337,41 @@ inline void rim_tab_build_grid(size_t n_tables, size_t n_nodes, const double *ga
 #define RIM_TAB_2D_MAX_MU 1024
 #define RIM_TAB_2D_MAX_CELLS ((size_t) 1 << 20)
 
+// what rim_tab_check_2d asks of everything but the values: for a caller whose log_n the host cannot read (tab_install.h)
+inline int rim_tab_check_2d_geometry(size_t n_tables, size_t n_nodes, double gamma_lo, double gamma_hi, size_t n_mu)
+{
+    if (n_tables < 1 || n_nodes < RIM_TAB_MIN_NODES || n_nodes > RIM_TAB_MAX_NODES) return -1;
+    if (n_mu < RIM_TAB_2D_MIN_MU || n_mu > RIM_TAB_2D_MAX_MU || n_nodes * n_mu > RIM_TAB_2D_MAX_CELLS) return -1;
+    if (n_tables > ((size_t) 1 << 40) / (n_nodes * n_mu)) return -1;
+    return rim_tab_check_range(gamma_lo, gamma_hi);
+}
+
 // a 2-D set: log_n [n_tables][n_nodes][n_mu], mu fastest.  0, or -1 for bad geometry or a non-finite value
 inline int rim_tab_check_2d(size_t n_tables, size_t n_nodes, double gamma_lo, double gamma_hi, size_t n_mu, const double *log_n)
 {
-    if (n_tables < 1 || n_nodes < RIM_TAB_MIN_NODES || n_nodes > RIM_TAB_MAX_NODES || !log_n) return -1;
-    if (n_mu < RIM_TAB_2D_MIN_MU || n_mu > RIM_TAB_2D_MAX_MU || n_nodes * n_mu > RIM_TAB_2D_MAX_CELLS) return -1;
-    if (n_tables > ((size_t) 1 << 40) / (n_nodes * n_mu)) return -1;
-    if (rim_tab_check_range(gamma_lo, gamma_hi)) return -1;
+    if (!log_n || rim_tab_check_2d_geometry(n_tables, n_nodes, gamma_lo, gamma_hi, n_mu)) return -1;
     for (size_t i = 0; i < n_tables * n_nodes * n_mu; i++)
         if (!rim_isfinite(log_n[i])) return -1;
     return 0;
+}
+
+// What a 2-D set holds in front of its node data, the words that do not depend on log_n: the header and the table headers
+// (normalisations 0).  h, hm: the node spacings along u and mu as the sweeps use them.  rim_tab_build_2d begins with it.
+inline void rim_tab_front_2d(size_t n_tables, size_t n_nodes, double gamma_lo, double gamma_hi, size_t n_mu, std::vector<double> &blob,
+                             double &h, double &hm)
+{
+    using namespace rim;
+    const double u_lo = rim_log(gamma_lo), u_hi = rim_log(gamma_hi);
+    h = (u_hi - u_lo) / (double) (n_nodes - 1);
+    hm = 2. / (double) (n_mu - 1);
+    blob.assign((size_t) TAB_HDR_DOUBLES + n_tables * TAB_2D_HDR, 0.);
+    rim_tab_set_header(blob.data(), n_tables, n_nodes, gamma_lo, gamma_hi, u_lo, 1. / h, h, -(double) n_mu);
+    for (size_t t = 0; t < n_tables; t++) {
+        double *th = blob.data() + TAB_HDR_DOUBLES + t * TAB_2D_HDR;
+        th[TAB_2D_LAST] = (double) (n_mu - 2);
+        th[TAB_2D_INVH] = 1. / hm;
+        th[TAB_2D_H] = hm;
+    }
 }
 
 // the 2-D set as one block of doubles (dev_symphony.h: TAB_2D_*); rim_tab_check_2d() has passed.  The order of the three
@@ -351,19 +381,13 @@ inline void rim_tab_build_2d(size_t n_tables, size_t n_nodes, double gamma_lo, d
                              std::vector<double> &blob)
 {
     using namespace rim;
-    const double u_lo = rim_log(gamma_lo), u_hi = rim_log(gamma_hi);
-    const double h = (u_hi - u_lo) / (double) (n_nodes - 1);
-    const double hm = 2. / (double) (n_mu - 1);
+    double h, hm;
+    rim_tab_front_2d(n_tables, n_nodes, gamma_lo, gamma_hi, n_mu, blob, h, hm);
     const size_t per_table = n_nodes * n_mu * 4;
-    blob.assign((size_t) TAB_HDR_DOUBLES + n_tables * TAB_2D_HDR + n_tables * per_table, 0.);
-    rim_tab_set_header(blob.data(), n_tables, n_nodes, gamma_lo, gamma_hi, u_lo, 1. / h, h, -(double) n_mu);
+    blob.resize(blob.size() + n_tables * per_table, 0.);
     const size_t longest = n_nodes > n_mu ? n_nodes : n_mu;
     std::vector<double> y(longest), pairs(2 * longest), cp(longest), dp(longest);
     for (size_t t = 0; t < n_tables; t++) {
-        double *th = blob.data() + TAB_HDR_DOUBLES + t * TAB_2D_HDR;
-        th[TAB_2D_LAST] = (double) (n_mu - 2);
-        th[TAB_2D_INVH] = 1. / hm;
-        th[TAB_2D_H] = hm;
         const double *src = log_n + t * n_nodes * n_mu;
         double *nodes = blob.data() + TAB_HDR_DOUBLES + n_tables * TAB_2D_HDR + t * per_table;
         for (size_t j = 0; j < n_mu; j++) {
@@ -387,27 +411,32 @@ inline void rim_tab_build_2d(size_t n_tables, size_t n_nodes, double gamma_lo, d
 }
 
 // rim_tab_check_2d() for a 2-D set on given nodes: gamma [n_nodes] as rim_tab_check_grid demands it, log_n
-// [n_tables][n_nodes][n_mu] and n_mu within the 2-D form's limits
+// [n_tables][n_nodes][n_mu] and n_mu within the 2-D form's limits; the _geometry form asks everything but the values
+inline int rim_tab_check_2d_grid_geometry(size_t n_tables, size_t n_nodes, const double *gamma, size_t n_mu)
+{
+    if (rim_tab_check_gamma_nodes(n_nodes, gamma)) return -1;
+    return rim_tab_check_2d_geometry(n_tables, n_nodes, gamma[0], gamma[n_nodes - 1], n_mu);
+}
+
 inline int rim_tab_check_2d_grid(size_t n_tables, size_t n_nodes, const double *gamma, size_t n_mu, const double *log_n)
 {
     if (rim_tab_check_gamma_nodes(n_nodes, gamma)) return -1;
     return rim_tab_check_2d(n_tables, n_nodes, gamma[0], gamma[n_nodes - 1], n_mu, log_n);
 }
 
-// the 2-D set on given nodes as one block of doubles (dev_symphony.h: tab_2d_grid_*); rim_tab_check_2d_grid() has passed.
-// The three families of sweeps in rim_tab_build_2d's order, those along u through rim_tab_spline_row_grid on h_i = u_{i+1} -
-// u_i; the guide as rim_tab_build_grid fills it.  The normalisation of a table is 0 as built and the caller fills it.
-inline void rim_tab_build_2d_grid(size_t n_tables, size_t n_nodes, const double *gamma, size_t n_mu, const double *log_n,
-                                  std::vector<double> &blob)
+// What a 2-D set on given gamma nodes holds in front of its node data: the header, the table headers (normalisations 0), the
+// guide and the u nodes.  h, ih [n_nodes]: u_{i+1} - u_i and its reciprocal as the sweeps along u use them (0 in the last
+// word); hm: the spacing of the mu nodes.  rim_tab_build_2d_grid begins with it.
+inline void rim_tab_front_2d_grid(size_t n_tables, size_t n_nodes, const double *gamma, size_t n_mu, std::vector<double> &blob,
+                                  std::vector<double> &h, std::vector<double> &ih, double &hm)
 {
     using namespace rim;
     size_t cells = 8;
     while (cells < n_nodes) cells *= 2;
-    const double hm = 2. / (double) (n_mu - 1);
-    const size_t per_table = n_nodes * n_mu * 4, nodes_at = tab_2d_grid_nodes_at(n_tables, n_nodes, cells);
-    blob.assign(nodes_at + n_tables * per_table, 0.);
-    const size_t longest = n_nodes > n_mu ? n_nodes : n_mu;
-    std::vector<double> u(n_nodes), h(n_nodes), ih(n_nodes), m(n_nodes), y(longest), pairs(2 * longest), cp(longest), dp(longest);
+    hm = 2. / (double) (n_mu - 1);
+    blob.assign(tab_2d_grid_nodes_at(n_tables, n_nodes, cells), 0.);
+    std::vector<double> u(n_nodes);
+    h.assign(n_nodes, 0.); ih.assign(n_nodes, 0.);
     for (size_t j = 0; j < n_nodes; j++) u[j] = rim_log(gamma[j]);
     for (size_t j = 0; j + 1 < n_nodes; j++) { h[j] = u[j + 1] - u[j]; ih[j] = 1. / h[j]; }
     h[n_nodes - 1] = 0.; ih[n_nodes - 1] = 0.;
@@ -421,6 +450,24 @@ inline void rim_tab_build_2d_grid(size_t n_tables, size_t n_nodes, const double 
         th[TAB_2D_LAST] = (double) (n_mu - 2);
         th[TAB_2D_INVH] = 1. / hm;
         th[TAB_2D_H] = hm;
+    }
+}
+
+// the 2-D set on given nodes as one block of doubles (dev_symphony.h: tab_2d_grid_*); rim_tab_check_2d_grid() has passed.
+// The three families of sweeps in rim_tab_build_2d's order, those along u through rim_tab_spline_row_grid on h_i = u_{i+1} -
+// u_i; the guide as rim_tab_build_grid fills it.  The normalisation of a table is 0 as built and the caller fills it.
+inline void rim_tab_build_2d_grid(size_t n_tables, size_t n_nodes, const double *gamma, size_t n_mu, const double *log_n,
+                                  std::vector<double> &blob)
+{
+    using namespace rim;
+    std::vector<double> h, ih;
+    double hm;
+    rim_tab_front_2d_grid(n_tables, n_nodes, gamma, n_mu, blob, h, ih, hm);
+    const size_t per_table = n_nodes * n_mu * 4, nodes_at = blob.size();
+    blob.resize(nodes_at + n_tables * per_table, 0.);
+    const size_t longest = n_nodes > n_mu ? n_nodes : n_mu;
+    std::vector<double> m(n_nodes), y(longest), pairs(2 * longest), cp(longest), dp(longest);
+    for (size_t t = 0; t < n_tables; t++) {
         const double *src = log_n + t * n_nodes * n_mu;
         double *nodes = blob.data() + nodes_at + t * per_table;
         for (size_t j = 0; j < n_mu; j++) {
@@ -494,7 +541,16 @@ inline int rim_tab_check_mu_nodes(size_t n_mu, const double *mu)
     return 0;
 }
 
-// rim_tab_check_2d_grid() for a set on given mu nodes too; sin_k may be null (no prefactor)
+// rim_tab_check_2d_grid() for a set on given mu nodes too; sin_k may be null (no prefactor).  The _geometry form asks
+// everything but the values.
+inline int rim_tab_check_2d_nodes_geometry(size_t n_tables, size_t n_nodes, const double *gamma, size_t n_mu, const double *mu,
+                                           const double *sin_k)
+{
+    if (rim_tab_check_mu_nodes(n_mu, mu)) return -1;
+    if (rim_tab_check_2d_grid_geometry(n_tables, n_nodes, gamma, n_mu)) return -1;
+    return sin_k ? rim_tab_check_sin_k(n_tables, sin_k) : 0;
+}
+
 inline int rim_tab_check_2d_nodes(size_t n_tables, size_t n_nodes, const double *gamma, size_t n_mu, const double *mu,
                                   const double *log_n, const double *sin_k)
 {
@@ -503,24 +559,22 @@ inline int rim_tab_check_2d_nodes(size_t n_tables, size_t n_nodes, const double 
     return sin_k ? rim_tab_check_sin_k(n_tables, sin_k) : 0;
 }
 
-// the 2-D set on given gamma and mu nodes as one block of doubles (dev_symphony.h: tab_2d_nodes_*); rim_tab_check_2d_nodes()
-// has passed.  The three families of sweeps in rim_tab_build_2d's order, all of them through rim_tab_spline_row_grid: along u
-// on h_i = u_{i+1} - u_i, along mu on h_j = mu_{j+1} - mu_j, each with its 1 / h formed once per set.  Both guides as
-// rim_tab_build_grid fills its one.  sin_k null: TAB_2D_K stays 0.  The normalisation of a table is 0 as built.
-inline void rim_tab_build_2d_nodes(size_t n_tables, size_t n_nodes, const double *gamma, size_t n_mu, const double *mu,
-                                   const double *log_n, const double *sin_k, std::vector<double> &blob)
+// What a 2-D set on given gamma and mu nodes holds in front of its node data: the header, the table headers with sin_k (null:
+// 0) and normalisations 0, both guides and both node arrays.  h, ih [n_nodes] and hm, ihm [n_mu]: the node distances and their
+// reciprocals as the sweeps use them (0 in the last word).  rim_tab_build_2d_nodes begins with it.
+inline void rim_tab_front_2d_nodes(size_t n_tables, size_t n_nodes, const double *gamma, size_t n_mu, const double *mu,
+                                   const double *sin_k, std::vector<double> &blob, std::vector<double> &h, std::vector<double> &ih,
+                                   std::vector<double> &hm, std::vector<double> &ihm)
 {
     using namespace rim;
     size_t cells = 8, mu_cells = 8;
     while (cells < n_nodes) cells *= 2;
     while (mu_cells < n_mu) mu_cells *= 2;
-    const size_t per_table = n_nodes * n_mu * 4;
     const size_t mu_guide_at = tab_2d_nodes_mu_guide_at(n_tables, n_nodes, cells);
     const size_t mu_nodes_at = mu_guide_at + tab_grid_guide_doubles(mu_cells);
-    const size_t nodes_at = tab_2d_nodes_nodes_at(n_tables, n_nodes, cells, n_mu, mu_cells);
-    blob.assign(nodes_at + n_tables * per_table, 0.);
-    const size_t longest = n_nodes > n_mu ? n_nodes : n_mu;
-    std::vector<double> u(n_nodes), h(n_nodes), ih(n_nodes), hm(n_mu), ihm(n_mu), col(longest), m(longest), cp(longest), dp(longest);
+    blob.assign(tab_2d_nodes_nodes_at(n_tables, n_nodes, cells, n_mu, mu_cells), 0.);
+    std::vector<double> u(n_nodes);
+    h.assign(n_nodes, 0.); ih.assign(n_nodes, 0.); hm.assign(n_mu, 0.); ihm.assign(n_mu, 0.);
     for (size_t j = 0; j < n_nodes; j++) u[j] = rim_log(gamma[j]);
     for (size_t j = 0; j + 1 < n_nodes; j++) { h[j] = u[j + 1] - u[j]; ih[j] = 1. / h[j]; }
     h[n_nodes - 1] = 0.; ih[n_nodes - 1] = 0.;
@@ -544,6 +598,24 @@ inline void rim_tab_build_2d_nodes(size_t n_tables, size_t n_nodes, const double
         th[TAB_2D_K] = sin_k ? sin_k[t] : 0.;
         th[TAB_2D_MU_GUIDE] = (double) (mu_guide_at - th_at);
         th[TAB_2D_MU_NODES] = (double) (mu_nodes_at - th_at);
+    }
+}
+
+// the 2-D set on given gamma and mu nodes as one block of doubles (dev_symphony.h: tab_2d_nodes_*); rim_tab_check_2d_nodes()
+// has passed.  The three families of sweeps in rim_tab_build_2d's order, all of them through rim_tab_spline_row_grid: along u
+// on h_i = u_{i+1} - u_i, along mu on h_j = mu_{j+1} - mu_j, each with its 1 / h formed once per set.  Both guides as
+// rim_tab_build_grid fills its one.  sin_k null: TAB_2D_K stays 0.  The normalisation of a table is 0 as built.
+inline void rim_tab_build_2d_nodes(size_t n_tables, size_t n_nodes, const double *gamma, size_t n_mu, const double *mu,
+                                   const double *log_n, const double *sin_k, std::vector<double> &blob)
+{
+    using namespace rim;
+    std::vector<double> h, ih, hm, ihm;
+    rim_tab_front_2d_nodes(n_tables, n_nodes, gamma, n_mu, mu, sin_k, blob, h, ih, hm, ihm);
+    const size_t per_table = n_nodes * n_mu * 4, nodes_at = blob.size();
+    blob.resize(nodes_at + n_tables * per_table, 0.);
+    const size_t longest = n_nodes > n_mu ? n_nodes : n_mu;
+    std::vector<double> col(longest), m(longest), cp(longest), dp(longest);
+    for (size_t t = 0; t < n_tables; t++) {
         const double *src = log_n + t * n_nodes * n_mu;
         double *nodes = blob.data() + nodes_at + t * per_table;
         for (size_t j = 0; j < n_mu; j++) {

@@ -165,6 +165,33 @@ public:
                                                sin_k.empty() ? nullptr : sin_k.data()),
               "rimphony_ctx_set_tables_2d_nodes");
     }
+    // Any 2-D form from ln n in device memory (rimphony_ctx_set_tables_2d_device): d_log_n [n_tables][n_nodes][n_mu] on this
+    // context's GPU, produced on `stream`.  gamma empty: n_nodes nodes uniform in ln gamma from gamma_lo to gamma_hi, else
+    // gamma holds the nodes and the two are not read; mu empty: n_mu nodes uniform in mu, else mu holds them (mu without
+    // gamma is refused); sin_k empty or [n_tables].  The set is the host entry's, word for word.  Synchronous.
+    void set_tables_2d_device(size_t n_tables, size_t n_nodes, const std::vector<double> &gamma, double gamma_lo, double gamma_hi,
+                              size_t n_mu, const std::vector<double> &mu, const double *d_log_n,
+                              const std::vector<double> &sin_k = {}, void *stream = nullptr) const
+    {
+        if ((!gamma.empty() && gamma.size() != n_nodes) || (!mu.empty() && mu.size() != n_mu))
+            throw std::runtime_error("set_tables_2d_device: gamma and mu must be empty or hold n_nodes and n_mu values");
+        if (!sin_k.empty() && sin_k.size() != n_tables)
+            throw std::runtime_error("set_tables_2d_device: sin_k must be empty or hold n_tables values");
+        check(rimphony_ctx_set_tables_2d_device(ctx_, n_tables, n_nodes, gamma.empty() ? nullptr : gamma.data(), gamma_lo, gamma_hi,
+                                                n_mu, mu.empty() ? nullptr : mu.data(), d_log_n,
+                                                sin_k.empty() ? nullptr : sin_k.data(), stream),
+              "rimphony_ctx_set_tables_2d_device");
+    }
+    // the installed set as the kernels read it, copied to the host (rimphony_debug_tables); empty without a set
+    std::vector<double> tables_blob() const
+    {
+        size_t n = 0;
+        const int rc = rimphony_debug_tables(ctx_, nullptr, 0, &n);
+        if (!n) { check(rc, "rimphony_debug_tables"); return {}; }
+        std::vector<double> out(n);
+        check(rimphony_debug_tables(ctx_, out.data(), out.size(), &n), "rimphony_debug_tables");
+        return out;
+    }
 private:
     rimphony_ctx *ctx_ = nullptr;
 };
