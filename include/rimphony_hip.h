@@ -384,6 +384,36 @@ int rimphony_ctx_set_tables_2d_device(rimphony_ctx *ctx, size_t n_tables, size_t
                                       double gamma_hi, size_t n_mu, const double *mu, const double *d_log_n, const double *sin_k,
                                       void *stream);
 
+/* The ends of the spline of a 2-D set, a choice per axis.  Every 2-D entry above interpolates with NATURAL ends: the second
+ * derivative of S across an end node is 0 -- S_uu = 0 at both ends of the gamma nodes, S_mumu = 0 at mu = +-1.  Along gamma the
+ * caller tapers the table and the ends carry nothing.  Along mu there is nothing to taper: mu = +-1 is the field direction,
+ * and a smooth distribution on the sphere generally has curvature there (a bi-Maxwellian's ln n is quadratic in mu).  With
+ * natural ends the error of S_mu near the pole falls only like the node distance, and S_mu is what df/dmu = f S_mu feeds into
+ * every absorption coefficient and into rho_Q and rho_V.  NOT-A-KNOT ends make the third derivative of S continuous across
+ * the second and the second-to-last node instead: every cubic along the axis comes back as itself, and the error is O(h^4) up
+ * to the edge (profiles/tabulated_2d_ends_accuracy.txt has the figures).
+ * The two entries below are rimphony_ctx_set_tables_2d_device's shape, for ln n in HOST memory and in DEVICE memory: one entry
+ * for all six 2-D forms, gamma, mu and sin_k NULL or given with the meaning they have there.
+ *   ends_gamma   governs the sweeps along ln gamma (S_u and S_umu), ends_mu the sweeps along mu (S_mu): each
+ *                RIMPHONY_TAB_ENDS_NATURAL or RIMPHONY_TAB_ENDS_NOT_A_KNOT.  Any other value is RIMPHONY_EINVAL, and the
+ *                previous set stays;
+ *   everything else as for the form's own entry, which is what checks and builds the set: what it refuses is refused here,
+ *                n_tables = 0 clears, a set of any form is replaced.
+ * With natural ends on both axes each installs exactly the set of the form's existing entry, word for word; the device entry
+ * installs the host entry's set word for word for every choice.  The choice costs nothing per sample: the kernels read {S,
+ * S_u, S_mu, S_umu} per node and never ask how they were solved.  It is recorded in a spare word of each table's header
+ * (ends_gamma + 2 ends_mu; rimphony_debug_tables shows it) that no kernel reads.
+ * Not offered: the 1-D forms (a separable table can be given as a surface); clamped ends with slopes given by the caller; a
+ * choice per table. */
+#define RIMPHONY_TAB_ENDS_NATURAL 0
+#define RIMPHONY_TAB_ENDS_NOT_A_KNOT 1
+int rimphony_ctx_set_tables_2d_ends(rimphony_ctx *ctx, size_t n_tables, size_t n_nodes, const double *gamma, double gamma_lo,
+                                    double gamma_hi, size_t n_mu, const double *mu, const double *log_n, const double *sin_k,
+                                    int ends_gamma, int ends_mu);
+int rimphony_ctx_set_tables_2d_device_ends(rimphony_ctx *ctx, size_t n_tables, size_t n_nodes, const double *gamma, double gamma_lo,
+                                           double gamma_hi, size_t n_mu, const double *mu, const double *d_log_n,
+                                           const double *sin_k, int ends_gamma, int ends_mu, void *stream);
+
 /* Diagnostics: the installed table set as the kernels read it, copied to `out` (HOST, `cap` doubles).  *n_doubles is the
  * size of the set in doubles, 0 (and nothing copied) where the context has none; RIMPHONY_EINVAL, with *n_doubles still set,
  * where cap is smaller.  The set holds offsets, never addresses, so two installs of the same numbers -- through a host entry

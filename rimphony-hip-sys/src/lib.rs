@@ -44,6 +44,10 @@ pub const RIMPHONY_PITCHY_PL: c_int = 2; // p, k, gamma_min, gamma_max, gamma_cu
 pub const RIMPHONY_PITCHY_KAPPA: c_int = 3; // kappa, width, k, gamma_cutoff
 pub const RIMPHONY_TABULATED: c_int = 4; // table index (the set: rimphony_ctx_set_tables)
 
+// the ends of the spline of a 2-D table set, per axis (rimphony_ctx_set_tables_2d_ends)
+pub const RIMPHONY_TAB_ENDS_NATURAL: c_int = 0;
+pub const RIMPHONY_TAB_ENDS_NOT_A_KNOT: c_int = 1;
+
 // coeff_mask bits = output slots, in the order of compute_all_dimensionless (lib.rs:176-177)
 pub const RIMPHONY_SLOT_J_I: u32 = 1 << 0;
 pub const RIMPHONY_SLOT_ALPHA_I: u32 = 1 << 1;
@@ -188,6 +192,39 @@ extern "C" {
         mu: *const c_double,
         d_log_n: *const c_double,
         sin_k: *const c_double,
+        stream: *mut c_void,
+    ) -> c_int;
+    /// Any of the six 2-D forms from ln n in host memory with a choice of the spline's ends per axis: `ends_gamma` and
+    /// `ends_mu` are RIMPHONY_TAB_ENDS_NATURAL or RIMPHONY_TAB_ENDS_NOT_A_KNOT; `gamma`, `mu` and `sin_k` null or given as
+    /// for rimphony_ctx_set_tables_2d_device.  Natural ends on both axes install the set of the form's own entry.
+    pub fn rimphony_ctx_set_tables_2d_ends(
+        ctx: *mut rimphony_ctx,
+        n_tables: usize,
+        n_nodes: usize,
+        gamma: *const c_double,
+        gamma_lo: c_double,
+        gamma_hi: c_double,
+        n_mu: usize,
+        mu: *const c_double,
+        log_n: *const c_double,
+        sin_k: *const c_double,
+        ends_gamma: c_int,
+        ends_mu: c_int,
+    ) -> c_int;
+    /// The same from ln n in device memory, on `stream`: the host entry's set, word for word.
+    pub fn rimphony_ctx_set_tables_2d_device_ends(
+        ctx: *mut rimphony_ctx,
+        n_tables: usize,
+        n_nodes: usize,
+        gamma: *const c_double,
+        gamma_lo: c_double,
+        gamma_hi: c_double,
+        n_mu: usize,
+        mu: *const c_double,
+        d_log_n: *const c_double,
+        sin_k: *const c_double,
+        ends_gamma: c_int,
+        ends_mu: c_int,
         stream: *mut c_void,
     ) -> c_int;
     /// The installed table set copied to the host: `n_doubles` receives its size, RIMPHONY_EINVAL where `cap` is smaller.

@@ -195,6 +195,12 @@ def build_tab2d_nodes_oracle():
     return _build_dist_oracle("tab2d_nodes_oracle.cpp", "liboracle_tab2dnodes.so")
 
 
+def build_tab2d_ends_oracle():
+    """The same for 2-D table sets of any of the six forms with a choice of the spline's ends per axis, and the host build
+    of the per-line solver of the device install (tests/support/tab2d_ends_oracle.cpp)."""
+    return _build_dist_oracle("tab2d_ends_oracle.cpp", "liboracle_tab2dends.so")
+
+
 def build_pitchy_tilt_oracle():
     """The CPU oracle of the analytic tilted power law times sin^k xi (tests/support/pitchy_tilt_oracle.cpp): what the 2-D
     tables with a sin^k prefactor are compared with.  Tests only."""

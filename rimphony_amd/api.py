@@ -239,6 +239,35 @@ def check_tables_2d_nodes(gamma, mu, log_n):
     return g, m, t
 
 
+TAB_ENDS_NATURAL, TAB_ENDS_NOT_A_KNOT = 0, 1
+_TAB_ENDS = {"natural": TAB_ENDS_NATURAL, "not-a-knot": TAB_ENDS_NOT_A_KNOT}
+
+
+def check_ends(ends):
+    """The ends of the spline of a 2-D set -> (ends_gamma, ends_mu), each TAB_ENDS_NATURAL or TAB_ENDS_NOT_A_KNOT, or None for
+    None (the entries that know of no choice).  ends: "natural" or "not-a-knot" for both axes, or a pair (gamma_end, mu_end)
+    of those names or values.  ValueError for anything else (include/rimphony_hip.h: rimphony_ctx_set_tables_2d_ends)."""
+    if ends is None:
+        return None
+
+    def one(e):
+        if isinstance(e, str):
+            if e not in _TAB_ENDS:
+                raise ValueError("ends: expected 'natural' or 'not-a-knot', got %r" % (e,))
+            return _TAB_ENDS[e]
+        if isinstance(e, (bool, float)) or e not in (TAB_ENDS_NATURAL, TAB_ENDS_NOT_A_KNOT):
+            raise ValueError("ends: expected 'natural' or 'not-a-knot', got %r" % (e,))
+        return int(e)
+
+    if isinstance(ends, str):
+        return one(ends), one(ends)
+    try:
+        eg, em = ends
+    except (TypeError, ValueError):
+        raise ValueError("ends: expected 'natural', 'not-a-knot' or a pair (gamma_end, mu_end), got %r" % (ends,))
+    return one(eg), one(em)
+
+
 class Context:
     """Owns a rimphony_ctx bound to one GPU."""
 
@@ -326,7 +355,7 @@ class Context:
                                                          None if k is None else k.ctypes.data_as(dp)),
                    "rimphony_ctx_set_tables_grid")
 
-    def set_tables_2d(self, gamma_lo, gamma_hi, log_n, sin_k=None):
+    def set_tables_2d(self, gamma_lo, gamma_hi, log_n, sin_k=None, ends=None):
         """The context's table set for kind TABULATED as surfaces: log_n [n_tables][n_nodes][n_mu] (a 2-D array is one
         table) = ln n(gamma, mu) at nodes uniform in ln gamma from gamma_lo to gamma_hi and uniform in mu = cos xi from -1
         to +1; f = norm exp(S) / (gamma^2 beta) with S the tensor-product natural cubic spline.  Replaces the previous set of
@@ -334,16 +363,23 @@ class Context:
         (include/rimphony_hip.h: rimphony_ctx_set_tables_2d).
         sin_k (a scalar, or one value per table, each in [0, 100]) multiplies each table by sin^k xi in closed form, f =
         norm sin^k xi exp(S) / (gamma^2 beta): for a distribution that vanishes along the field, whose ln n no surface can
-        hold.  log_n is then the smooth remainder, ln(n / sin^k xi) (rimphony_ctx_set_tables_2d_pitchy)."""
+        hold.  log_n is then the smooth remainder, ln(n / sin^k xi) (rimphony_ctx_set_tables_2d_pitchy).
+        ends chooses the ends of the spline: None or "natural" (S'' = 0 across the end nodes), "not-a-knot" (every cubic
+        along an axis comes back as itself: for a surface curved at mu = +-1, a bi-Maxwellian say), or a pair (gamma_end,
+        mu_end) (check_ends; rimphony_ctx_set_tables_2d_ends).  It costs nothing per sample."""
+        ends = check_ends(ends)
         if log_n is None:
             capi.check(self.lib.rimphony_ctx_set_tables_2d(self.handle, 0, 0, 1.0, 2.0, 0, None), "rimphony_ctx_set_tables_2d")
             return
         if isinstance(log_n, torch.Tensor) and log_n.is_cuda:
             if not (math.isfinite(gamma_lo) and math.isfinite(gamma_hi) and 1.0 <= gamma_lo < gamma_hi):
                 raise ValueError("expected 1 <= gamma_lo < gamma_hi, got %r, %r" % (gamma_lo, gamma_hi))
-            self._set_tables_2d_device(None, float(gamma_lo), float(gamma_hi), None, log_n, sin_k)
+            self._set_tables_2d_device(None, float(gamma_lo), float(gamma_hi), None, log_n, sin_k, ends)
             return
         t = check_tables_2d(gamma_lo, gamma_hi, log_n)
+        if ends is not None:
+            self._set_tables_2d_ends(None, float(gamma_lo), float(gamma_hi), None, t, sin_k, ends)
+            return
         if sin_k is not None:
             k = check_sin_k(sin_k, t.shape[0])
             dp = ctypes.POINTER(ctypes.c_double)
@@ -355,20 +391,24 @@ class Context:
                                                        t.shape[2], t.ctypes.data_as(ctypes.POINTER(ctypes.c_double))),
                    "rimphony_ctx_set_tables_2d")
 
-    def set_tables_2d_grid(self, gamma, log_n, sin_k=None):
+    def set_tables_2d_grid(self, gamma, log_n, sin_k=None, ends=None):
         """The context's table set as surfaces on gamma nodes of the caller's choosing: gamma [n_nodes] strictly increasing
         from >= 1, shared by the tables; log_n [n_tables][n_nodes][n_mu] (a 2-D array is one table) = ln n(gamma_i, mu_j),
         the mu nodes uniform from -1 to +1.  What set_tables_2d holds, on the nodes set_tables_grid takes: a cold core under
         an anisotropic tail.  Replaces the previous set of any form; log_n None clears it.  Synchronous: the normalisation of
         every table is integrated here, once (include/rimphony_hip.h: rimphony_ctx_set_tables_2d_grid).  sin_k as for
-        set_tables_2d (rimphony_ctx_set_tables_2d_grid_pitchy)."""
+        set_tables_2d (rimphony_ctx_set_tables_2d_grid_pitchy), and so ends."""
+        ends = check_ends(ends)
         if log_n is None:
             capi.check(self.lib.rimphony_ctx_set_tables_2d_grid(self.handle, 0, 0, None, 0, None), "rimphony_ctx_set_tables_2d_grid")
             return
         if isinstance(log_n, torch.Tensor) and log_n.is_cuda:
-            self._set_tables_2d_device(check_gamma_nodes(gamma), 1.0, 2.0, None, log_n, sin_k)
+            self._set_tables_2d_device(check_gamma_nodes(gamma), 1.0, 2.0, None, log_n, sin_k, ends)
             return
         g, t = check_tables_2d_grid(gamma, log_n)
+        if ends is not None:
+            self._set_tables_2d_ends(g, 1.0, 2.0, None, t, sin_k, ends)
+            return
         dp = ctypes.POINTER(ctypes.c_double)
         if sin_k is not None:
             k = check_sin_k(sin_k, t.shape[0])
@@ -381,21 +421,25 @@ class Context:
                    "rimphony_ctx_set_tables_2d_grid")
 
     # -- batched compute() -------------------------------------------------------
-    def set_tables_2d_nodes(self, gamma, mu, log_n, sin_k=None):
+    def set_tables_2d_nodes(self, gamma, mu, log_n, sin_k=None, ends=None):
         """The context's table set as surfaces on gamma nodes AND mu nodes of the caller's choosing: gamma [n_nodes] strictly
         increasing from >= 1 and mu [n_mu] strictly increasing from exactly -1 to exactly +1, both shared by the tables;
         log_n [n_tables][n_nodes][n_mu] (a 2-D array is one table) = ln n(gamma_i, mu_j).  What set_tables_2d_grid holds, on
         mu nodes graded towards a beam, a ring or the edge of a loss cone, or uniform in xi (mu_nodes_uniform_in_xi).
-        sin_k as for set_tables_2d.  Replaces the previous set of any form; log_n None clears it.  Synchronous: the
+        sin_k and ends as for set_tables_2d.  Replaces the previous set of any form; log_n None clears it.  Synchronous: the
         normalisation of every table is integrated here, once (include/rimphony_hip.h: rimphony_ctx_set_tables_2d_nodes)."""
+        ends = check_ends(ends)
         if log_n is None:
             capi.check(self.lib.rimphony_ctx_set_tables_2d_nodes(self.handle, 0, 0, None, 0, None, None, None),
                        "rimphony_ctx_set_tables_2d_nodes")
             return
         if isinstance(log_n, torch.Tensor) and log_n.is_cuda:
-            self._set_tables_2d_device(check_gamma_nodes(gamma), 1.0, 2.0, check_mu_nodes(mu), log_n, sin_k)
+            self._set_tables_2d_device(check_gamma_nodes(gamma), 1.0, 2.0, check_mu_nodes(mu), log_n, sin_k, ends)
             return
         g, m, t = check_tables_2d_nodes(gamma, mu, log_n)
+        if ends is not None:
+            self._set_tables_2d_ends(g, 1.0, 2.0, m, t, sin_k, ends)
+            return
         k = None if sin_k is None else check_sin_k(sin_k, t.shape[0])
         dp = ctypes.POINTER(ctypes.c_double)
         capi.check(self.lib.rimphony_ctx_set_tables_2d_nodes(self.handle, t.shape[0], t.shape[1], g.ctypes.data_as(dp), t.shape[2],
@@ -403,12 +447,24 @@ class Context:
                                                              None if k is None else k.ctypes.data_as(dp)),
                    "rimphony_ctx_set_tables_2d_nodes")
 
-    def _set_tables_2d_device(self, gamma, gamma_lo, gamma_hi, mu, log_n, sin_k):
+    def _set_tables_2d_ends(self, gamma, gamma_lo, gamma_hi, mu, t, sin_k, ends):
+        """set_tables_2d, set_tables_2d_grid and set_tables_2d_nodes for a numpy log_n with a choice of ends: gamma, mu and
+        t validated host arrays (gamma, mu None where the form places its own nodes), ends a pair from check_ends
+        (include/rimphony_hip.h: rimphony_ctx_set_tables_2d_ends)."""
+        k = None if sin_k is None else check_sin_k(sin_k, t.shape[0])
+        dp = ctypes.POINTER(ctypes.c_double)
+        rc = self.lib.rimphony_ctx_set_tables_2d_ends(
+            self.handle, t.shape[0], t.shape[1], None if gamma is None else gamma.ctypes.data_as(dp), gamma_lo, gamma_hi, t.shape[2],
+            None if mu is None else mu.ctypes.data_as(dp), t.ctypes.data_as(dp), None if k is None else k.ctypes.data_as(dp),
+            ends[0], ends[1])
+        capi.check(rc, "rimphony_ctx_set_tables_2d_ends")
+
+    def _set_tables_2d_device(self, gamma, gamma_lo, gamma_hi, mu, log_n, sin_k, ends=None):
         """set_tables_2d, set_tables_2d_grid and set_tables_2d_nodes for a log_n that is a CUDA tensor: the same set, word for
         word, solved on the GPU from where the tensor lies, on the current stream (include/rimphony_hip.h:
         rimphony_ctx_set_tables_2d_device).  gamma, mu: validated host arrays or None; the tensor is held to the rules of
         _check_input, [n_nodes][n_mu] or [n_tables][n_nodes][n_mu] within the form's limits.  The library itself looks for a
-        non-finite value.  Synchronous."""
+        non-finite value.  Synchronous.  ends: None, or a pair from check_ends (rimphony_ctx_set_tables_2d_device_ends)."""
         if log_n.dim() not in (2, 3):
             raise ValueError("log_n: expected [n_nodes][n_mu] or [n_tables][n_nodes][n_mu]")
         self._check_input("log_n", log_n, log_n.numel())
@@ -427,6 +483,13 @@ class Context:
             raise ValueError("log_n: expected rows of %d values, one per mu node, got %d" % (mu.shape[0], nmu))
         k = None if sin_k is None else check_sin_k(sin_k, nt)
         dp = ctypes.POINTER(ctypes.c_double)
+        if ends is not None:
+            rc = self.lib.rimphony_ctx_set_tables_2d_device_ends(
+                self.handle, nt, nn, None if gamma is None else gamma.ctypes.data_as(dp), gamma_lo, gamma_hi, nmu,
+                None if mu is None else mu.ctypes.data_as(dp), ctypes.c_void_p(log_n.data_ptr()),
+                None if k is None else k.ctypes.data_as(dp), ends[0], ends[1], self._stream())
+            capi.check(rc, "rimphony_ctx_set_tables_2d_device_ends")
+            return
         rc = self.lib.rimphony_ctx_set_tables_2d_device(
             self.handle, nt, nn, None if gamma is None else gamma.ctypes.data_as(dp), gamma_lo, gamma_hi, nmu,
             None if mu is None else mu.ctypes.data_as(dp), ctypes.c_void_p(log_n.data_ptr()),
@@ -979,28 +1042,30 @@ class TabulatedDistribution2D(TabulatedDistribution):
     gamma_lo to gamma_hi and uniform in mu = cos xi from -1 to +1; f = norm exp(S(ln gamma, mu)) / (gamma^2 beta) inside
     the table, 0 outside, S the tensor-product natural cubic spline (Context.set_tables_2d).  It need not be a product
     n(gamma) g(mu).  sin_k, a number in [0, 100], multiplies it by sin^k xi in closed form: log_n is then the smooth
-    remainder ln(n / sin^k xi).  Installs its table whenever it computes, as TabulatedDistribution does."""
+    remainder ln(n / sin^k xi).  ends chooses the ends of the spline as for Context.set_tables_2d: "not-a-knot" for a surface
+    curved at mu = +-1.  Installs its table whenever it computes, as TabulatedDistribution does."""
 
-    def __init__(self, gamma_lo, gamma_hi, log_n, sin_k=None):
+    def __init__(self, gamma_lo, gamma_hi, log_n, sin_k=None, ends=None):
         self.gamma_lo, self.gamma_hi = float(gamma_lo), float(gamma_hi)
         log_n = np.asarray(log_n, dtype=np.float64)
         if log_n.ndim != 2:
             raise ValueError("log_n: expected one table, [n_nodes][n_mu]")
         self.log_n = check_tables_2d(self.gamma_lo, self.gamma_hi, log_n)
         self.sin_k = None if sin_k is None else check_sin_k(sin_k, 1)
+        self.ends = check_ends(ends)
 
     @classmethod
-    def from_function(cls, fn, gamma_lo, gamma_hi, n_nodes=512, n_mu=65, sin_k=None):
+    def from_function(cls, fn, gamma_lo, gamma_hi, n_nodes=512, n_mu=65, sin_k=None, ends=None):
         """Tabulate n(gamma, mu) = fn(gamma[:, None], mu[None, :]) (vectorised, positive) on n_nodes nodes uniform in
         ln gamma and n_mu nodes uniform in mu from -1 to +1.  With sin_k, fn gives the smooth remainder n / sin^k xi."""
         gamma = np.exp(np.linspace(math.log(gamma_lo), math.log(gamma_hi), int(n_nodes)))
         gamma[0], gamma[-1] = gamma_lo, gamma_hi
         mu = np.linspace(-1.0, 1.0, int(n_mu))
         n = np.broadcast_to(np.asarray(fn(gamma[:, None], mu[None, :]), dtype=np.float64), (int(n_nodes), int(n_mu)))
-        return cls(gamma_lo, gamma_hi, np.log(n), sin_k)
+        return cls(gamma_lo, gamma_hi, np.log(n), sin_k, ends)
 
     def _install(self, ctx):
-        ctx.set_tables_2d(self.gamma_lo, self.gamma_hi, self.log_n, self.sin_k)
+        ctx.set_tables_2d(self.gamma_lo, self.gamma_hi, self.log_n, self.sin_k, self.ends)
         return ctx
 
 
@@ -1036,28 +1101,29 @@ class TabulatedDistribution2DGrid(TabulatedDistribution):
     """A distribution given as a surface on gamma nodes of its own: log_n [n_nodes][n_mu] = ln n(gamma_i, mu_j) at the
     strictly increasing gamma [n_nodes] and at mu nodes uniform from -1 to +1 (Context.set_tables_2d_grid);
     f = norm exp(S(ln gamma, mu)) / (gamma^2 beta) between the end nodes, 0 outside, S the tensor-product natural cubic
-    spline on the given nodes.  sin_k as for TabulatedDistribution2D.  Installs its table whenever it computes, as
+    spline on the given nodes.  sin_k and ends as for TabulatedDistribution2D.  Installs its table whenever it computes, as
     TabulatedDistribution does."""
 
-    def __init__(self, gamma, log_n, sin_k=None):
+    def __init__(self, gamma, log_n, sin_k=None, ends=None):
         log_n = np.asarray(log_n, dtype=np.float64)
         if log_n.ndim != 2:
             raise ValueError("log_n: expected one table, [n_nodes][n_mu]")
         self.gamma, self.log_n = check_tables_2d_grid(gamma, log_n)
         self.gamma_lo, self.gamma_hi = float(self.gamma[0]), float(self.gamma[-1])
         self.sin_k = None if sin_k is None else check_sin_k(sin_k, 1)
+        self.ends = check_ends(ends)
 
     @classmethod
-    def from_function(cls, fn, gamma, n_mu=65, sin_k=None):
+    def from_function(cls, fn, gamma, n_mu=65, sin_k=None, ends=None):
         """Tabulate n(gamma, mu) = fn(gamma[:, None], mu[None, :]) (vectorised, positive) at the given gamma nodes and
         n_mu nodes uniform in mu from -1 to +1.  With sin_k, fn gives the smooth remainder n / sin^k xi."""
         gamma = np.asarray(gamma, dtype=np.float64)
         mu = np.linspace(-1.0, 1.0, int(n_mu))
         n = np.broadcast_to(np.asarray(fn(gamma[:, None], mu[None, :]), dtype=np.float64), (gamma.shape[0], int(n_mu)))
-        return cls(gamma, np.log(n), sin_k)
+        return cls(gamma, np.log(n), sin_k, ends)
 
     def _install(self, ctx):
-        ctx.set_tables_2d_grid(self.gamma, self.log_n, self.sin_k)
+        ctx.set_tables_2d_grid(self.gamma, self.log_n, self.sin_k, self.ends)
         return ctx
 
 
@@ -1065,28 +1131,29 @@ class TabulatedDistribution2DNodes(TabulatedDistribution):
     """A distribution given as a surface on gamma nodes and mu nodes of its own: log_n [n_nodes][n_mu] = ln n(gamma_i,
     mu_j) at the strictly increasing gamma [n_nodes] and mu [n_mu], mu from exactly -1 to exactly +1
     (Context.set_tables_2d_nodes); f = norm exp(S(ln gamma, mu)) / (gamma^2 beta) between the end gamma nodes, 0 outside,
-    S the tensor-product natural cubic spline on the given nodes.  sin_k as for TabulatedDistribution2D.  Installs its
-    table whenever it computes, as TabulatedDistribution does."""
+    S the tensor-product natural cubic spline on the given nodes.  sin_k and ends as for TabulatedDistribution2D.  Installs
+    its table whenever it computes, as TabulatedDistribution does."""
 
-    def __init__(self, gamma, mu, log_n, sin_k=None):
+    def __init__(self, gamma, mu, log_n, sin_k=None, ends=None):
         log_n = np.asarray(log_n, dtype=np.float64)
         if log_n.ndim != 2:
             raise ValueError("log_n: expected one table, [n_nodes][n_mu]")
         self.gamma, self.mu, self.log_n = check_tables_2d_nodes(gamma, mu, log_n)
         self.gamma_lo, self.gamma_hi = float(self.gamma[0]), float(self.gamma[-1])
         self.sin_k = None if sin_k is None else check_sin_k(sin_k, 1)
+        self.ends = check_ends(ends)
 
     @classmethod
-    def from_function(cls, fn, gamma, mu, sin_k=None):
+    def from_function(cls, fn, gamma, mu, sin_k=None, ends=None):
         """Tabulate n(gamma, mu) = fn(gamma[:, None], mu[None, :]) (vectorised, positive) at the given gamma and mu nodes.
         With sin_k, fn gives the smooth remainder n / sin^k xi."""
         gamma = np.asarray(gamma, dtype=np.float64)
         mu = np.asarray(mu, dtype=np.float64)
         n = np.broadcast_to(np.asarray(fn(gamma[:, None], mu[None, :]), dtype=np.float64), (gamma.shape[0], mu.shape[0]))
-        return cls(gamma, mu, np.log(n), sin_k)
+        return cls(gamma, mu, np.log(n), sin_k, ends)
 
     def _install(self, ctx):
-        ctx.set_tables_2d_nodes(self.gamma, self.mu, self.log_n, self.sin_k)
+        ctx.set_tables_2d_nodes(self.gamma, self.mu, self.log_n, self.sin_k, self.ends)
         return ctx
 
 

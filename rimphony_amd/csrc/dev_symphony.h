@@ -88,9 +88,11 @@ enum { TAB_PITCH_LAST = 0, TAB_PITCH_INVH = 1, TAB_PITCH_H = 2, TAB_PITCH_P = 3,
 // {S, S_u, S_mu, S_umu} of the tensor-product natural cubic spline S(u, mu) at the node, mu fastest: the nodes (i, j) and
 // (i, j + 1) are 64 contiguous bytes and a sample reads two such runs.  A set with a sin^k xi prefactor keeps the table's k
 // in the first of the spare words, TAB_2D_K (0 as built without one: only the kinds with a prefactor read it).  A set on
-// given mu nodes (tab_2d_nodes_* below) uses two more, TAB_2D_MU_GUIDE and TAB_2D_MU_NODES.
+// given mu nodes (tab_2d_nodes_* below) uses two more, TAB_2D_MU_GUIDE and TAB_2D_MU_NODES.  The last one, TAB_2D_ENDS, records
+// how the spline was solved -- ends_u + 2 ends_mu, each 0 for natural ends and 1 for not-a-knot ends (tab_spline.h) -- for
+// whoever reads a set back: no kernel reads it.
 enum { TAB_2D_LAST = 0, TAB_2D_INVH = 1, TAB_2D_H = 2, TAB_2D_NORM = 3, TAB_2D_K = 4, TAB_2D_MU_GUIDE = 5, TAB_2D_MU_NODES = 6,
-       TAB_2D_HDR = 8 };
+       TAB_2D_ENDS = 7, TAB_2D_HDR = 8 };
 RIM_DEV bool tab_set_is_2d(const double *hdr) { return hdr[TAB_HDR_NMU] < 0.; }
 // A set with a sin^k xi prefactor (rim_tab_build_pitchy): header and gamma rows as ever, TAB_HDR_NMU = n_mu (0: no g), then
 // per table TAB_PITCHY_PRE words {k, n_mu, two spare} and, straight behind them, what a pitch row is: TAB_PITCH_HDR words

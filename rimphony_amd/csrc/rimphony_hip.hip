@@ -583,6 +583,7 @@ struct RimTabDeviceNodes {
     std::vector<double> axes;       // the axis block along u, then the one along mu (tab_install.h: rim_tab_install_axis)
     double hu, hmu;
     int grid_u, grid_mu;
+    int ends_u, ends_mu;            // tab_spline.h: RIM_TAB_ENDS_*
     hipStream_t st;
 };
 static int install_tables(rimphony_ctx *c, const std::vector<double> &blob, int tab_kind, RimTabFill fill = nullptr, size_t fill_at = 0,
@@ -635,8 +636,8 @@ static int install_tables(rimphony_ctx *c, const std::vector<double> &blob, int 
             s.log_n = dev->d_log_n;
             s.nodes = fresh.p + blob.size();
             s.n_tables = dev->n_tables; s.n_nodes = dev->n_nodes; s.n_mu = dev->n_mu;
-            s.au = rim_tab_axis_of(aux.p, dev->n_nodes, dev->hu, dev->grid_u);
-            s.amu = rim_tab_axis_of(aux.p + rim_tab_axis_doubles(dev->n_nodes), dev->n_mu, dev->hmu, dev->grid_mu);
+            s.au = rim_tab_axis_of(aux.p, dev->n_nodes, dev->hu, dev->grid_u, dev->ends_u);
+            s.amu = rim_tab_axis_of(aux.p + rim_tab_axis_doubles(dev->n_nodes), dev->n_mu, dev->hmu, dev->grid_mu, dev->ends_mu);
             rim_tab_install_launch_sweeps(st, s);
             e = hipGetLastError();
         }
@@ -813,11 +814,13 @@ static int check_device_range(const void *p, size_t bytes, int device)
 // Any of the six 2-D forms from ln n in device memory: gamma null, the nodes uniform in ln gamma; mu null, uniform in mu;
 // sin_k null, no prefactor.  The front of the set -- headers, guides, node words -- is the host entry's own
 // (tab_spline.h: rim_tab_front_2d*); the node data are solved on the device (install_tables), to the host entry's bits.
-extern "C" int rimphony_ctx_set_tables_2d_device(rimphony_ctx *c, size_t n_tables, size_t n_nodes, const double *gamma, double gamma_lo,
-                                                 double gamma_hi, size_t n_mu, const double *mu, const double *d_log_n,
-                                                 const double *sin_k, void *stream)
+// ends_u, ends_mu: the ends of the spline along u and along mu (tab_spline.h: RIM_TAB_ENDS_*), which the caller has checked.
+static int set_tables_2d_device(rimphony_ctx *c, size_t n_tables, size_t n_nodes, const double *gamma, double gamma_lo, double gamma_hi,
+                                size_t n_mu, const double *mu, const double *d_log_n, const double *sin_k, int ends_u, int ends_mu,
+                                void *stream)
 {
     if (!c) return RIMPHONY_EINVAL;
+    const int ends = ends_u + 2 * ends_mu;
     std::vector<double> blob;
     if (!n_tables) return install_tables(c, blob, DIST_TABULATED_ISO);
     if (!gamma && mu) return RIMPHONY_EINVAL;
@@ -833,31 +836,88 @@ extern "C" int rimphony_ctx_set_tables_2d_device(rimphony_ctx *c, size_t n_table
     dev.n_tables = n_tables; dev.n_nodes = n_nodes; dev.n_mu = n_mu;
     dev.hu = 0.; dev.hmu = 0.;
     dev.grid_u = gamma != nullptr; dev.grid_mu = mu != nullptr;
+    dev.ends_u = ends_u; dev.ends_mu = ends_mu;
     dev.st = (hipStream_t) stream;
     int tab_kind;
     RimTabFill fill;
     try {
         std::vector<double> h, ih, hm, ihm;
         if (mu) {
-            rim_tab_front_2d_nodes(n_tables, n_nodes, gamma, n_mu, mu, sin_k, blob, h, ih, hm, ihm);
+            rim_tab_front_2d_nodes(n_tables, n_nodes, gamma, n_mu, mu, sin_k, blob, h, ih, hm, ihm, ends);
             tab_kind = sin_k ? DIST_TABULATED_2D_NODES_PITCHY : DIST_TABULATED_2D_NODES;
             fill = sin_k ? rim_tab_2d_nodes_pitchy_launch_table_norms : rim_tab_2d_nodes_launch_table_norms;
         } else if (gamma) {
-            rim_tab_front_2d_grid(n_tables, n_nodes, gamma, n_mu, blob, h, ih, dev.hmu);
+            rim_tab_front_2d_grid(n_tables, n_nodes, gamma, n_mu, blob, h, ih, dev.hmu, ends);
             tab_kind = sin_k ? DIST_TABULATED_2D_GRID_PITCHY : DIST_TABULATED_2D_GRID;
             fill = sin_k ? rim_tab_2d_grid_pitchy_launch_table_norms : rim_tab_2d_grid_launch_table_norms;
         } else {
-            rim_tab_front_2d(n_tables, n_nodes, gamma_lo, gamma_hi, n_mu, blob, dev.hu, dev.hmu);
+            rim_tab_front_2d(n_tables, n_nodes, gamma_lo, gamma_hi, n_mu, blob, dev.hu, dev.hmu, ends);
             tab_kind = sin_k ? DIST_TABULATED_2D_PITCHY : DIST_TABULATED_2D;
             fill = sin_k ? rim_tab_2d_pitchy_launch_table_norms : rim_tab_launch_table_norms;
         }
         if (sin_k && !mu) rim_tab_put_2d_sin_k(n_tables, sin_k, blob);
         dev.axes.assign(rim_tab_axis_doubles(n_nodes) + rim_tab_axis_doubles(n_mu), 0.);
-        rim_tab_install_axis(n_nodes, dev.hu, gamma ? h.data() : nullptr, gamma ? ih.data() : nullptr, dev.axes.data());
+        rim_tab_install_axis(n_nodes, dev.hu, gamma ? h.data() : nullptr, gamma ? ih.data() : nullptr, dev.axes.data(), ends_u);
         rim_tab_install_axis(n_mu, dev.hmu, mu ? hm.data() : nullptr, mu ? ihm.data() : nullptr,
-                             dev.axes.data() + rim_tab_axis_doubles(n_nodes));
+                             dev.axes.data() + rim_tab_axis_doubles(n_nodes), ends_mu);
     } catch (const std::bad_alloc &) { return RIMPHONY_ENOMEM; }
     return install_tables(c, blob, tab_kind, fill, 0, &dev);
+}
+
+extern "C" int rimphony_ctx_set_tables_2d_device(rimphony_ctx *c, size_t n_tables, size_t n_nodes, const double *gamma, double gamma_lo,
+                                                 double gamma_hi, size_t n_mu, const double *mu, const double *d_log_n,
+                                                 const double *sin_k, void *stream)
+{
+    return set_tables_2d_device(c, n_tables, n_nodes, gamma, gamma_lo, gamma_hi, n_mu, mu, d_log_n, sin_k, RIM_TAB_ENDS_NATURAL,
+                                RIM_TAB_ENDS_NATURAL, stream);
+}
+
+// The same with a choice of the spline's ends per axis (tab_spline.h: RIM_TAB_ENDS_*; anything else is refused before the set
+// is looked at).  Natural ends on both axes: the set of the entry above.
+extern "C" int rimphony_ctx_set_tables_2d_device_ends(rimphony_ctx *c, size_t n_tables, size_t n_nodes, const double *gamma,
+                                                      double gamma_lo, double gamma_hi, size_t n_mu, const double *mu,
+                                                      const double *d_log_n, const double *sin_k, int ends_gamma, int ends_mu, void *stream)
+{
+    if (!c || rim_tab_check_ends(ends_gamma, ends_mu)) return RIMPHONY_EINVAL;
+    return set_tables_2d_device(c, n_tables, n_nodes, gamma, gamma_lo, gamma_hi, n_mu, mu, d_log_n, sin_k, ends_gamma, ends_mu, stream);
+}
+
+// Any of the six 2-D forms from ln n in HOST memory with a choice of the spline's ends per axis: gamma, mu and sin_k null or
+// given as for the device entry.  Each form is checked and built by what its own entry calls, so natural ends on both axes
+// install that entry's set, and what it refuses is refused here.
+extern "C" int rimphony_ctx_set_tables_2d_ends(rimphony_ctx *c, size_t n_tables, size_t n_nodes, const double *gamma, double gamma_lo,
+                                               double gamma_hi, size_t n_mu, const double *mu, const double *log_n, const double *sin_k,
+                                               int ends_gamma, int ends_mu)
+{
+    if (!c || rim_tab_check_ends(ends_gamma, ends_mu)) return RIMPHONY_EINVAL;
+    std::vector<double> blob;
+    if (!n_tables) return install_tables(c, blob, DIST_TABULATED_ISO);
+    if (!gamma && mu) return RIMPHONY_EINVAL;
+    int tab_kind;
+    RimTabFill fill;
+    try {
+        if (mu) {
+            if (rim_tab_check_2d_nodes(n_tables, n_nodes, gamma, n_mu, mu, log_n, sin_k)) return RIMPHONY_EINVAL;
+            rim_tab_build_2d_nodes(n_tables, n_nodes, gamma, n_mu, mu, log_n, sin_k, blob, ends_gamma, ends_mu);
+            tab_kind = sin_k ? DIST_TABULATED_2D_NODES_PITCHY : DIST_TABULATED_2D_NODES;
+            fill = sin_k ? rim_tab_2d_nodes_pitchy_launch_table_norms : rim_tab_2d_nodes_launch_table_norms;
+        } else if (gamma) {
+            if (rim_tab_check_2d_grid(n_tables, n_nodes, gamma, n_mu, log_n) || (sin_k && rim_tab_check_sin_k(n_tables, sin_k)))
+                return RIMPHONY_EINVAL;
+            if (sin_k) rim_tab_build_2d_grid_pitchy(n_tables, n_nodes, gamma, n_mu, log_n, sin_k, blob, ends_gamma, ends_mu);
+            else rim_tab_build_2d_grid(n_tables, n_nodes, gamma, n_mu, log_n, blob, ends_gamma, ends_mu);
+            tab_kind = sin_k ? DIST_TABULATED_2D_GRID_PITCHY : DIST_TABULATED_2D_GRID;
+            fill = sin_k ? rim_tab_2d_grid_pitchy_launch_table_norms : rim_tab_2d_grid_launch_table_norms;
+        } else {
+            if (rim_tab_check_2d(n_tables, n_nodes, gamma_lo, gamma_hi, n_mu, log_n) || (sin_k && rim_tab_check_sin_k(n_tables, sin_k)))
+                return RIMPHONY_EINVAL;
+            if (sin_k) rim_tab_build_2d_pitchy(n_tables, n_nodes, gamma_lo, gamma_hi, n_mu, log_n, sin_k, blob, ends_gamma, ends_mu);
+            else rim_tab_build_2d(n_tables, n_nodes, gamma_lo, gamma_hi, n_mu, log_n, blob, ends_gamma, ends_mu);
+            tab_kind = sin_k ? DIST_TABULATED_2D_PITCHY : DIST_TABULATED_2D;
+            fill = sin_k ? rim_tab_2d_pitchy_launch_table_norms : rim_tab_launch_table_norms;
+        }
+    } catch (const std::bad_alloc &) { return RIMPHONY_ENOMEM; }
+    return install_tables(c, blob, tab_kind, fill);
 }
 
 // The installed set as the kernels read it, copied to the host (diagnostics and tests).  It holds offsets, never addresses,

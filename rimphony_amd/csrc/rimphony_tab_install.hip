@@ -5,7 +5,8 @@
 // a chain of n dependent divisions, so the work is latency-bound and wants many lines in flight, not wide blocks: blocks of
 // one wave, as many as there are waves of lines.  The lanes of a wave hold neighbouring mu columns in families 0 and 2 (their
 // loads of ln n share cache lines; their stores are 32 bytes apart) and neighbouring gamma rows in family 1 (each lane walks
-// its own contiguous row).
+// its own contiguous row).  The ends of the spline, natural or not-a-knot per axis, travel in the axes of the set
+// (RimTabAxis::ends) and are uniform over a launch: the two forms of a line's first and last step do not diverge.
 #include <hip/hip_runtime.h>
 #include "detmath.h"
 #include "tab_install.h"

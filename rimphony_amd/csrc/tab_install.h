@@ -16,6 +16,10 @@
 //   1  S_mu along mu for every (table, gamma row)
 //   2  S_umu along u through the S_mu words of a column -- it reads what family 1 wrote, so it runs after it
 // All indices are size_t.
+//
+// An axis with not-a-knot ends (RimTabAxis::ends, tab_spline.h: RIM_TAB_ENDS_NOT_A_KNOT) differs in its first and last rows
+// only: cp[0] and den[n - 1] of the axis block are the host's for those rows, and the line forms their right-hand sides from
+// y_2 and y_{n-3} as well -- the first it reads ahead, the second it keeps from the pass -- with the host's expressions.
 #ifndef RIM_TAB_INSTALL_H
 #define RIM_TAB_INSTALL_H
 
@@ -24,55 +28,58 @@
 
 // One axis of a set as the line solver reads it: n nodes, either `hu` apart (grid == 0: rim_tab_spline_row) or h[j] = x_{j+1}
 // - x_j apart with ih[j] = 1 / h[j] (grid != 0: rim_tab_spline_row_grid).  cp, den: n doubles each, rim_tab_install_axis.
+// ends: 0 natural, 1 not-a-knot.
 struct RimTabAxis {
     const double *cp, *den, *h, *ih;
     double hu;
     size_t n;
-    int grid;
+    int grid, ends;
 };
 
 // doubles of an axis block {cp[n], den[n], h[n], ih[n]}; the last two rows stay 0 for a uniform axis
 inline size_t rim_tab_axis_doubles(size_t n) { return 4 * n; }
 
 // The axis block at `blk` (rim_tab_axis_doubles(n) doubles) for n nodes hu apart (h, ih null) or h[], ih[] apart: cp and den
-// as the host's sweep forms them, in its own expressions.  den[0] is never read; a set on given nodes never reads cp[n - 1].
-inline void rim_tab_install_axis(size_t n, double hu, const double *h, const double *ih, double *blk)
+// as the host's sweep forms them, in its own expressions, for the ends `ends` of the axis.  den[0] is never read; a set on
+// given nodes never reads cp[n - 1].
+inline void rim_tab_install_axis(size_t n, double hu, const double *h, const double *ih, double *blk, int ends = 0)
 {
     double *cp = blk, *den = blk + n, *bh = blk + 2 * n, *bih = blk + 3 * n;
     const size_t last = n - 1;
-    cp[0] = 0.5;
+    cp[0] = ends ? 2. : 0.5;
     den[0] = 0.;
     if (!h) {
         (void) hu;
         for (size_t j = 1; j <= last; j++) {
             const double diag = j < last ? 4. : 2.;
-            den[j] = diag - cp[j - 1];
+            den[j] = (ends && j == last) ? 1. - 2. * cp[j - 1] : diag - cp[j - 1];
             cp[j] = 1. / den[j];
             bh[j] = 0.; bih[j] = 0.;
         }
         bh[0] = 0.; bih[0] = 0.;
         return;
     }
+    if (ends) cp[0] = (h[0] + h[1]) / h[1];
     for (size_t j = 1; j < last; j++) {
         den[j] = 2. * (ih[j - 1] + ih[j]) - ih[j - 1] * cp[j - 1];
         cp[j] = ih[j] / den[j];
     }
-    den[last] = 2. - cp[last - 1];
+    den[last] = ends ? h[last - 2] - (h[last - 1] + h[last - 2]) * cp[last - 1] : 2. - cp[last - 1];
     cp[last] = 0.;
     for (size_t j = 0; j < n; j++) { bh[j] = h[j]; bih[j] = ih[j]; }
 }
 
 // the axis over a block rim_tab_install_axis filled (on the device: over its copy there)
-RIM_DEV RimTabAxis rim_tab_axis_of(const double *blk, size_t n, double hu, int grid)
+RIM_DEV RimTabAxis rim_tab_axis_of(const double *blk, size_t n, double hu, int grid, int ends = 0)
 {
     RimTabAxis a;
     a.cp = blk; a.den = blk + n; a.h = blk + 2 * n; a.ih = blk + 3 * n;
-    a.hu = hu; a.n = n; a.grid = grid;
+    a.hu = hu; a.n = n; a.grid = grid; a.ends = ends;
     return a;
 }
 
-// One line: the slopes of the natural cubic spline through y_j = src[j * sstride] on the axis, into slope[j * ostride]; where
-// `val` is not null, the values into val[j * ostride] as well.  src and slope never share a word.
+// One line: the slopes of the cubic spline through y_j = src[j * sstride] on the axis, with the axis's ends, into
+// slope[j * ostride]; where `val` is not null, the values into val[j * ostride] as well.  src and slope never share a word.
 RIM_DEV void rim_tab_install_line(const RimTabAxis &ax, const double *src, size_t sstride, double *val, double *slope, size_t ostride)
 {
     const size_t last = ax.n - 1;
@@ -81,25 +88,37 @@ RIM_DEV void rim_tab_install_line(const RimTabAxis &ax, const double *src, size_
     double dp, m;
     if (!ax.grid) {
         const double h = ax.hu;
-        dp = 3. * (yc - ym) / h / 2.;
+        if (ax.ends) dp = (5. * ((yc - ym) / h) + (src[2 * sstride] - yc) / h) / 2.;
+        else dp = 3. * (yc - ym) / h / 2.;
         slope[0] = dp;
+        double yb = ym;                             // y[j - 2] of the last step
         for (size_t j = 1; j <= last; j++) {
             double rhs, yp = 0.;
             if (j < last) {
                 yp = src[(j + 1) * sstride];
                 rhs = 3. * (yp - ym) / h;
+                dp = (rhs - dp) / ax.den[j];
+            } else if (ax.ends) {
+                rhs = (5. * ((yc - ym) / h) + (ym - yb) / h) / 2.;
+                dp = (rhs - 2. * dp) / ax.den[j];
             } else {
                 rhs = 3. * (yc - ym) / h;
+                dp = (rhs - dp) / ax.den[j];
             }
-            dp = (rhs - dp) / ax.den[j];
             slope[j * ostride] = dp;
             if (val) val[j * ostride] = yc;
-            ym = yc; yc = yp;
+            yb = ym; ym = yc; yc = yp;
         }
         m = dp;
     } else {
         double sl = (yc - ym) / ax.h[0];            // (y[j] - y[j - 1]) / h[j - 1]
-        dp = 3. * sl / 2.;
+        double sb = sl;                             // (y[j - 1] - y[j - 2]) / h[j - 2] of the last step
+        if (ax.ends) {
+            const double s1 = (src[2 * sstride] - yc) / ax.h[1], w = ax.h[0] + ax.h[1];
+            dp = ((3. * ax.h[0] + 2. * ax.h[1]) * ax.h[1] * sl + ax.h[0] * ax.h[0] * s1) / w / ax.h[1];
+        } else {
+            dp = 3. * sl / 2.;
+        }
         slope[0] = dp;
         for (size_t j = 1; j < last; j++) {
             const double yp = src[(j + 1) * sstride];
@@ -108,9 +127,15 @@ RIM_DEV void rim_tab_install_line(const RimTabAxis &ax, const double *src, size_
             dp = (rhs - ax.ih[j - 1] * dp) / ax.den[j];
             slope[j * ostride] = dp;
             if (val) val[j * ostride] = yc;
-            ym = yc; yc = yp; sl = sr;
+            ym = yc; yc = yp; sb = sl; sl = sr;
         }
-        m = (3. * sl - dp) / ax.den[last];
+        if (ax.ends) {
+            const double hl = ax.h[last - 1], hk = ax.h[last - 2], w = hl + hk;
+            const double rhs = ((3. * hl + 2. * hk) * hk * sl + hl * hl * sb) / w;
+            m = (rhs - w * dp) / ax.den[last];
+        } else {
+            m = (3. * sl - dp) / ax.den[last];
+        }
         slope[last * ostride] = m;
         if (val) val[last * ostride] = yc;
     }

@@ -41,6 +41,13 @@
 // geometry-only part (rim_tab_check_2d_geometry and its _grid_ and _nodes_ counterparts).  A set whose log_n lies in device
 // memory uses those parts alone and solves the node data on the device, to the same bits (tab_install.h).
 //
+// The ends of the spline of a 2-D set are a choice per axis (RIM_TAB_ENDS_NATURAL, RIM_TAB_ENDS_NOT_A_KNOT: the trailing
+// arguments of both line solvers and of the 2-D builders, natural where they are left out).  Natural ends force a second
+// derivative of 0 at the end nodes; not-a-knot ends make the third derivative continuous across the second and the
+// second-to-last node, so that every cubic comes back as itself and the error stays O(h^4) up to the edge.  The choice is a
+// word of each table's header (TAB_2D_ENDS = ends_u + 2 ends_mu) that no kernel reads: the kernels see {S, S_u, S_mu, S_umu}
+// and never ask how they were solved.
+//
 // Plain C++ with the elementary functions of detmath.h, so that the library (hipcc's host pass) and the tests' table
 // oracle (g++) produce the same bits from the same table.
 #ifndef RIM_TAB_SPLINE_H
@@ -70,14 +77,40 @@ inline int rim_tab_check(size_t n_tables, size_t n_nodes, double gamma_lo, doubl
     return 0;
 }
 
+#define RIM_TAB_ENDS_NATURAL 0
+#define RIM_TAB_ENDS_NOT_A_KNOT 1
+
+// an end condition per axis of a 2-D set: each RIM_TAB_ENDS_NATURAL or RIM_TAB_ENDS_NOT_A_KNOT
+inline int rim_tab_check_ends(int ends_u, int ends_mu)
+{
+    return ((ends_u != RIM_TAB_ENDS_NATURAL && ends_u != RIM_TAB_ENDS_NOT_A_KNOT) ||
+            (ends_mu != RIM_TAB_ENDS_NATURAL && ends_mu != RIM_TAB_ENDS_NOT_A_KNOT)) ? -1 : 0;
+}
+
 // The slopes of the natural cubic spline through y[0 .. n-1] at nodes h apart, written with the values as {y_j, m_j} pairs
 // to row[2 j], row[2 j + 1].  cp, dp: n doubles each, the swept upper diagonal and right-hand side of the Thomas algorithm.
-inline void rim_tab_spline_row(const double *y, size_t n, double h, double *row, double *cp, double *dp)
+// ends = RIM_TAB_ENDS_NOT_A_KNOT: the first row is m_0 + 2 m_1 = (5 s_0 + s_1) / 2, s_j = (y_{j+1} - y_j) / h -- the third
+// derivatives 6 (m_j + m_{j+1} - 2 s_j) / h^2 of the first two pieces set equal, m_2 eliminated with the row of node 1 -- and
+// the last row its mirror, 2 m_{n-2} + m_{n-1} = (5 s_{n-2} + s_{n-3}) / 2.  The sweep needs no pivoting: its denominators are
+// 2 at node 1, 3.5 .. 3.74 inside and 1 - 2 cp > 0.46 in the last row.
+inline void rim_tab_spline_row(const double *y, size_t n, double h, double *row, double *cp, double *dp, int ends = RIM_TAB_ENDS_NATURAL)
 {
     const size_t last = n - 1;
-    cp[0] = 0.5;
-    dp[0] = 3. * (y[1] - y[0]) / h / 2.;
+    if (ends) {
+        cp[0] = 2.;
+        dp[0] = (5. * ((y[1] - y[0]) / h) + (y[2] - y[1]) / h) / 2.;
+    } else {
+        cp[0] = 0.5;
+        dp[0] = 3. * (y[1] - y[0]) / h / 2.;
+    }
     for (size_t j = 1; j <= last; j++) {
+        if (ends && j == last) {
+            const double rhs = (5. * ((y[last] - y[last - 1]) / h) + (y[last - 1] - y[last - 2]) / h) / 2.;
+            const double den = 1. - 2. * cp[j - 1];
+            cp[j] = 1. / den;
+            dp[j] = (rhs - 2. * dp[j - 1]) / den;
+            break;
+        }
         const double diag = j < last ? 4. : 2.;
         const double rhs = j < last ? 3. * (y[j + 1] - y[j - 1]) / h : 3. * (y[last] - y[last - 1]) / h;
         const double den = diag - cp[j - 1];
@@ -264,11 +297,23 @@ inline int rim_tab_check_grid(size_t n_tables, size_t n_nodes, const double *gam
 // The slopes m[0 .. n-1] of the natural cubic spline through (u_j, y[j]) on nodes h[j] = u_{j+1} - u_j apart, ih[j] = 1 / h[j]:
 //   ih[j-1] m_{j-1} + 2 (ih[j-1] + ih[j]) m_j + ih[j] m_{j+1} = 3 (s_{j-1} ih[j-1] + s_j ih[j]),  s_j = (y_{j+1} - y_j) / h[j],
 // 2 m_0 + m_1 = 3 s_0 and its mirror at the ends.  One fixed order of operations: the bits depend on it.  cp, dp: n doubles.
-inline void rim_tab_spline_row_grid(const double *y, size_t n, const double *h, const double *ih, double *m, double *cp, double *dp)
+// ends = RIM_TAB_ENDS_NOT_A_KNOT: (m_0 + m_1 - 2 s_0) / h_0^2 = (m_1 + m_2 - 2 s_1) / h_1^2, with m_2 eliminated by the row of
+// node 1, is the first row of de Boor's CUBSPL,
+//   h_1 m_0 + (h_0 + h_1) m_1 = ((3 h_0 + 2 h_1) h_1 s_0 + h_0^2 s_1) / (h_0 + h_1),
+// and the last row is its mirror.  No pivoting: the denominator at node 1 is ih_0 + ih_1, those behind it exceed ih[j-1] +
+// 2 ih[j], and the last one, h_{n-3} - (h_{n-2} + h_{n-3}) cp[n-2], stays above h_{n-3}^2 / (h_{n-2} + 2 h_{n-3}).
+inline void rim_tab_spline_row_grid(const double *y, size_t n, const double *h, const double *ih, double *m, double *cp, double *dp,
+                                    int ends = RIM_TAB_ENDS_NATURAL)
 {
     const size_t last = n - 1;
-    cp[0] = 0.5;
-    dp[0] = 3. * ((y[1] - y[0]) / h[0]) / 2.;
+    if (ends) {
+        const double s0 = (y[1] - y[0]) / h[0], s1 = (y[2] - y[1]) / h[1], w = h[0] + h[1];
+        cp[0] = w / h[1];
+        dp[0] = ((3. * h[0] + 2. * h[1]) * h[1] * s0 + h[0] * h[0] * s1) / w / h[1];
+    } else {
+        cp[0] = 0.5;
+        dp[0] = 3. * ((y[1] - y[0]) / h[0]) / 2.;
+    }
     for (size_t j = 1; j < last; j++) {
         const double sl = (y[j] - y[j - 1]) / h[j - 1], sr = (y[j + 1] - y[j]) / h[j];
         const double rhs = 3. * (sl * ih[j - 1] + sr * ih[j]);
@@ -276,7 +321,14 @@ inline void rim_tab_spline_row_grid(const double *y, size_t n, const double *h, 
         cp[j] = ih[j] / den;
         dp[j] = (rhs - ih[j - 1] * dp[j - 1]) / den;
     }
-    m[last] = (3. * ((y[last] - y[last - 1]) / h[last - 1]) - dp[last - 1]) / (2. - cp[last - 1]);
+    if (ends) {
+        const double sl = (y[last - 1] - y[last - 2]) / h[last - 2], sr = (y[last] - y[last - 1]) / h[last - 1];
+        const double w = h[last - 1] + h[last - 2];
+        const double rhs = ((3. * h[last - 1] + 2. * h[last - 2]) * h[last - 2] * sr + h[last - 1] * h[last - 1] * sl) / w;
+        m[last] = (rhs - w * dp[last - 1]) / (h[last - 2] - w * cp[last - 1]);
+    } else {
+        m[last] = (3. * ((y[last] - y[last - 1]) / h[last - 1]) - dp[last - 1]) / (2. - cp[last - 1]);
+    }
     for (size_t j = last; j-- > 0;) m[j] = dp[j] - cp[j] * m[j + 1];
 }
 
@@ -358,7 +410,7 @@ inline int rim_tab_check_2d(size_t n_tables, size_t n_nodes, double gamma_lo, do
 // What a 2-D set holds in front of its node data, the words that do not depend on log_n: the header and the table headers
 // (normalisations 0).  h, hm: the node spacings along u and mu as the sweeps use them.  rim_tab_build_2d begins with it.
 inline void rim_tab_front_2d(size_t n_tables, size_t n_nodes, double gamma_lo, double gamma_hi, size_t n_mu, std::vector<double> &blob,
-                             double &h, double &hm)
+                             double &h, double &hm, int ends = 0)
 {
     using namespace rim;
     const double u_lo = rim_log(gamma_lo), u_hi = rim_log(gamma_hi);
@@ -371,6 +423,7 @@ inline void rim_tab_front_2d(size_t n_tables, size_t n_nodes, double gamma_lo, d
         th[TAB_2D_LAST] = (double) (n_mu - 2);
         th[TAB_2D_INVH] = 1. / hm;
         th[TAB_2D_H] = hm;
+        th[TAB_2D_ENDS] = (double) ends;
     }
 }
 
@@ -378,11 +431,11 @@ inline void rim_tab_front_2d(size_t n_tables, size_t n_nodes, double gamma_lo, d
 // families of sweeps is fixed, because the bits depend on it: S_u along u for each mu column, S_mu along mu for each u row,
 // S_umu along u through the S_mu values of a column.
 inline void rim_tab_build_2d(size_t n_tables, size_t n_nodes, double gamma_lo, double gamma_hi, size_t n_mu, const double *log_n,
-                             std::vector<double> &blob)
+                             std::vector<double> &blob, int ends_u = 0, int ends_mu = 0)
 {
     using namespace rim;
     double h, hm;
-    rim_tab_front_2d(n_tables, n_nodes, gamma_lo, gamma_hi, n_mu, blob, h, hm);
+    rim_tab_front_2d(n_tables, n_nodes, gamma_lo, gamma_hi, n_mu, blob, h, hm, ends_u + 2 * ends_mu);
     const size_t per_table = n_nodes * n_mu * 4;
     blob.resize(blob.size() + n_tables * per_table, 0.);
     const size_t longest = n_nodes > n_mu ? n_nodes : n_mu;
@@ -392,19 +445,19 @@ inline void rim_tab_build_2d(size_t n_tables, size_t n_nodes, double gamma_lo, d
         double *nodes = blob.data() + TAB_HDR_DOUBLES + n_tables * TAB_2D_HDR + t * per_table;
         for (size_t j = 0; j < n_mu; j++) {
             for (size_t i = 0; i < n_nodes; i++) y[i] = src[i * n_mu + j];
-            rim_tab_spline_row(y.data(), n_nodes, h, pairs.data(), cp.data(), dp.data());
+            rim_tab_spline_row(y.data(), n_nodes, h, pairs.data(), cp.data(), dp.data(), ends_u);
             for (size_t i = 0; i < n_nodes; i++) {
                 nodes[(i * n_mu + j) * 4] = pairs[2 * i];
                 nodes[(i * n_mu + j) * 4 + 1] = pairs[2 * i + 1];
             }
         }
         for (size_t i = 0; i < n_nodes; i++) {
-            rim_tab_spline_row(src + i * n_mu, n_mu, hm, pairs.data(), cp.data(), dp.data());
+            rim_tab_spline_row(src + i * n_mu, n_mu, hm, pairs.data(), cp.data(), dp.data(), ends_mu);
             for (size_t j = 0; j < n_mu; j++) nodes[(i * n_mu + j) * 4 + 2] = pairs[2 * j + 1];
         }
         for (size_t j = 0; j < n_mu; j++) {
             for (size_t i = 0; i < n_nodes; i++) y[i] = nodes[(i * n_mu + j) * 4 + 2];
-            rim_tab_spline_row(y.data(), n_nodes, h, pairs.data(), cp.data(), dp.data());
+            rim_tab_spline_row(y.data(), n_nodes, h, pairs.data(), cp.data(), dp.data(), ends_u);
             for (size_t i = 0; i < n_nodes; i++) nodes[(i * n_mu + j) * 4 + 3] = pairs[2 * i + 1];
         }
     }
@@ -428,7 +481,7 @@ inline int rim_tab_check_2d_grid(size_t n_tables, size_t n_nodes, const double *
 // guide and the u nodes.  h, ih [n_nodes]: u_{i+1} - u_i and its reciprocal as the sweeps along u use them (0 in the last
 // word); hm: the spacing of the mu nodes.  rim_tab_build_2d_grid begins with it.
 inline void rim_tab_front_2d_grid(size_t n_tables, size_t n_nodes, const double *gamma, size_t n_mu, std::vector<double> &blob,
-                                  std::vector<double> &h, std::vector<double> &ih, double &hm)
+                                  std::vector<double> &h, std::vector<double> &ih, double &hm, int ends = 0)
 {
     using namespace rim;
     size_t cells = 8;
@@ -450,6 +503,7 @@ inline void rim_tab_front_2d_grid(size_t n_tables, size_t n_nodes, const double 
         th[TAB_2D_LAST] = (double) (n_mu - 2);
         th[TAB_2D_INVH] = 1. / hm;
         th[TAB_2D_H] = hm;
+        th[TAB_2D_ENDS] = (double) ends;
     }
 }
 
@@ -490,6 +544,43 @@ inline void rim_tab_build_2d_grid(size_t n_tables, size_t n_nodes, const double 
     }
 }
 
+// The same with a choice of the spline's ends along u and along mu (RIM_TAB_ENDS_*), an overload and not a defaulted argument:
+// the text above stays as it was written, because a test of the tests builds a mutant of it
+// (tests/test_tabulated_2d_grid_host.py).  Natural ends on both axes give the set above, word for word.
+inline void rim_tab_build_2d_grid(size_t n_tables, size_t n_nodes, const double *gamma, size_t n_mu, const double *log_n,
+                                  std::vector<double> &blob, int ends_u, int ends_mu)
+{
+    using namespace rim;
+    std::vector<double> h, ih;
+    double hm;
+    rim_tab_front_2d_grid(n_tables, n_nodes, gamma, n_mu, blob, h, ih, hm, ends_u + 2 * ends_mu);
+    const size_t per_table = n_nodes * n_mu * 4, nodes_at = blob.size();
+    blob.resize(nodes_at + n_tables * per_table, 0.);
+    const size_t longest = n_nodes > n_mu ? n_nodes : n_mu;
+    std::vector<double> m(n_nodes), y(longest), pairs(2 * longest), cp(longest), dp(longest);
+    for (size_t t = 0; t < n_tables; t++) {
+        const double *src = log_n + t * n_nodes * n_mu;
+        double *nodes = blob.data() + nodes_at + t * per_table;
+        for (size_t j = 0; j < n_mu; j++) {
+            for (size_t i = 0; i < n_nodes; i++) y[i] = src[i * n_mu + j];
+            rim_tab_spline_row_grid(y.data(), n_nodes, h.data(), ih.data(), m.data(), cp.data(), dp.data(), ends_u);
+            for (size_t i = 0; i < n_nodes; i++) {
+                nodes[(i * n_mu + j) * 4] = y[i];
+                nodes[(i * n_mu + j) * 4 + 1] = m[i];
+            }
+        }
+        for (size_t i = 0; i < n_nodes; i++) {
+            rim_tab_spline_row(src + i * n_mu, n_mu, hm, pairs.data(), cp.data(), dp.data(), ends_mu);
+            for (size_t j = 0; j < n_mu; j++) nodes[(i * n_mu + j) * 4 + 2] = pairs[2 * j + 1];
+        }
+        for (size_t j = 0; j < n_mu; j++) {
+            for (size_t i = 0; i < n_nodes; i++) y[i] = nodes[(i * n_mu + j) * 4 + 2];
+            rim_tab_spline_row_grid(y.data(), n_nodes, h.data(), ih.data(), m.data(), cp.data(), dp.data(), ends_u);
+            for (size_t i = 0; i < n_nodes; i++) nodes[(i * n_mu + j) * 4 + 3] = m[i];
+        }
+    }
+}
+
 // A 2-D set of either form with a sin^k xi prefactor per table: the form's own check and sin_k as rim_tab_check_sin_k
 // demands it; the form's own blob with k in the word TAB_2D_K of each table's header, which is 0 as the form builds it (the
 // table headers of both forms start TAB_HDR_DOUBLES words into the set).  The normalisation is 0 as built, as ever.
@@ -514,16 +605,16 @@ inline void rim_tab_put_2d_sin_k(size_t n_tables, const double *sin_k, std::vect
 }
 
 inline void rim_tab_build_2d_pitchy(size_t n_tables, size_t n_nodes, double gamma_lo, double gamma_hi, size_t n_mu,
-                                    const double *log_n, const double *sin_k, std::vector<double> &blob)
+                                    const double *log_n, const double *sin_k, std::vector<double> &blob, int ends_u = 0, int ends_mu = 0)
 {
-    rim_tab_build_2d(n_tables, n_nodes, gamma_lo, gamma_hi, n_mu, log_n, blob);
+    rim_tab_build_2d(n_tables, n_nodes, gamma_lo, gamma_hi, n_mu, log_n, blob, ends_u, ends_mu);
     rim_tab_put_2d_sin_k(n_tables, sin_k, blob);
 }
 
 inline void rim_tab_build_2d_grid_pitchy(size_t n_tables, size_t n_nodes, const double *gamma, size_t n_mu, const double *log_n,
-                                         const double *sin_k, std::vector<double> &blob)
+                                         const double *sin_k, std::vector<double> &blob, int ends_u = 0, int ends_mu = 0)
 {
-    rim_tab_build_2d_grid(n_tables, n_nodes, gamma, n_mu, log_n, blob);
+    rim_tab_build_2d_grid(n_tables, n_nodes, gamma, n_mu, log_n, blob, ends_u, ends_mu);
     rim_tab_put_2d_sin_k(n_tables, sin_k, blob);
 }
 
@@ -564,7 +655,7 @@ inline int rim_tab_check_2d_nodes(size_t n_tables, size_t n_nodes, const double 
 // reciprocals as the sweeps use them (0 in the last word).  rim_tab_build_2d_nodes begins with it.
 inline void rim_tab_front_2d_nodes(size_t n_tables, size_t n_nodes, const double *gamma, size_t n_mu, const double *mu,
                                    const double *sin_k, std::vector<double> &blob, std::vector<double> &h, std::vector<double> &ih,
-                                   std::vector<double> &hm, std::vector<double> &ihm)
+                                   std::vector<double> &hm, std::vector<double> &ihm, int ends = 0)
 {
     using namespace rim;
     size_t cells = 8, mu_cells = 8;
@@ -598,6 +689,7 @@ inline void rim_tab_front_2d_nodes(size_t n_tables, size_t n_nodes, const double
         th[TAB_2D_K] = sin_k ? sin_k[t] : 0.;
         th[TAB_2D_MU_GUIDE] = (double) (mu_guide_at - th_at);
         th[TAB_2D_MU_NODES] = (double) (mu_nodes_at - th_at);
+        th[TAB_2D_ENDS] = (double) ends;
     }
 }
 
@@ -606,11 +698,11 @@ inline void rim_tab_front_2d_nodes(size_t n_tables, size_t n_nodes, const double
 // on h_i = u_{i+1} - u_i, along mu on h_j = mu_{j+1} - mu_j, each with its 1 / h formed once per set.  Both guides as
 // rim_tab_build_grid fills its one.  sin_k null: TAB_2D_K stays 0.  The normalisation of a table is 0 as built.
 inline void rim_tab_build_2d_nodes(size_t n_tables, size_t n_nodes, const double *gamma, size_t n_mu, const double *mu,
-                                   const double *log_n, const double *sin_k, std::vector<double> &blob)
+                                   const double *log_n, const double *sin_k, std::vector<double> &blob, int ends_u = 0, int ends_mu = 0)
 {
     using namespace rim;
     std::vector<double> h, ih, hm, ihm;
-    rim_tab_front_2d_nodes(n_tables, n_nodes, gamma, n_mu, mu, sin_k, blob, h, ih, hm, ihm);
+    rim_tab_front_2d_nodes(n_tables, n_nodes, gamma, n_mu, mu, sin_k, blob, h, ih, hm, ihm, ends_u + 2 * ends_mu);
     const size_t per_table = n_nodes * n_mu * 4, nodes_at = blob.size();
     blob.resize(nodes_at + n_tables * per_table, 0.);
     const size_t longest = n_nodes > n_mu ? n_nodes : n_mu;
@@ -620,19 +712,19 @@ inline void rim_tab_build_2d_nodes(size_t n_tables, size_t n_nodes, const double
         double *nodes = blob.data() + nodes_at + t * per_table;
         for (size_t j = 0; j < n_mu; j++) {
             for (size_t i = 0; i < n_nodes; i++) col[i] = src[i * n_mu + j];
-            rim_tab_spline_row_grid(col.data(), n_nodes, h.data(), ih.data(), m.data(), cp.data(), dp.data());
+            rim_tab_spline_row_grid(col.data(), n_nodes, h.data(), ih.data(), m.data(), cp.data(), dp.data(), ends_u);
             for (size_t i = 0; i < n_nodes; i++) {
                 nodes[(i * n_mu + j) * 4] = col[i];
                 nodes[(i * n_mu + j) * 4 + 1] = m[i];
             }
         }
         for (size_t i = 0; i < n_nodes; i++) {
-            rim_tab_spline_row_grid(src + i * n_mu, n_mu, hm.data(), ihm.data(), m.data(), cp.data(), dp.data());
+            rim_tab_spline_row_grid(src + i * n_mu, n_mu, hm.data(), ihm.data(), m.data(), cp.data(), dp.data(), ends_mu);
             for (size_t j = 0; j < n_mu; j++) nodes[(i * n_mu + j) * 4 + 2] = m[j];
         }
         for (size_t j = 0; j < n_mu; j++) {
             for (size_t i = 0; i < n_nodes; i++) col[i] = nodes[(i * n_mu + j) * 4 + 2];
-            rim_tab_spline_row_grid(col.data(), n_nodes, h.data(), ih.data(), m.data(), cp.data(), dp.data());
+            rim_tab_spline_row_grid(col.data(), n_nodes, h.data(), ih.data(), m.data(), cp.data(), dp.data(), ends_u);
             for (size_t i = 0; i < n_nodes; i++) nodes[(i * n_mu + j) * 4 + 3] = m[i];
         }
     }

@@ -182,6 +182,40 @@ public:
                                                 sin_k.empty() ? nullptr : sin_k.data(), stream),
               "rimphony_ctx_set_tables_2d_device");
     }
+    // Any 2-D form from ln n in host memory with a choice of the spline's ends per axis (rimphony_ctx_set_tables_2d_ends):
+    // ends_gamma and ends_mu are RIMPHONY_TAB_ENDS_NATURAL or RIMPHONY_TAB_ENDS_NOT_A_KNOT; gamma, mu and sin_k empty or given
+    // as for set_tables_2d_device.  Natural ends on both axes install what the form's own set_tables_2d* installs; not-a-knot
+    // ends along mu are for a surface curved at mu = +-1.
+    void set_tables_2d_ends(size_t n_tables, size_t n_nodes, const std::vector<double> &gamma, double gamma_lo, double gamma_hi,
+                            size_t n_mu, const std::vector<double> &mu, const std::vector<double> &log_n,
+                            const std::vector<double> &sin_k, int ends_gamma, int ends_mu) const
+    {
+        if ((!gamma.empty() && gamma.size() != n_nodes) || (!mu.empty() && mu.size() != n_mu))
+            throw std::runtime_error("set_tables_2d_ends: gamma and mu must be empty or hold n_nodes and n_mu values");
+        if (log_n.size() != n_tables * n_nodes * n_mu)
+            throw std::runtime_error("set_tables_2d_ends: log_n must hold n_tables * n_nodes * n_mu values");
+        if (!sin_k.empty() && sin_k.size() != n_tables)
+            throw std::runtime_error("set_tables_2d_ends: sin_k must be empty or hold n_tables values");
+        check(rimphony_ctx_set_tables_2d_ends(ctx_, n_tables, n_nodes, gamma.empty() ? nullptr : gamma.data(), gamma_lo, gamma_hi, n_mu,
+                                              mu.empty() ? nullptr : mu.data(), n_tables ? log_n.data() : nullptr,
+                                              sin_k.empty() ? nullptr : sin_k.data(), ends_gamma, ends_mu),
+              "rimphony_ctx_set_tables_2d_ends");
+    }
+    // The same from ln n in device memory, produced on `stream` (rimphony_ctx_set_tables_2d_device_ends): the set of
+    // set_tables_2d_ends, word for word.
+    void set_tables_2d_device_ends(size_t n_tables, size_t n_nodes, const std::vector<double> &gamma, double gamma_lo, double gamma_hi,
+                                   size_t n_mu, const std::vector<double> &mu, const double *d_log_n, const std::vector<double> &sin_k,
+                                   int ends_gamma, int ends_mu, void *stream = nullptr) const
+    {
+        if ((!gamma.empty() && gamma.size() != n_nodes) || (!mu.empty() && mu.size() != n_mu))
+            throw std::runtime_error("set_tables_2d_device_ends: gamma and mu must be empty or hold n_nodes and n_mu values");
+        if (!sin_k.empty() && sin_k.size() != n_tables)
+            throw std::runtime_error("set_tables_2d_device_ends: sin_k must be empty or hold n_tables values");
+        check(rimphony_ctx_set_tables_2d_device_ends(ctx_, n_tables, n_nodes, gamma.empty() ? nullptr : gamma.data(), gamma_lo, gamma_hi,
+                                                     n_mu, mu.empty() ? nullptr : mu.data(), d_log_n,
+                                                     sin_k.empty() ? nullptr : sin_k.data(), ends_gamma, ends_mu, stream),
+              "rimphony_ctx_set_tables_2d_device_ends");
+    }
     // the installed set as the kernels read it, copied to the host (rimphony_debug_tables); empty without a set
     std::vector<double> tables_blob() const
     {
