@@ -127,6 +127,10 @@ void rimo_calc_f_derivatives(const rimo_dist *d, double gamma, double cos_xi, do
 double rimo_symphony(const rimo_dist *d, int coeff, int stokes, double s, double theta, rimo_counters *c);
 double rimo_heyvaerts(const rimo_dist *d, int coeff, int stokes, double s, double theta, rimo_counters *c);
 double rimo_compute_dimensionless(const rimo_dist *d, int coeff, int stokes, double s, double theta, rimo_counters *c);
+/* the same with the coefficient's status word (the bits of include/rimphony_hip.h:74-80 by their numeric values), set
+ * where this restatement's own control flow meets the failure; see rimo_symphony.c */
+double rimo_compute_dimensionless_st(const rimo_dist *d, int coeff, int stokes, double s, double theta, rimo_counters *c,
+                                     unsigned *status);
 void rimo_compute_all_dimensionless(const rimo_dist *d, double s, double theta, double out[8], rimo_counters *c);
 double rimo_compute_cgs(const rimo_dist *d, int coeff, int stokes, double nu, double b, double n_e, double theta);
 
@@ -149,6 +153,11 @@ double rimo_symphony_deriv_probe(const rimo_dist *d, int coeff, int stokes, int 
  * (else one struct summed over the batch). nthreads<=1: serial. */
 int rimo_batch(int kind, size_t n, const double *s, const double *theta, const double *const *params,
                uint32_t coeff_mask, double *out, rimo_counters *counters, int nthreads);
+
+/* rimo_batch with, per slot, the status word and the integrand samples (rimo_counters.integrand_evals); one task per
+ * (row, slot) */
+int rimo_batch_st(int kind, size_t n, const double *s, const double *theta, const double *const *params,
+                  uint32_t coeff_mask, double *out, uint8_t *status, uint64_t *work, int nthreads);
 
 /* high-frequency closed forms (power_law.rs:133-170, thermal_juettner.rs:94-142): out = {rho_Q, rho_V} */
 int rimo_highfreq(int kind, const double *params, double s, double theta, double out[2]);

@@ -427,6 +427,7 @@ static double inner_qag(hey_state *st, rimo_fn f, double a, double b)
     double result, abserr;
     uint64_t nev = 0;
     int status = rimo_qag(f, st, a, b, 0., 1e-3, 4096, st->iws, &result, &abserr, &nev);
+    if (status) rimo_t_status |= RIMO_ST_INNER_FAIL;
     if (st->c) {
         st->c->gk_evals += nev;
         st->c->inner_qag_calls++;
@@ -461,6 +462,7 @@ static double outer_integral(hey_state *st, rimo_fn f, double a, double b)
     double result, abserr;
     uint64_t nev = 0;
     int status = rimo_qag(f, st, a, b, 0., 1e-3, 4096, st->ows, &result, &abserr, &nev);
+    if (status) rimo_t_status |= RIMO_ST_OUTER_FAIL;
     if (st->c) {
         st->c->outer_gk_evals += nev;
         st->c->outer_qag_calls++;
@@ -530,7 +532,7 @@ double rimo_heyvaerts(const rimo_dist *d, int coeff, int stokes, double s, doubl
 
     steps = 0;
     while (keep_going) {
-        if (++steps > hey_max_steps) goto done;
+        if (++steps > hey_max_steps) { rimo_t_status |= RIMO_ST_CHUNK_CAP; goto done; }
         if (nr_val != 0.) {
             const double rel_deriv = deriv_of(&st, nr_outer_integrand, pomega_right);
             if (rel_deriv == 0. || m_fabs(1. / (rel_deriv * delta_right)) > DELTA_SCALE_FACTOR)
@@ -547,7 +549,7 @@ double rimo_heyvaerts(const rimo_dist *d, int coeff, int stokes, double s, doubl
     keep_going = 1;
     steps = 0;
     while (keep_going) {
-        if (++steps > hey_max_steps) goto done;
+        if (++steps > hey_max_steps) { rimo_t_status |= RIMO_ST_CHUNK_CAP; goto done; }
         const double rel_deriv = deriv_of(&st, nr_outer_integrand, pomega_left);
         if (rel_deriv == 0. || m_fabs(1. / (rel_deriv * delta_left)) > DELTA_SCALE_FACTOR)
             delta_left *= DELTA_SCALE_FACTOR;
@@ -565,7 +567,7 @@ double rimo_heyvaerts(const rimo_dist *d, int coeff, int stokes, double s, doubl
         keep_going = 1;
         steps = 0;
         while (keep_going) {
-            if (++steps > hey_max_steps) goto done;
+            if (++steps > hey_max_steps) { rimo_t_status |= RIMO_ST_CHUNK_CAP; goto done; }
             if (qr_val != 0.) {
                 const double rel_deriv = deriv_of(&st, qr_outer_integrand, sigma_low);
                 if (rel_deriv == 0. || m_fabs(1. / (rel_deriv * delta_sigma)) > DELTA_SCALE_FACTOR) {
@@ -574,6 +576,7 @@ double rimo_heyvaerts(const rimo_dist *d, int coeff, int stokes, double s, doubl
                 }
             }
             else if (qr_is_endless(&st, sigma_low)) {
+                rimo_t_status |= RIMO_ST_CHUNK_CAP;
                 goto done;          /* provably endless: the step cap at once (see qr_is_endless) */
             }
             const double contrib = outer_integral(&st, qr_outer_integrand, sigma_low, sigma_low + delta_sigma);

@@ -103,4 +103,14 @@ static inline void m_sincos(double x, double *s, double *c) { rim_sincos(x, s, c
 #define m_sqrt(x) __builtin_sqrt(x)
 #define m_fabs(x) __builtin_fabs(x)
 
+/* the status word of the coefficient the calling thread is computing (rimo_compute_dimensionless_st, rimo.h): the reason
+ * bits are set where the reference's errors arise; the entry points without a status never read it */
+#define RIMO_ST_INNER_FAIL 1
+#define RIMO_ST_OUTER_FAIL 2
+#define RIMO_ST_CHUNK_CAP 4
+#define RIMO_ST_NONFINITE 16
+#define RIMO_ST_NORM_FAIL 32
+#define RIMO_ST_NOT_COMPUTED 64
+extern __thread unsigned rimo_t_status;
+
 #endif

@@ -27,6 +27,8 @@ static rimo_tuning g_tuning = { 1e-3, 1e-3, 1e5, 30, RIMO_MAX_CHUNKS, 4096 };
 void rimo_set_tuning(const rimo_tuning *t) { g_tuning = t ? *t : TUNING_DEFAULT; }
 void rimo_get_tuning(rimo_tuning *t) { *t = g_tuning; }
 
+__thread unsigned rimo_t_status = 0;
+
 typedef struct {
     const rimo_dist *d;
     int coeff, stokes;
@@ -173,7 +175,10 @@ static double gamma_integral(sym_state *st, double n)
         st->c->inner_qag_calls++;
         if (st->gamma_ws->size > st->c->max_inner_size) st->c->max_inner_size = st->gamma_ws->size;
     }
-    if (status) fail_log(n, gamma0, gamma1, result, abserr, st->negative_lobe, status, st->gamma_ws->size, 0);
+    if (status) {
+        rimo_t_status |= RIMO_ST_INNER_FAIL;
+        fail_log(n, gamma0, gamma1, result, abserr, st->negative_lobe, status, st->gamma_ws->size, 0);
+    }
     return status ? RIM_NAN : result;
 }
 
@@ -200,7 +205,7 @@ static double n_integration(sym_state *st, double n_start, int *failed)
     while (m_fabs(contrib) >= m_fabs(ans / TOLERANCE)) {
         double deriv, derr;
 
-        if (++chunks > g_tuning.max_chunks) { *failed = 1; break; }
+        if (++chunks > g_tuning.max_chunks) { rimo_t_status |= RIMO_ST_CHUNK_CAP; *failed = 1; break; }
 
         rimo_deriv_central(gamma_integral_cb, st, n_start, 1e-10 * n_start, &deriv, &derr);
         if (st->c) st->c->deriv_calls++;
@@ -222,6 +227,7 @@ static double n_integration(sym_state *st, double n_start, int *failed)
                 if (n_ws->size > st->c->max_outer_size) st->c->max_outer_size = n_ws->size;
             }
             if (status) {
+                rimo_t_status |= RIMO_ST_OUTER_FAIL;
                 fail_log(n_start, n_start, n_start + delta_n, contrib, abserr, st->negative_lobe, status, n_ws->size, 1);
                 *failed = 1;
                 break;
@@ -417,6 +423,26 @@ double rimo_compute_dimensionless(const rimo_dist *d, int coeff, int stokes, dou
     return rimo_symphony(d, coeff, stokes, s, theta, c);
 }
 
+/* The same value with the status word of include/rimphony_hip.h:74-80 (its numeric values, restated in rimo_math.h),
+ * set from this restatement's own control flow: INNER_FAIL where a gamma-integral / inner Heyvaerts QAG returns a GSL
+ * error (symphony.rs:380, heyvaerts.rs:204-211) wherever it was called from, OUTER_FAIL where an n-chunk / outer
+ * Heyvaerts QAG does (symphony.rs:269), CHUNK_CAP where a marching loop ends at this restatement's cap (or at once, where
+ * it is provably endless), NONFINITE <=> the value is NaN.  (Faraday, I) is not available: NaN, NONFINITE | NOT_COMPUTED. */
+double rimo_compute_dimensionless_st(const rimo_dist *d, int coeff, int stokes, double s, double theta, rimo_counters *c,
+                                     unsigned *status)
+{
+    double v;
+    rimo_t_status = 0;
+    if (coeff == RIMO_FARADAY && stokes == RIMO_STOKES_I) {
+        *status = RIMO_ST_NONFINITE | RIMO_ST_NOT_COMPUTED;
+        return RIM_NAN;
+    }
+    v = rimo_compute_dimensionless(d, coeff, stokes, s, theta, c);
+    *status = rimo_t_status | (v != v ? RIMO_ST_NONFINITE : 0u);
+    rimo_t_status = 0;
+    return v;
+}
+
 static const int SLOT_COEFF[8] = { RIMO_EMISSION, RIMO_ABSORPTION, RIMO_EMISSION, RIMO_ABSORPTION,
                                    RIMO_EMISSION, RIMO_ABSORPTION, RIMO_FARADAY, RIMO_FARADAY };
 static const int SLOT_STOKES[8] = { RIMO_STOKES_I, RIMO_STOKES_I, RIMO_STOKES_Q, RIMO_STOKES_Q,
@@ -495,6 +521,40 @@ int rimo_batch(int kind, size_t n, const double *s, const double *theta, const d
         counters_add(&total, &local);
     }
     if (counters) *counters = total;
+    return 0;
+}
+
+/* rimo_batch with a status word and the integrand samples of every slot; unselected slots: NaN, NONFINITE | NOT_COMPUTED,
+ * no work; a failed normalisation: NaN, NONFINITE | NORM_FAIL on every selected slot */
+int rimo_batch_st(int kind, size_t n, const double *s, const double *theta, const double *const *params,
+                  uint32_t coeff_mask, double *out, uint8_t *status, uint64_t *work, int nthreads)
+{
+    static const int NPAR[4] = { 4, 1, 5, 4 };
+    if (kind < 0 || kind > 3) return -1;
+    const int np = NPAR[kind];
+    if (nthreads < 1) nthreads = 1;
+
+#pragma omp parallel for schedule(dynamic, 1) num_threads(nthreads)
+    for (long long t = 0; t < (long long) n * 8; t++) {
+        const long long i = t / 8;
+        const int k = (int) (t % 8);
+        double par[RIMO_MAX_PARAMS];
+        rimo_dist d;
+        rimo_counters c;
+        double v = RIM_NAN;
+        unsigned st = RIMO_ST_NONFINITE | RIMO_ST_NOT_COMPUTED;
+        memset(&c, 0, sizeof c);
+        if (coeff_mask & (1u << k)) {
+            for (int j = 0; j < np; j++) par[j] = params[j][i];
+            if (rimo_dist_init(&d, kind, par))
+                st = RIMO_ST_NONFINITE | RIMO_ST_NORM_FAIL;
+            else
+                v = rimo_compute_dimensionless_st(&d, SLOT_COEFF[k], SLOT_STOKES[k], s[i], theta[i], &c, &st);
+        }
+        out[t] = v;
+        status[t] = (uint8_t) st;
+        work[t] = c.integrand_evals;
+    }
     return 0;
 }
 

@@ -1,7 +1,6 @@
 """The committed fixture of the long Faraday outer quadratures (tests/golden/faraday_long_det.npz, written by
 tools/make_faraday_long_fixture.py) for the host and the GPU tests: loading, the size classes, and the rows of a kind as the
 arrays a batch call takes.  Test infrastructure only."""
-import ctypes
 import os
 
 import numpy as np
@@ -44,12 +43,11 @@ def rows_of(config, classes):
 
 
 def recompute(L, i, slot):
-    """(value, Counters dict) of slot `slot` of fixture row i by the oracle library L"""
+    """(value, Counters dict, status word) of slot `slot` of fixture row i by the oracle library L"""
     f = load()
     kind = {c: k for k, c in enumerate(CONFIGS)}[str(f["config"][i])]
     d, st = oracle_bind.mkdist(L, kind, [float(x) for x in f["params"][i, :int(f["nparams"][i])]])
     assert st == 0
-    c = oracle_bind.Counters()
     co, stk = SLOTS[slot]
-    v = L.rimo_compute_dimensionless(ctypes.byref(d), co, stk, float(f["s"][i]), float(f["theta"][i]), ctypes.byref(c))
-    return v, c.as_dict()
+    v, status, c = oracle_bind.compute_st(L, d, co, stk, float(f["s"][i]), float(f["theta"][i]))
+    return v, c, status

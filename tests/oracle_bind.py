@@ -2,7 +2,7 @@
 and bench.py's cpu_baseline leg.  Test infrastructure only."""
 import ctypes
 import os
-from ctypes import POINTER, c_double, c_int, c_size_t, c_uint32, c_uint64, c_void_p
+from ctypes import POINTER, c_double, c_int, c_size_t, c_uint8, c_uint32, c_uint64, c_void_p
 
 import numpy as np
 
@@ -48,6 +48,11 @@ def load(flavour="det"):
     L.rimo_calc_f_derivatives.argtypes = [POINTER(Dist), c_double, c_double, dp, dp]
     L.rimo_compute_dimensionless.restype = c_double
     L.rimo_compute_dimensionless.argtypes = [POINTER(Dist), c_int, c_int, c_double, c_double, POINTER(Counters)]
+    L.rimo_compute_dimensionless_st.restype = c_double
+    L.rimo_compute_dimensionless_st.argtypes = [POINTER(Dist), c_int, c_int, c_double, c_double, POINTER(Counters),
+                                                POINTER(ctypes.c_uint)]
+    L.rimo_batch_st.restype = c_int
+    L.rimo_batch_st.argtypes = [c_int, c_size_t, dp, dp, POINTER(dp), c_uint32, dp, POINTER(c_uint8), POINTER(c_uint64), c_int]
     L.rimo_compute_cgs.restype = c_double
     L.rimo_compute_cgs.argtypes = [POINTER(Dist), c_int, c_int, c_double, c_double, c_double, c_double]
     L.rimo_gamma_integrand.restype = c_double
@@ -106,6 +111,27 @@ def batch(L, kind, s, theta, params, mask=0xFF, nthreads=8, want_counters=False)
     rc = L.rimo_batch(kind, n, _dp(s), _dp(theta), pp, mask, _dp(out), ctypes.byref(c), nthreads)
     assert rc == 0
     return (out, c.as_dict()) if want_counters else out
+
+
+def compute_st(L, dist, coeff, stokes, s, theta):
+    """(value, status word, Counters as a dict) of one coefficient: rimo_compute_dimensionless_st"""
+    c, st = Counters(), ctypes.c_uint(0)
+    v = L.rimo_compute_dimensionless_st(ctypes.byref(dist), coeff, stokes, s, theta, ctypes.byref(c), ctypes.byref(st))
+    return v, int(st.value), c.as_dict()
+
+
+def batch_st(L, kind, s, theta, params, mask=0xFF, nthreads=8):
+    """(values [n][8], status [n][8] uint8, work [n][8] uint64 = the integrand samples of each slot): rimo_batch_st"""
+    s = np.ascontiguousarray(s, dtype=np.float64)
+    theta = np.ascontiguousarray(theta, dtype=np.float64)
+    params = [np.ascontiguousarray(p, dtype=np.float64) for p in params]
+    n = len(s)
+    out, status, work = np.zeros((n, 8)), np.zeros((n, 8), dtype=np.uint8), np.zeros((n, 8), dtype=np.uint64)
+    pp = (POINTER(c_double) * len(params))(*[_dp(p) for p in params])
+    rc = L.rimo_batch_st(kind, n, _dp(s), _dp(theta), pp, mask, _dp(out), status.ctypes.data_as(POINTER(c_uint8)),
+                         work.ctypes.data_as(POINTER(c_uint64)), nthreads)
+    assert rc == 0
+    return out, status, work
 
 
 def batch_norm(L, kind, params):

@@ -69,9 +69,10 @@ def _recompute_and_compare(oracle, cls):
     tasks = [(int(i), slot) for i in np.flatnonzero(f["cls"] == cls) for slot in range(8)]
     with ThreadPoolExecutor(min(16, os.cpu_count() or 1)) as pool:
         res = list(pool.map(lambda t: fl.recompute(oracle, *t), tasks))
-    for (i, slot), (v, c) in zip(tasks, res):
+    for (i, slot), (v, c, status) in zip(tasks, res):
         where = (str(f["config"][i]), int(f["row"][i]), slot)
         assert same_bits(v, f["values"][i, slot]), (where, v, f["values"][i, slot])
+        assert status == f["status"][i, slot], (where, status, int(f["status"][i, slot]))
         assert c["integrand_evals"] == f["integrand_evals"][i, slot], where
         if slot >= 6:
             for name in ("max_outer_size", "outer_qag_calls", "inner_qag_calls"):
@@ -79,7 +80,7 @@ def _recompute_and_compare(oracle, cls):
 
 
 def test_mid_rows_reproduce(oracle):
-    """The 'mid' rows, all eight slots, computed again by the oracle: the stored bits and counters."""
+    """The 'mid' rows, all eight slots, computed again by the oracle: the stored bits, status words and counters."""
     _recompute_and_compare(oracle, "mid")
 
 

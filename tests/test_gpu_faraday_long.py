@@ -3,8 +3,8 @@
 the outer subinterval list -- 48: rounds (pitchy-kappa); 64: the list leaves LDS; limit / 2 + 2 = 2050: GSL's qpsrt no
 longer keeps its list fully sorted, the kernels go on picking by argmax; 4096: the quadrature gives up -- and the fixture's
 rows reach every one of those classes.  Every comparison is bit for bit: values with the NaN pattern, the per-coefficient
-work column against the oracle's integrand samples, the launch's sample count, and the status words by the rule
-NaN <=> NONFINITE set, finite <=> 0, ended at 4096 => OUTER_FAIL set.
+work column against the oracle's integrand samples, the launch's sample count, and the status words: equal to the
+oracle's (the fixture's status column), and by the rule NaN <=> NONFINITE set, finite <=> 0, ended at 4096 => OUTER_FAIL set.
 
 The 'mid' rows (seconds of one CPU core) run with all eight slots in the session's context, whatever its mode; the 'limit'
 rows (a quarter of a million inner integrals in one chain) only on a context that owns the device, where the cooperative
@@ -97,6 +97,9 @@ def check_launch(cfg, cls, got, where):
     nan = np.isnan(out[:, sel])
     assert ((st[:, sel] & ST_NONFINITE) != 0)[nan].all(), st[:, sel].tolist()
     assert (st[:, sel][~nan] == 0).all(), st[:, sel].tolist()
+    # the FULL word of every selected slot is the oracle's (the fixture's status column: rimo_compute_dimensionless_st)
+    want_st = f["status"][idx][:, sel].astype(np.int64)
+    assert (st[:, sel] == want_st).all(), (st[:, sel].tolist(), want_st.tolist())
     at_limit = f["max_outer_size"][idx].astype(np.int64) == fl.LIMIT                    # [rows][2]: the Faraday pair
     assert ((st[:, 6:] & ST_OUTER_FAIL) != 0)[at_limit].all(), st[:, 6:].tolist()
     if cls == "limit":

@@ -12,6 +12,8 @@ to the oracle's bits in every size class of the outer subinterval list:
   s, theta [n], params [n][5]      the row as workload.make_rows generates it (params padded with NaN), nparams [n]
   values [n][8]                    rimo_compute_dimensionless per slot (api.SLOTS order; NaN where a quadrature fails)
   integrand_evals [n][8]           the integrand samples of each slot
+  status [n][8]                    the status word of each slot (uint8; the bits of include/rimphony_hip.h:74-80) as
+                                   rimo_compute_dimensionless_st sets it from the oracle's own control flow
   max_outer_size, outer_qag_calls, inner_qag_calls [n][2]
                                    of the Faraday pair (slots 6, 7 = rho_Q, rho_V)
   cls [n]                          'mid' (seconds of CPU) or 'limit' (an outer list beyond limit / 2 + 2: a minute or two)
@@ -22,7 +24,6 @@ timestamps: the same oracle writes the same bytes.
 
 CPU only; a few minutes on 16 threads.  Usage: python tools/make_faraday_long_fixture.py [--threads 16]"""
 import argparse
-import ctypes
 import io
 import os
 import sys
@@ -72,14 +73,13 @@ def one_row(config, row):
 
 
 def compute(L, config, row, slot):
-    """(value, Counters as a dict) of one slot of one row"""
+    """(value, Counters as a dict, status word) of one slot of one row"""
     kind, s, theta, params = one_row(config, row)
     d, st = oracle_bind.mkdist(L, kind, params)
     assert st == 0, (config, row)
-    c = oracle_bind.Counters()
     co, stk = SLOTS[slot]
-    v = L.rimo_compute_dimensionless(ctypes.byref(d), co, stk, s, theta, ctypes.byref(c))
-    return v, c.as_dict()
+    v, status, c = oracle_bind.compute_st(L, d, co, stk, s, theta)
+    return v, c, status
 
 
 def compute_rows(L, rows, slots, threads):
@@ -112,7 +112,8 @@ def assemble(rows, res):
     n = len(rows)
     f = {"config": np.array([r[0] for r in rows]), "row": np.array([r[1] for r in rows], dtype=np.int64),
          "cls": np.array([r[2] for r in rows]), "s": np.zeros(n), "theta": np.zeros(n), "params": np.full((n, 5), np.nan),
-         "nparams": np.zeros(n, dtype=np.int64), "values": np.zeros((n, 8)), "integrand_evals": np.zeros((n, 8), dtype=np.uint64),
+         "nparams": np.zeros(n, dtype=np.int64), "values": np.zeros((n, 8)), "status": np.zeros((n, 8), dtype=np.uint8),
+         "integrand_evals": np.zeros((n, 8), dtype=np.uint64),
          "max_outer_size": np.zeros((n, 2), dtype=np.uint64), "outer_qag_calls": np.zeros((n, 2), dtype=np.uint64),
          "inner_qag_calls": np.zeros((n, 2), dtype=np.uint64)}
     for i, (cfg, row, _) in enumerate(rows):
@@ -120,8 +121,9 @@ def assemble(rows, res):
         f["nparams"][i] = len(params)
         f["params"][i, :len(params)] = params
         for slot in range(8):
-            v, c = res[cfg, row, slot]
+            v, c, status = res[cfg, row, slot]
             f["values"][i, slot] = v
+            f["status"][i, slot] = status
             f["integrand_evals"][i, slot] = c["integrand_evals"]
             if slot >= 6:
                 for name in ("max_outer_size", "outer_qag_calls", "inner_qag_calls"):
@@ -143,6 +145,9 @@ def check_classes(f):
     # the class tag says where a row may run: a 'mid' row has no list past limit / 2 + 2
     mid = f["cls"] == "mid"
     assert (size[mid] < HALF).all() and (size[~mid].max(axis=1) > HALF).all()
+    # the status words: NONFINITE <=> NaN in every slot, and a list that ran to the limit is an OUTER_FAIL
+    assert (((f["status"] & 16) != 0) == np.isnan(f["values"])).all()
+    assert ((f["status"][:, 6:] & 2) != 0)[size == LIMIT].all()
 
 
 def write_npz(path, arrays):
