@@ -414,6 +414,40 @@ int rimphony_ctx_set_tables_2d_device_ends(rimphony_ctx *ctx, size_t n_tables, s
                                            double gamma_hi, size_t n_mu, const double *mu, const double *d_log_n,
                                            const double *sin_k, int ends_gamma, int ends_mu, void *stream);
 
+/* Tabulated distributions as a FAMILY with a continuous index per row: a set of energy tables on nodes uniform in ln gamma,
+ * optionally with a sin^k xi exponent per table, where the one parameter of a RIMPHONY_TABULATED row is a REAL index x and
+ * every sample blends two neighbouring tables -- a Fokker-Planck run stored at 64 times, a cooling sequence, a scan over
+ * magnetisation, evaluated between the stored states.
+ *   log_n   HOST, [n_tables][n_nodes]: ln n at the nodes, shapes and limits exactly as for rimphony_ctx_set_tables;
+ *   sin_k   NULL, or HOST [n_tables]: the exponent of each table, range and meaning as for rimphony_ctx_set_tables_pitchy
+ *           (there is no log_g here).
+ * Checked with the plain forms' own checks (RIMPHONY_EINVAL, the previous set stays); n_tables = 0 clears the set; the call
+ * replaces a set of any form and a set of any form replaces it; rimphony_debug_tables reads the set back.
+ * The index rule of a row:
+ *   valid   x finite and 0 <= x <= n_tables - 1; -0.0 counts as 0;
+ *   tables  a = (long long) x the lower one, b = a + 1 the upper one -- except at a == n_tables - 1, where b = a;
+ *   weight  w = x - a;
+ *   blend   H = H_a + w (H_b - H_a) for the spline and k = k_a + w (k_b - k_a) for the exponent, each as one
+ *           fma(w, q_b - q_a, q_a) per quantity -- the four node words of the sample's interval, then ONE cubic --, so that
+ *           w = 0 gives q_a itself;
+ *   f       = norm e^H sin^k xi / (gamma^2 beta) inside the table, 0 outside, with the derivatives of the plain forms;
+ *   else    a NaN, an index out of range or a non-integer beyond the last table is a NaN normalisation: every selected slot
+ *           of the row is NaN with RIMPHONY_ST_NORM_FAIL, as for a bad index of the other forms.
+ * The normalisation is per row: norm = 1 / (4 pi P(k) int e^H dgamma) over the blended spline with the settings of the plain
+ * forms, P(k) the closed form of the pitchy kinds at the blended k (1 without sin_k).  Nothing is integrated at install.
+ * A row at an integer x carries the BITS of the same table installed through rimphony_ctx_set_tables (no sin_k) or
+ * rimphony_ctx_set_tables_pitchy (sin_k, no g): values, status words, work counters, the normalisation and calc_f.  The
+ * existing entries keep refusing a non-integer index.
+ * The blend is linear in the index, and exact where ln n is linear in the parameter the tables are spaced in: ln n of a power
+ * law in p, ln n of a Juettner shape in 1 / T, ln sin^k xi in k.  Two tables reproduce the analytic power law at every p
+ * between them (and with sin_k the pitchy power law at every (p, k)) to the accuracy of the plain form.  Elsewhere the error
+ * is that of linear interpolation of ln n between neighbouring tables.
+ * RIMPHONY_TAB_GROUP chooses between the group kernel and one wave per coefficient as for the other forms (the same bits).
+ * Not offered: families of the forms with g, on given nodes or in 2-D (their normalisations are fixed at install); families
+ * in two parameters; higher-order blending across tables; a crank-out subcommand; a bench leg. */
+int rimphony_ctx_set_tables_family(rimphony_ctx *ctx, size_t n_tables, size_t n_nodes, double gamma_lo, double gamma_hi,
+                                   const double *log_n, const double *sin_k);
+
 /* Diagnostics: the installed table set as the kernels read it, copied to `out` (HOST, `cap` doubles).  *n_doubles is the
  * size of the set in doubles, 0 (and nothing copied) where the context has none; RIMPHONY_EINVAL, with *n_doubles still set,
  * where cap is smaller.  The set holds offsets, never addresses, so two installs of the same numbers -- through a host entry

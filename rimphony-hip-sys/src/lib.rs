@@ -120,6 +120,15 @@ extern "C" {
         log_g: *const c_double,
         sin_k: *const c_double,
     ) -> c_int;
+    pub fn rimphony_ctx_set_tables_family(
+        ctx: *mut rimphony_ctx,
+        n_tables: usize,
+        n_nodes: usize,
+        gamma_lo: c_double,
+        gamma_hi: c_double,
+        log_n: *const c_double,
+        sin_k: *const c_double,
+    ) -> c_int;
     pub fn rimphony_ctx_set_tables_grid(
         ctx: *mut rimphony_ctx,
         n_tables: usize,
@@ -389,6 +398,24 @@ impl HipContext {
             rimphony_ctx_set_tables_pitchy(
                 self.raw, log_n.len() / n_nodes, n_nodes, gamma_lo, gamma_hi, log_n.as_ptr(), n_mu,
                 if log_g.is_empty() { std::ptr::null() } else { log_g.as_ptr() }, sin_k.as_ptr(),
+            )
+        };
+        if rc != RIMPHONY_OK {
+            return Err(error_text(rc));
+        }
+        Ok(())
+    }
+
+    /// A family of energy tables (include/rimphony_hip.h: rimphony_ctx_set_tables_family): the parameter of a row is then a
+    /// real index into the tables, whose splines every sample blends.  `sin_k` empty, or one exponent in [0, 100] per table.
+    pub fn set_tables_family(&self, n_nodes: usize, gamma_lo: f64, gamma_hi: f64, log_n: &[f64], sin_k: &[f64]) -> Result<(), String> {
+        if n_nodes == 0 || log_n.len() % n_nodes != 0 || (!sin_k.is_empty() && sin_k.len() != log_n.len() / n_nodes) {
+            return Err(error_text(RIMPHONY_EINVAL));
+        }
+        let rc = unsafe {
+            rimphony_ctx_set_tables_family(
+                self.raw, log_n.len() / n_nodes, n_nodes, gamma_lo, gamma_hi, log_n.as_ptr(),
+                if sin_k.is_empty() { std::ptr::null() } else { sin_k.as_ptr() },
             )
         };
         if rc != RIMPHONY_OK {

@@ -78,6 +78,9 @@ def build_hip(force=False, verbose=False):
                                     os.path.join(CSRC, "rimphony_tab_2d_nodes.hip"), os.path.join(CSRC, "rimphony_tab_2d_nodes_group.hip"),
                                     os.path.join(CSRC, "rimphony_tab_2d_nodes_pitchy.hip"),
                                     os.path.join(CSRC, "rimphony_tab_2d_nodes_pitchy_group.hip"),
+                                    os.path.join(CSRC, "rimphony_tab_family.hip"), os.path.join(CSRC, "rimphony_tab_family_group.hip"),
+                                    os.path.join(CSRC, "rimphony_tab_family_pitchy.hip"),
+                                    os.path.join(CSRC, "rimphony_tab_family_pitchy_group.hip"),
                                     os.path.join(CSRC, "rimphony_tab_install.hip"),
                                     "-ldl", "-o", LIB]
     if verbose:
@@ -165,6 +168,11 @@ def build_tilt_oracle():
 def build_tab_pitchy_oracle():
     """The same for table sets with a sin^k xi prefactor per table (tests/support/tab_pitchy_oracle.cpp)."""
     return _build_dist_oracle("tab_pitchy_oracle.cpp", "liboracle_tabpitchy.so")
+
+
+def build_tab_family_oracle():
+    """The same for families of energy tables, a real index per row (tests/support/tab_family_oracle.cpp)."""
+    return _build_dist_oracle("tab_family_oracle.cpp", "liboracle_tabfamily.so")
 
 
 def build_pitchy_beam_oracle():

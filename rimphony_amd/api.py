@@ -14,6 +14,8 @@ behaviour; see src/lib.rs of pkgw/rimphony):
   PitchyKappaDistribution(kappa, width, k).gamma_cutoff(..)...         pitchy_kappa.rs:70-125
   TabulatedDistribution(gamma_lo, gamma_hi, log_n)  the open DistributionFunction trait (lib.rs:111-146) as data: a table
                                                     of ln n(gamma), spline-interpolated inside the integrand
+  TabulatedFamily(gamma_lo, gamma_hi, log_n, ...)   a set of such tables with a continuous parameter: .at(value) is the member
+                                                    between two stored tables, blended inside the integrand
 
 plus the batched compute() the north star adds: `compute_batch`.  PyTorch is
 used only as plumbing (device buffers, the current HIP stream).  Everything is
@@ -337,6 +339,24 @@ class Context:
         capi.check(self.lib.rimphony_ctx_set_tables(self.handle, t.shape[0], t.shape[1], float(gamma_lo), float(gamma_hi),
                                                     t.ctypes.data_as(ctypes.POINTER(ctypes.c_double))),
                    "rimphony_ctx_set_tables")
+
+    def set_tables_family(self, gamma_lo, gamma_hi, log_n, sin_k=None):
+        """The context's table set as a FAMILY: log_n [n_tables][n_nodes] as for set_tables, and the one parameter of a
+        TABULATED row a real index x in [0, n_tables - 1].  Every sample blends the splines of tables floor(x) and
+        floor(x) + 1 with the weight x - floor(x); the normalisation is per row, over the blended spline.  sin_k (a scalar, or
+        one value per table, each in [0, 100]) gives each table a sin^k xi prefactor whose exponent is blended likewise.  A
+        row at an integer x carries the bits of that table installed through set_tables; an x outside the range is a NaN
+        row.  Replaces the previous set of any form; log_n None clears it.  Synchronous (include/rimphony_hip.h:
+        rimphony_ctx_set_tables_family)."""
+        if log_n is None:
+            capi.check(self.lib.rimphony_ctx_set_tables_family(self.handle, 0, 0, 1.0, 2.0, None, None), "rimphony_ctx_set_tables_family")
+            return
+        t = check_tables(gamma_lo, gamma_hi, log_n)
+        k = None if sin_k is None else check_sin_k(sin_k, t.shape[0])
+        dp = ctypes.POINTER(ctypes.c_double)
+        capi.check(self.lib.rimphony_ctx_set_tables_family(self.handle, t.shape[0], t.shape[1], float(gamma_lo), float(gamma_hi),
+                                                           t.ctypes.data_as(dp), None if k is None else k.ctypes.data_as(dp)),
+                   "rimphony_ctx_set_tables_family")
 
     def set_tables_grid(self, gamma, log_n, log_g=None, sin_k=None):
         """The context's table set on gamma nodes of the caller's choosing: gamma [n_nodes] strictly increasing from >= 1,
@@ -1155,6 +1175,82 @@ class TabulatedDistribution2DNodes(TabulatedDistribution):
     def _install(self, ctx):
         ctx.set_tables_2d_nodes(self.gamma, self.mu, self.log_n, self.sin_k, self.ends)
         return ctx
+
+
+class TabulatedFamily:
+    """A family of tabulated distributions with a continuous parameter: log_n [n_tables][n_nodes] = ln n(gamma) at nodes
+    uniform in ln gamma from gamma_lo to gamma_hi, table i belonging to the value param[i] of whatever the tables were
+    stored by (a time, a temperature, a magnetisation); sin_k optionally one sin^k xi exponent per table
+    (Context.set_tables_family).  Between two tables the library blends ln n -- and k -- LINEARLY IN THE INDEX, and
+    index() maps a value to the index piecewise linearly in param.  The blend is therefore exact where ln n is linear in
+    param: a power law stored by p, sin^k xi stored by k.  ln n of a Juettner shape is linear in 1 / T, not in T: to be
+    exact there, space param in 1 / T (param = 1 / T of each table) and ask for at(1 / T).  param None: the index itself.
+
+    A batch over many rows installs the family once and passes x = family.index(values) as the one parameter array of kind
+    TABULATED; at(value) is the one-point object with the reference's trait."""
+
+    def __init__(self, gamma_lo, gamma_hi, log_n, sin_k=None, param=None):
+        self.gamma_lo, self.gamma_hi = float(gamma_lo), float(gamma_hi)
+        self.log_n = check_tables(self.gamma_lo, self.gamma_hi, log_n)
+        n = self.log_n.shape[0]
+        self.sin_k = None if sin_k is None else check_sin_k(sin_k, n)
+        self.param = np.arange(n, dtype=np.float64) if param is None else np.ascontiguousarray(param, dtype=np.float64)
+        if self.param.shape != (n,):
+            raise ValueError("param: expected one value per table (%d), got shape %r" % (n, self.param.shape))
+        d = np.diff(self.param)
+        if not np.isfinite(self.param).all() or not ((d > 0).all() or (d < 0).all()):
+            raise ValueError("param: expected finite, strictly monotonic values")
+
+    @classmethod
+    def from_function(cls, fn, gamma_lo, gamma_hi, param, n_nodes=4096, sin_k=None):
+        """Tabulate n(gamma; a) = fn(gamma, a) (vectorised in gamma, positive) for every a of param on n_nodes nodes uniform
+        in ln gamma; sin_k as in the constructor."""
+        gamma = np.exp(np.linspace(math.log(gamma_lo), math.log(gamma_hi), int(n_nodes)))
+        gamma[0], gamma[-1] = gamma_lo, gamma_hi
+        param = np.atleast_1d(np.asarray(param, dtype=np.float64))
+        log_n = np.stack([np.log(np.asarray(fn(gamma, float(a)), dtype=np.float64)) for a in param])
+        return cls(gamma_lo, gamma_hi, log_n, sin_k, param)
+
+    def index(self, values):
+        """The real index of each value: piecewise linear in param.  ValueError for a value outside param (or a NaN)."""
+        v = np.asarray(values, dtype=np.float64)
+        lo, hi = min(self.param[0], self.param[-1]), max(self.param[0], self.param[-1])
+        if not ((v >= lo) & (v <= hi)).all():
+            raise ValueError("value outside the family's parameter range [%r, %r]" % (lo, hi))
+        n = len(self.param)
+        if n == 1:
+            return np.zeros_like(v)
+        if self.param[0] < self.param[-1]:
+            return np.interp(v, self.param, np.arange(n, dtype=np.float64))
+        return np.interp(v, self.param[::-1], np.arange(n, dtype=np.float64)[::-1])
+
+    def _install(self, ctx):
+        ctx.set_tables_family(self.gamma_lo, self.gamma_hi, self.log_n, self.sin_k)
+        return ctx
+
+    def at(self, value):
+        """The member of the family at `value`: full_calculation, calc_f and calc_f_derivatives, as TabulatedDistribution."""
+        return _FamilyMember(self, float(self.index(float(value))))
+
+
+class _FamilyMember(_DistributionFunction):
+    def __init__(self, family, x):
+        self.family, self.x = family, x
+
+    def _install(self, ctx):
+        return self.family._install(ctx)
+
+    def _kind_params(self):
+        return TABULATED, [self.x]
+
+    def _calc(self, gamma, cos_xi):
+        self._install(self.ctx or default_context())
+        return super()._calc(gamma, cos_xi)
+
+    def full_calculation(self, ctx=None):
+        calc = _TabulatedCalculator(self, ctx)
+        calc.params = [self.x]
+        return calc
 
 
 class _TabulatedCalculator(FullSynchrotronCalculator):

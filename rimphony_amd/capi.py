@@ -25,6 +25,7 @@ SYMBOLS = [
     "rimphony_ctx_set_tables_2d_pitchy", "rimphony_ctx_set_tables_2d_grid_pitchy", "rimphony_ctx_set_tables_2d_nodes",
     "rimphony_ctx_set_tables_2d_device", "rimphony_debug_tables",
     "rimphony_ctx_set_tables_2d_ends", "rimphony_ctx_set_tables_2d_device_ends",
+    "rimphony_ctx_set_tables_family",
 ]
 
 
@@ -187,6 +188,9 @@ def load():
         lib.rimphony_ctx_set_tables_2d_device_ends.restype = c_int
         lib.rimphony_ctx_set_tables_2d_device_ends.argtypes = [c_void_p, c_size_t, c_size_t, dp, c_double, c_double, c_size_t, dp,
                                                                c_void_p, dp, c_int, c_int, c_void_p]
+    if hasattr(lib, "rimphony_ctx_set_tables_family"):
+        lib.rimphony_ctx_set_tables_family.restype = c_int
+        lib.rimphony_ctx_set_tables_family.argtypes = [c_void_p, c_size_t, c_size_t, c_double, c_double, dp, dp]
     if hasattr(lib, "rimphony_ctx_set_tables_grid"):
         lib.rimphony_ctx_set_tables_grid.restype = c_int
         lib.rimphony_ctx_set_tables_grid.argtypes = [c_void_p, c_size_t, c_size_t, dp, dp, c_size_t, dp, dp]

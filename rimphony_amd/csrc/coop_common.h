@@ -23,6 +23,8 @@ __device__ inline void load_params(const ParamPtrs &pp, size_t i, DistParams &d)
         d.par[0] = pp.p[0][i];
         d.par[1] = rim_frombits((uint64_t) (uintptr_t) pp.p[1]);
         d.par[2] = 0.; d.par[3] = 0.; d.par[4] = 0.;
+        // (a family with a sin^k prefactor: p[2] is the context's array of row lines, dev_symphony.h: tab_family_line)
+        if (KIND == DIST_TABULATED_FAMILY_PITCHY) d.par[2] = rim_frombits((uint64_t) (uintptr_t) (pp.p[2] + i * TAB_FAMILY_LINE));
         return;
     }
     constexpr int NP = (KIND == DIST_POWER_LAW) ? 4 : (KIND == DIST_THERMAL_JUETTNER) ? 1 : (KIND == DIST_PITCHY_PL) ? 5 : 4;

@@ -63,8 +63,11 @@ __global__ __launch_bounds__(64) void norm_kernel(ParamPtrs pp, size_t n, double
         DistParams d;
         load_params<KIND>(pp, i, d);
         // (the tabulated kind: dist_prepare replaces the table index in par[0], so the index is judged first)
-        constexpr bool TAB = KIND == DIST_TABULATED || KIND == DIST_TABULATED_PITCHY || KIND == DIST_TABULATED_GRID;
-        const bool tab_ok = !TAB || tab_row_ok(pp.p[1], d.par[0]);
+        constexpr bool TAB = KIND == DIST_TABULATED || KIND == DIST_TABULATED_PITCHY || KIND == DIST_TABULATED_GRID || tab_kind_family(KIND);
+        // (a family judges a real index: x in [0, n_tables - 1])
+        size_t fam_a;
+        double fam_w;
+        const bool tab_ok = !TAB || (tab_kind_family(KIND) ? tab_family_row(pp.p[1], d.par[0], fam_a, fam_w) : tab_row_ok(pp.p[1], d.par[0]));
         dist_prepare<KIND>(d, RIM_NAN);
 
         double lo, hi, epsrel, pa = 1.;
@@ -74,7 +77,7 @@ __global__ __launch_bounds__(64) void norm_kernel(ParamPtrs pp, size_t n, double
             lo = d.inv_kappa_width; hi = d.neg_inverse_t; epsrel = 1e-8;
             // a pitch row: P = 1/2 int g dmu of its header takes the place of the pitchy kinds' 2F1 (pitchy_pl.rs:98-111)
             // (a sin^k set: every table has one, with the factor in it -- NaN where its quadrature failed)
-            if (tab_has_pitch(d)) pa = ((const double *) (uintptr_t) rim_bits(d.par[0]))[TAB_PITCH_P];
+            if (tab_norm_has_pitch<KIND>(d)) pa = ((const double *) (uintptr_t) rim_bits(d.par[0]))[TAB_PITCH_P];
         } else if (KIND == DIST_POWER_LAW) { lo = d.par[1]; hi = d.par[2]; epsrel = 1e-8; }
         else if (KIND == DIST_PITCHY_PL) { lo = d.par[2]; hi = d.par[3]; epsrel = 1e-8; pa = hyperg_2F1_at_1(0.5, -0.5 * d.par[1], 1.5); }
         else if (KIND == DIST_PITCHY_KAPPA) {
@@ -91,7 +94,7 @@ __global__ __launch_bounds__(64) void norm_kernel(ParamPtrs pp, size_t n, double
         wave_qag(f, g, st, lo, hi, 0., epsrel, 1000, q, &s_qpark);
         double v = RIM_NAN;
         if (q.status == QAG_SUCCESS) {
-            if (KIND == DIST_PITCHY_PL || KIND == DIST_PITCHY_KAPPA || (TAB && tab_has_pitch(d)))
+            if (KIND == DIST_PITCHY_PL || KIND == DIST_PITCHY_KAPPA || (TAB && tab_norm_has_pitch<KIND>(d)))
                 v = 1. / (2. * RIM_TWO_PI * pa * q.result);
             else v = 1. / (2. * RIM_TWO_PI * q.result);
         }

@@ -42,12 +42,19 @@ enum { DIST_POWER_LAW = 0, DIST_THERMAL_JUETTNER = 1, DIST_PITCHY_PL = 2, DIST_P
        // nor these two: the 2-D form on gamma nodes AND mu nodes of the caller's choosing (rim_tab_build_2d_nodes), without
        // and with a sin^k xi prefactor.  The surface of the other 2-D forms, the gamma lookup of DIST_TABULATED_2D_GRID and the
        // same kind of lookup along mu (tab_2d_nodes_mu_interval); the older forms keep the code they always ran.
-       DIST_TABULATED_2D_NODES = 12, DIST_TABULATED_2D_NODES_PITCHY = 13 };
+       DIST_TABULATED_2D_NODES = 12, DIST_TABULATED_2D_NODES_PITCHY = 13,
+       // nor these two: the tabulated kind where the set is a FAMILY (rim_tab_build_family): energy tables on nodes uniform in
+       // ln gamma, without and with a sin^k xi prefactor per table, and a row's parameter a REAL index x into them.  A sample
+       // blends the node words of tables a = floor(x) and a + 1 with the weight w = x - a and evaluates one cubic
+       // (tab_spline_family); with a prefactor k is blended likewise.  The older forms keep the code they always ran.
+       DIST_TABULATED_FAMILY = 14, DIST_TABULATED_FAMILY_PITCHY = 15 };
+constexpr bool tab_kind_family(int kind) { return kind == DIST_TABULATED_FAMILY || kind == DIST_TABULATED_FAMILY_PITCHY; }
 constexpr bool dist_is_tab(int kind)
 {
     return kind == DIST_TABULATED || kind == DIST_TABULATED_ISO || kind == DIST_TABULATED_2D || kind == DIST_TABULATED_PITCHY ||
         kind == DIST_TABULATED_GRID || kind == DIST_TABULATED_2D_GRID || kind == DIST_TABULATED_2D_PITCHY ||
-        kind == DIST_TABULATED_2D_GRID_PITCHY || kind == DIST_TABULATED_2D_NODES || kind == DIST_TABULATED_2D_NODES_PITCHY;
+        kind == DIST_TABULATED_2D_GRID_PITCHY || kind == DIST_TABULATED_2D_NODES || kind == DIST_TABULATED_2D_NODES_PITCHY ||
+        tab_kind_family(kind);
 }
 // the 2-D forms: on nodes uniform in ln gamma, on given gamma nodes (mu uniform), on given gamma and mu nodes, and which of
 // them carry a sin^k prefactor
@@ -170,9 +177,67 @@ RIM_DEV bool tab_row_ok(const double *hdr, double idx)
     return idx >= 0. && idx < hdr[TAB_HDR_NTABLES] && (double) (long long) idx == idx;
 }
 
+// A family (rim_tab_build_family): the header of an isotropic set, TAB_HDR_NTABLES = n_tables, then n_tables + 1 gamma rows
+// of [n_nodes][2] = {y_j, m_j} -- the last one a copy of the row before it, so that the row "one further on" of every table
+// exists and a sample never asks whether it does --, then, where the set has a sin^k xi prefactor, one header of TAB_PITCHY_PRE
+// + TAB_PITCH_HDR words per table as a sin^k set without g has them: {k, 0, two spare | three spare, P(k)}.
+// The index rule of a row: x finite with 0 <= x <= n_tables - 1 (-0.0 counts as 0), a = (long long) x, w = x - a; anything
+// else names no table.  `a` is 0 and w is 0 for such a row, so that every read stays inside the set.
+RIM_DEV bool tab_family_row(const double *hdr, double x, size_t &a, double &w)
+{
+    const bool ok = x >= 0. && x <= hdr[TAB_HDR_NTABLES] - 1.;
+    a = ok ? (size_t) (long long) x : 0;
+    w = ok ? x - (double) a : 0.;
+    return ok;
+}
+RIM_DEV const double *tab_family_k_headers(const double *hdr)
+{
+    return hdr + TAB_HDR_DOUBLES + ((size_t) hdr[TAB_HDR_NTABLES] + 1) * (size_t) hdr[TAB_HDR_NNODES] * 2;
+}
+// k of a row of a family with a prefactor: k_a + w (k_b - k_a), b = a + 1 or, at the last table, a
+RIM_DEV double tab_family_k(const double *hdr, size_t a, double w)
+{
+    const double *kh = tab_family_k_headers(hdr);
+    const size_t b = a + 1 < (size_t) hdr[TAB_HDR_NTABLES] ? a + 1 : a;
+    const double ka = kh[a * (TAB_PITCHY_PRE + TAB_PITCH_HDR)], kb = kh[b * (TAB_PITCHY_PRE + TAB_PITCH_HDR)];
+    return rim_fma(w, kb - ka, ka);
+}
+// The 64-byte line of a batch row of such a family, laid out as the header of a sin^k table without g, so that what reads
+// TAB_PITCHY_K and TAB_PITCH_P from a table's header reads them from here: {k, 0, w, spare | 0, 0, 0, P}.  par[0] of the
+// row names word TAB_PITCHY_PRE of it; w sits where a table's header has a spare word.
+enum { TAB_FAMILY_LINE = TAB_PITCHY_PRE + TAB_PITCH_HDR, TAB_FAMILY_W = -2 };
+RIM_DEV void tab_family_line(double *line, double k, double w, double pa)
+{
+    line[0] = k; line[1] = 0.; line[2] = w; line[3] = 0.;
+    line[4] = 0.; line[5] = 0.; line[6] = 0.; line[7] = pa;
+}
+
 template <int KIND>
 RIM_DEV void dist_prepare(DistParams &d, double norm)
 {
+    if (tab_kind_family(KIND)) {
+        // In: par[0] the real index x, par[1] the bit pattern of the set's address and, with a prefactor, par[2] that of the
+        // row's line (tab_family_line).  Out: what an isotropic row carries, par[1] the address of row a -- row b is the
+        // next one, (par[4] + 2) * 2 doubles further on -- and par[0] the weight w itself or, with a prefactor, the address
+        // of the line's pitch-row part, where w is word TAB_FAMILY_W.  DistParams does not grow.
+        const double *hdr = (const double *) (uintptr_t) rim_bits(d.par[1]);
+        size_t a;
+        double w;
+        const bool ok = tab_family_row(hdr, d.par[0], a, w);
+        const size_t nn = (size_t) hdr[TAB_HDR_NNODES];
+        if (KIND == DIST_TABULATED_FAMILY_PITCHY)
+            d.par[0] = rim_frombits((uint64_t) (uintptr_t) ((const double *) (uintptr_t) rim_bits(d.par[2]) + TAB_PITCHY_PRE));
+        else d.par[0] = w;
+        d.par[1] = rim_frombits((uint64_t) (uintptr_t) (hdr + TAB_HDR_DOUBLES + a * nn * 2));
+        d.par[2] = hdr[TAB_HDR_ULO];
+        d.par[3] = hdr[TAB_HDR_INVH];
+        d.par[4] = hdr[TAB_HDR_NNODES] - 2.;           // the index of the last interval
+        d.inv_gamma_cutoff = hdr[TAB_HDR_H];
+        d.inv_kappa_width = hdr[TAB_HDR_GLO];
+        d.neg_inverse_t = hdr[TAB_HDR_GHI];
+        d.norm = ok ? norm : RIM_NAN;
+        return;
+    }
     if (dist_is_tab(KIND)) {
         // In: par[0] the table index, par[1] the bit pattern of the table set's address.  The kind has one parameter, so the
         // fields the others use carry what a sample needs (DistParams does not grow): par[1] the bit pattern of the row's
@@ -319,8 +384,38 @@ RIM_DEV void tab_spline(const DistParams &d, double gamma, double &hval, double 
     dhdu = dhdt * d.par[3];
 }
 
+// tab_spline for a row of a family (d: dist_prepare<DIST_TABULATED_FAMILY> or <DIST_TABULATED_FAMILY_PITCHY>): the four node
+// words {y0, m0, y1, m1} of the interval from row a and from the row behind it, each blended with one rim_fma(w, q_b - q_a, q_a)
+// -- w = 0 gives q_a itself --, then ONE Hermite cubic: the interpolant is linear in its node words.  The index as in
+// tab_spline; every read stays inside the two rows.
+template <int KIND>
+RIM_DEV void tab_spline_family(const DistParams &d, double gamma, double &hval, double &dhdu)
+{
+    const double *row = (const double *) (uintptr_t) rim_bits(d.par[1]);
+    const double w = KIND == DIST_TABULATED_FAMILY_PITCHY ? ((const double *) (uintptr_t) rim_bits(d.par[0]))[TAB_FAMILY_W] : d.par[0];
+    const double x = (rim_log(gamma) - d.par[2]) * d.par[3];
+    double xc = x;
+    if (!(xc >= 0.)) xc = 0.;
+    if (xc > d.par[4]) xc = d.par[4];
+    const long long j = (long long) xc;
+    const double t = x - (double) j;
+    const double *qa = row + 2 * j;
+    const double *qb = qa + 2 * ((long long) d.par[4] + 2);
+    double q[4];
+    q[0] = rim_fma(w, qb[0] - qa[0], qa[0]);
+    q[1] = rim_fma(w, qb[1] - qa[1], qa[1]);
+    q[2] = rim_fma(w, qb[2] - qa[2], qa[2]);
+    q[3] = rim_fma(w, qb[3] - qa[3], qa[3]);
+    double dhdt;
+    tab_hermite(q, d.inv_gamma_cutoff, t, hval, dhdt);
+    dhdu = dhdt * d.par[3];
+}
+
 // does the row have a pitch-angle factor?  (wave-uniform; DIST_TABULATED_ISO: known not to at compile time)
 RIM_DEV bool tab_has_pitch(const DistParams &d) { return rim_bits(d.par[0]) != 0; }
+// the same where the normalisation asks (norm_kernel): par[0] of a family without a prefactor is a weight, not an address
+template <int KIND>
+RIM_DEV bool tab_norm_has_pitch(const DistParams &d) { return KIND == DIST_TABULATED_FAMILY ? false : tab_has_pitch(d); }
 template <int KIND>
 RIM_DEV bool tab_kind_has_pitch(const DistParams &d)
 {
@@ -328,7 +423,8 @@ RIM_DEV bool tab_kind_has_pitch(const DistParams &d)
     // row does)
     return KIND == DIST_TABULATED_2D || KIND == DIST_TABULATED_PITCHY || KIND == DIST_TABULATED_GRID ||
         KIND == DIST_TABULATED_2D_GRID || tab_kind_2d_pitchy(KIND) || KIND == DIST_TABULATED_2D_NODES ||
-        (KIND != DIST_TABULATED_ISO && tab_has_pitch(d));
+        KIND == DIST_TABULATED_FAMILY_PITCHY ||
+        (KIND != DIST_TABULATED_ISO && KIND != DIST_TABULATED_FAMILY && tab_has_pitch(d));
 }
 
 // The spline G(mu) = ln g of a pitch row (tab_has_pitch) and dG/dmu at mu = cos xi.  The interval index is formed from a
@@ -409,6 +505,7 @@ RIM_DEV double tab_norm_integrand(const DistParams &d, double g)
 {
     double hval, dhdu;
     if (KIND == DIST_TABULATED_GRID) tab_spline_grid(d, g, hval, dhdu);
+    else if (tab_kind_family(KIND)) tab_spline_family<KIND>(d, g, hval, dhdu);
     else tab_spline(d, g, hval, dhdu);
     return rim_exp(hval);
 }
@@ -697,9 +794,10 @@ RIM_DEV void tab_calc_f_both(const DistParams &d, double gamma, double cos_xi, d
     }
     double hval, dhdu;
     if (KIND == DIST_TABULATED_GRID) tab_spline_grid(d, gamma, hval, dhdu);
+    else if (tab_kind_family(KIND)) tab_spline_family<KIND>(d, gamma, hval, dhdu);
     else tab_spline(d, gamma, hval, dhdu);
     const double beta = rim_sqrt(1. - rim_div_moderate(1., gamma * gamma));
-    if (KIND == DIST_TABULATED_PITCHY || KIND == DIST_TABULATED_GRID) {
+    if (KIND == DIST_TABULATED_PITCHY || KIND == DIST_TABULATED_GRID || KIND == DIST_TABULATED_FAMILY_PITCHY) {
         // f = norm n(gamma) sin^k xi g(mu) / (gamma^2 beta), d f / d mu = f (G' - k mu / sin^2 xi): the factor and its term as
         // the pitchy kinds form them (pitchy_pl.rs:56-61), k a wave-uniform load; without a pitch row G = G' = 0
         const double *ph = (const double *) (uintptr_t) rim_bits(d.par[0]);

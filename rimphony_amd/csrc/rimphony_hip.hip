@@ -334,9 +334,9 @@ struct rimphony_ctx {
     unsigned long long hb_task;
     // what hipOccupancyMaxActiveBlocksPerMultiprocessor answered (-1: the query failed), asked once per context
     // (= per device) and instantiation: coop_kernel<P> by problem (0 Symphony, 1 Heyvaerts) and distribution kind,
-    int resident[2][14];            // (kind 4 ten times: the cell of a table set is its DIST_TABULATED* value, tab_kind below)
+    int resident[2][16];            // (kind 4 twelve times: the cell of a table set is its DIST_TABULATED* value, tab_kind below)
     int resident_f32[4];            // ... the Symphony kernels' fp32-integrand variants,
-    int resident_group[2][14];      // ... group_kernel<P> [Symphony groups / Faraday pair][kind] (kind 4: the cells of `resident`; no Faraday pair)
+    int resident_group[2][16];      // ... group_kernel<P> [Symphony groups / Faraday pair][kind] (kind 4: the cells of `resident`; no Faraday pair)
     // 0: this context has the GPU to itself (it holds the device's lock file); 1: another context or process had
     // the device first -- smaller persistent grids, no cooperative tail (see rimphony_ctx_create)
     int shared_mode;
@@ -355,6 +355,9 @@ struct rimphony_ctx {
     // the table set of the tabulated distribution (rimphony_ctx_set_tables; dev_symphony.h has the layout), or empty
     RimDevBuf<double> d_tab;
     int tab_kind = DIST_TABULATED_ISO;  // the form of that set as its DIST_TABULATED* value (tab_launch.h): which instantiation of the kind's kernels runs
+    // a family with a sin^k prefactor: one 64-byte line per row of the batch in flight (dev_symphony.h: tab_family_line),
+    // written by the normalisation's launch and read by every later kernel of the batch
+    RimDevBuf<double> d_famline;
 };
 
 // ---- last error (thread-local text; the codes are in rimphony_hip.h) ---------------------------
@@ -423,6 +426,7 @@ static void ctx_free(rimphony_ctx *c)
     c->d_gspill.release();
     c->d_gboard.release();
     c->d_tab.release();
+    c->d_famline.release();
     c->d_in.release();
     c->d_out.release();
     c->d_status.release();
@@ -661,7 +665,7 @@ static int install_tables(rimphony_ctx *c, const std::vector<double> &blob, int 
     return RIMPHONY_OK;
 }
 
-// The nine entries: check, build, install; n_tables = 0 clears through any of them.  A set of energy tables, each with a
+// The entries: check, build, install; n_tables = 0 clears through any of them.  A set of energy tables, each with a
 // pitch row (log_g) or none with one (log_g null and n_mu = 0: the isotropic form).
 extern "C" int rimphony_ctx_set_tables_pitch(rimphony_ctx *c, size_t n_tables, size_t n_nodes, double gamma_lo, double gamma_hi,
                                              const double *log_n, size_t n_mu, const double *log_g)
@@ -728,6 +732,22 @@ extern "C" int rimphony_ctx_set_tables_pitchy(rimphony_ctx *c, size_t n_tables, 
         catch (const std::bad_alloc &) { return RIMPHONY_ENOMEM; }
     }
     return install_tables(c, blob, DIST_TABULATED_PITCHY, log_g ? rim_tab_launch_pitchy_p : nullptr);
+}
+
+// A family of energy tables: a row of a batch names a real index x in [0, n_tables - 1] and its samples blend tables floor(x)
+// and floor(x) + 1 (rimphony_tab_family.hip; with sin_k rimphony_tab_family_pitchy.hip).  The plain forms' own checks and their
+// own spline solve, table by table; nothing is integrated at install: the normalisation is per row.
+extern "C" int rimphony_ctx_set_tables_family(rimphony_ctx *c, size_t n_tables, size_t n_nodes, double gamma_lo, double gamma_hi,
+                                              const double *log_n, const double *sin_k)
+{
+    if (!c) return RIMPHONY_EINVAL;
+    std::vector<double> blob;
+    if (n_tables) {
+        if (rim_tab_check_family(n_tables, n_nodes, gamma_lo, gamma_hi, log_n, sin_k)) return RIMPHONY_EINVAL;
+        try { rim_tab_build_family(n_tables, n_nodes, gamma_lo, gamma_hi, log_n, sin_k, blob); }
+        catch (const std::bad_alloc &) { return RIMPHONY_ENOMEM; }
+    }
+    return install_tables(c, blob, sin_k ? DIST_TABULATED_FAMILY_PITCHY : DIST_TABULATED_FAMILY);
 }
 
 // A set on gamma nodes of its own, always this form: the sin^k form's contents on the given nodes.  The host solves the
@@ -956,6 +976,17 @@ static int check_batch_args(int kind, std::initializer_list<const void *> head, 
     return RIMPHONY_OK;
 }
 
+// The lines of `n` rows of a family with a sin^k prefactor: room for them in the context, and their address in pp.p[2]
+// (load_params), where the normalisation's launch writes them.  Any other set: nothing.
+static int family_lines(rimphony_ctx *c, int kind, size_t n, ParamPtrs &pp)
+{
+    if (kind != RIMPHONY_TABULATED || c->tab_kind != DIST_TABULATED_FAMILY_PITCHY) return RIMPHONY_OK;
+    const int rc = c->d_famline.grow(n, n * TAB_FAMILY_LINE * sizeof(double), "the rows' lines of a table family");
+    if (rc) return rc;
+    pp.p[2] = c->d_famline.p;
+    return RIMPHONY_OK;
+}
+
 static int make_param_ptrs(const rimphony_ctx *c, int kind, const double *const *d_params, ParamPtrs &pp)
 {
     bool empty;
@@ -980,6 +1011,7 @@ extern "C" int rimphony_batch_norm_device(rimphony_ctx *c, int kind, size_t n, c
     if (rc) return rc;
     ParamPtrs pp;
     rc = make_param_ptrs(c, kind, d_params, pp);
+    if (!rc) rc = family_lines(c, kind, n, pp);
     if (rc) return rc;
     return launch_norm(c, kind, n, pp, d_norm, st);
 }
@@ -1173,10 +1205,14 @@ static const bool RIM_TAB_GROUP_DEFAULT[5] = {      // [tab_kind - DIST_TABULATE
     true,       // DIST_TABULATED_PITCHY        NOT MEASURED (profiles/tabulated_group_times.txt)
     true,       // DIST_TABULATED_GRID          NOT MEASURED (profiles/tabulated_grid_times.txt)
 };
+// (A family of energy tables has no line of its own either: it takes the line of the plain form its integer rows are -- the
+// isotropic form's, or with a prefactor the sin^k form's -- until profiles/tabulated_family_times.txt says otherwise.)
 static bool rim_tab_runs_group(const rimphony_ctx *c)
 {
     if (c->knobs.tab_group >= 0) return c->knobs.tab_group != 0;
-    const int form = c->tab_kind >= DIST_TABULATED_2D_GRID ? (int) DIST_TABULATED_2D : c->tab_kind;
+    const int form = c->tab_kind == DIST_TABULATED_FAMILY ? (int) DIST_TABULATED_ISO
+                   : c->tab_kind == DIST_TABULATED_FAMILY_PITCHY ? (int) DIST_TABULATED_PITCHY
+                   : c->tab_kind >= DIST_TABULATED_2D_GRID ? (int) DIST_TABULATED_2D : c->tab_kind;
     return RIM_TAB_GROUP_DEFAULT[form - DIST_TABULATED];
 }
 
@@ -1240,6 +1276,7 @@ static int batch_compute_locked(rimphony_ctx *c, int kind, size_t n, const doubl
     if (rc) return rc;
 
     rc = ensure_norm(c, n);
+    if (!rc) rc = family_lines(c, kind, n, pp);
     if (rc) return rc;
 
     // full_calculation()
@@ -1688,6 +1725,8 @@ static int single_point_norm(rimphony_ctx *c, int kind, const double *params, hi
     ParamPtrs pp;
     for (int k = 0; k < 5; k++) pp.p[k] = c->d_norm.p + 1 + k;
     if (kind == RIMPHONY_TABULATED) pp.p[1] = c->d_tab.p;
+    rc = family_lines(c, kind, 1, pp);
+    if (rc) return rc;
     return launch_norm(c, kind, 1, pp, c->d_norm.p, st);
 }
 
@@ -1703,6 +1742,9 @@ int RimPointSeam::begin(rimphony_ctx *c, int kind_, const double *params, int co
     if (rc) return rc;
     rc = single_point_norm(c, kind_, params, st);
     if (rc) return rc;
+    // (a family with a sin^k prefactor: the point's line, which the normalisation has just written -- dist_of reads par[2])
+    if (kind_ == RIMPHONY_TABULATED && c->tab_kind == DIST_TABULATED_FAMILY_PITCHY)
+        pa.par[2] = rim_frombits((uint64_t) (uintptr_t) c->d_famline.p);
     if (waves_per_cu) {
         grid = persistent_grid(c, count, waves_per_cu);
         rc = ensure_spill(c, grid);

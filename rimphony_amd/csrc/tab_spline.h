@@ -48,6 +48,10 @@
 // word of each table's header (TAB_2D_ENDS = ends_u + 2 ends_mu) that no kernel reads: the kernels see {S, S_u, S_mu, S_umu}
 // and never ask how they were solved.
 //
+// A set of energy tables on nodes uniform in ln gamma may be a FAMILY (rim_tab_check_family, rim_tab_build_family): a row of a
+// batch names a real index x and its samples blend the node words of tables floor(x) and floor(x) + 1.  The rows of an
+// isotropic set with the last one repeated, and the headers of a sin^k set without g where the family has a prefactor.
+//
 // Plain C++ with the elementary functions of detmath.h, so that the library (hipcc's host pass) and the tests' table
 // oracle (g++) produce the same bits from the same table.
 #ifndef RIM_TAB_SPLINE_H
@@ -728,6 +732,31 @@ inline void rim_tab_build_2d_nodes(size_t n_tables, size_t n_nodes, const double
             for (size_t i = 0; i < n_nodes; i++) nodes[(i * n_mu + j) * 4 + 3] = m[i];
         }
     }
+}
+
+// A FAMILY of energy tables on nodes uniform in ln gamma (dev_symphony.h: tab_family_*), with or without a sin^k xi prefactor
+// per table (sin_k null: without).  The checks are the plain forms' own: rim_tab_check, rim_tab_check_sin_k.
+inline int rim_tab_check_family(size_t n_tables, size_t n_nodes, double gamma_lo, double gamma_hi, const double *log_n,
+                                const double *sin_k)
+{
+    if (rim_tab_check(n_tables, n_nodes, gamma_lo, gamma_hi, log_n)) return -1;
+    return sin_k ? rim_tab_check_sin_k(n_tables, sin_k) : 0;
+}
+
+// The family as one block of doubles; rim_tab_check_family() has passed.  The rows are rim_tab_build()'s, table by table --
+// the spline solve is linear in the data, so a blend of two solved rows is the solved blend --, then the last row once more,
+// then the headers of a sin^k set without g (rim_tab_build_pitchy_table), P the closed form.
+inline void rim_tab_build_family(size_t n_tables, size_t n_nodes, double gamma_lo, double gamma_hi, const double *log_n,
+                                 const double *sin_k, std::vector<double> &blob)
+{
+    using namespace rim;
+    rim_tab_build(n_tables, n_nodes, gamma_lo, gamma_hi, log_n, blob);
+    const size_t row = n_nodes * 2, rows_end = blob.size();
+    blob.resize(rows_end + row + (sin_k ? n_tables * (size_t) TAB_FAMILY_LINE : 0), 0.);
+    for (size_t j = 0; j < row; j++) blob[rows_end + j] = blob[rows_end - row + j];
+    if (!sin_k) return;
+    for (size_t t = 0; t < n_tables; t++)
+        rim_tab_build_pitchy_table(blob.data() + rows_end + row, t, sin_k[t], 0, nullptr, 0., nullptr, nullptr);
 }
 
 #endif

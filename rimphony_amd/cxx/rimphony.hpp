@@ -94,6 +94,18 @@ public:
                                              log_g.empty() ? nullptr : log_g.data(), n_tables ? sin_k.data() : nullptr),
               "rimphony_ctx_set_tables_pitchy");
     }
+    // A FAMILY of energy tables (rimphony_ctx_set_tables_family): log_n [n_tables][n_nodes] as for set_tables, sin_k empty or
+    // [n_tables].  The one parameter of a RIMPHONY_TABULATED row is then a real index x in [0, n_tables - 1]; every sample
+    // blends tables floor(x) and floor(x) + 1 with the weight x - floor(x), and k likewise.
+    void set_tables_family(size_t n_tables, size_t n_nodes, double gamma_lo, double gamma_hi, const std::vector<double> &log_n,
+                           const std::vector<double> &sin_k = {}) const
+    {
+        if (log_n.size() != n_tables * n_nodes) throw std::runtime_error("set_tables_family: log_n must hold n_tables * n_nodes values");
+        if (!sin_k.empty() && sin_k.size() != n_tables) throw std::runtime_error("set_tables_family: sin_k must hold n_tables values");
+        check(rimphony_ctx_set_tables_family(ctx_, n_tables, n_nodes, gamma_lo, gamma_hi, n_tables ? log_n.data() : nullptr,
+                                             sin_k.empty() ? nullptr : sin_k.data()),
+              "rimphony_ctx_set_tables_family");
+    }
     // A set on gamma nodes of the caller's choosing (rimphony_ctx_set_tables_grid): gamma [n_nodes] strictly increasing from
     // >= 1, shared by the tables; log_n [n_tables][n_nodes]; log_g [n_tables][n_mu] and sin_k [n_tables] may be empty.
     void set_tables_grid(size_t n_tables, const std::vector<double> &gamma, const std::vector<double> &log_n, size_t n_mu = 0,
@@ -481,6 +493,64 @@ public:
 private:
     double glo_, ghi_;
     std::vector<double> log_n_, log_g_, sin_k_;
+};
+
+// A family of tabulated distributions with a continuous parameter (include/rimphony_hip.h: rimphony_ctx_set_tables_family):
+// log_n [n_tables][n_nodes] at nodes uniform in ln gamma, table i belonging to param[i] (strictly monotonic; empty: the index
+// itself), sin_k empty or one exponent per table.  The library blends ln n and k linearly in the index, and index() is
+// piecewise linear in param: exact where ln n is linear in param (a power law stored by p; a Juettner shape stored by 1 / T,
+// so space param in 1 / T to be exact there).  at(value) is the member at that value, used as TabulatedDistribution is.
+class TabulatedFamily {
+public:
+    class Member : public DistributionFunction {
+    protected:
+        int abi_kind() const override { return RIMPHONY_TABULATED; }
+        std::vector<double> abi_params() const override { return {x_}; }      // the real index
+    public:
+        Member(const TabulatedFamily &family, double x) : family_(family), x_(x) {}
+        double index() const { return x_; }
+        void install(const Context &ctx) const { family_.install(ctx); }
+        double calc_f(const Context &ctx, double gamma, double cos_xi) const
+        { install(ctx); return DistributionFunction::calc_f(ctx, gamma, cos_xi); }
+        std::array<double, 2> calc_f_derivatives(const Context &ctx, double gamma, double cos_xi) const
+        { install(ctx); return DistributionFunction::calc_f_derivatives(ctx, gamma, cos_xi); }
+        FullSynchrotronCalculator full_calculation(std::shared_ptr<Context> ctx) const
+        {
+            install(*ctx);
+            return FullSynchrotronCalculator(std::move(ctx), RIMPHONY_TABULATED, {x_});
+        }
+    private:
+        const TabulatedFamily &family_;
+        double x_;
+    };
+    TabulatedFamily(double gamma_lo, double gamma_hi, size_t n_tables, std::vector<double> log_n, std::vector<double> sin_k = {},
+                    std::vector<double> param = {})
+        : glo_(gamma_lo), ghi_(gamma_hi), n_tables_(n_tables), log_n_(std::move(log_n)), sin_k_(std::move(sin_k)), param_(std::move(param))
+    {
+        if (n_tables_ == 0 || log_n_.size() % n_tables_ != 0) throw std::runtime_error("TabulatedFamily: log_n must hold n_tables rows");
+        if (param_.empty()) for (size_t i = 0; i < n_tables_; i++) param_.push_back((double) i);
+        if (param_.size() != n_tables_) throw std::runtime_error("TabulatedFamily: param must hold n_tables values");
+        for (size_t i = 1; i + 1 < n_tables_; i++)
+            if (!((param_[i] - param_[i - 1]) * (param_[i + 1] - param_[i]) > 0.)) throw std::runtime_error("TabulatedFamily: param must be strictly monotonic");
+        if (n_tables_ == 2 && !(param_[0] != param_[1])) throw std::runtime_error("TabulatedFamily: param must be strictly monotonic");
+    }
+    void install(const Context &ctx) const { ctx.set_tables_family(n_tables_, log_n_.size() / n_tables_, glo_, ghi_, log_n_, sin_k_); }
+    // the real index of a value: piecewise linear in param; throws outside it
+    double index(double value) const
+    {
+        if (n_tables_ == 1) { if (value == param_[0]) return 0.; throw std::runtime_error("TabulatedFamily: value outside param"); }
+        const bool up = param_[0] < param_[1];
+        for (size_t i = 0; i + 1 < n_tables_; i++) {
+            const double a = param_[i], b = param_[i + 1];
+            if (up ? (value >= a && value <= b) : (value <= a && value >= b)) return (double) i + (value - a) / (b - a);
+        }
+        throw std::runtime_error("TabulatedFamily: value outside param");
+    }
+    Member at(double value) const { return Member(*this, index(value)); }
+private:
+    double glo_, ghi_;
+    size_t n_tables_;
+    std::vector<double> log_n_, sin_k_, param_;
 };
 
 // A distribution given as a surface: log_n [n_nodes][n_mu], mu fastest, = ln n(gamma, mu) at nodes uniform in ln gamma and
