@@ -443,10 +443,56 @@ int rimphony_ctx_set_tables_2d_device_ends(rimphony_ctx *ctx, size_t n_tables, s
  * between them (and with sin_k the pitchy power law at every (p, k)) to the accuracy of the plain form.  Elsewhere the error
  * is that of linear interpolation of ln n between neighbouring tables.
  * RIMPHONY_TAB_GROUP chooses between the group kernel and one wave per coefficient as for the other forms (the same bits).
- * Not offered: families of the forms with g, on given nodes or in 2-D (their normalisations are fixed at install); families
+ * Not offered: families of the forms with g or on given gamma nodes (2-D surfaces: rimphony_ctx_set_tables_2d_family); families
  * in two parameters; higher-order blending across tables; a crank-out subcommand; a bench leg. */
 int rimphony_ctx_set_tables_family(rimphony_ctx *ctx, size_t n_tables, size_t n_nodes, double gamma_lo, double gamma_hi,
                                    const double *log_n, const double *sin_k);
+
+/* Tabulated distributions as a FAMILY OF 2-D SURFACES with a continuous index per row: a set of surfaces ln n(gamma, mu) on
+ * gamma nodes and mu nodes of the caller's choosing, optionally with a sin^k xi exponent per table, where the one parameter
+ * of a RIMPHONY_TABULATED row is a REAL index x and every sample blends two neighbouring surfaces -- a PIC or Fokker-Planck
+ * run whose anisotropy changes with energy, stored at 64 times and evaluated between them.
+ *   gamma, mu, log_n [n_tables][n_nodes][n_mu], sin_k (NULL, or HOST [n_tables])
+ *           exactly what rimphony_ctx_set_tables_2d_nodes accepts, with its limits: 8 .. 65536 gamma nodes, 8 .. 1024 mu
+ *           nodes from exactly -1 to exactly +1, n_nodes * n_mu <= 2^20 per table, k in [0, 100].  Nodes uniform in ln gamma
+ *           or in mu are a special case: pass them;
+ *   ends_gamma, ends_mu
+ *           RIMPHONY_TAB_ENDS_NATURAL or RIMPHONY_TAB_ENDS_NOT_A_KNOT per axis, as for rimphony_ctx_set_tables_2d_ends.
+ * Checked with the plain form's own check (RIMPHONY_EINVAL, the previous set stays); n_tables = 0 clears the set; the call
+ * replaces a set of any form and a set of any form replaces it; rimphony_debug_tables reads the set back: the set of
+ * rimphony_ctx_set_tables_2d_nodes word for word, but for the normalisation word of every table header, which is a NaN (no
+ * trailing copy of the last table).
+ * The index rule of a row is that of rimphony_ctx_set_tables_family:
+ *   valid   x finite and 0 <= x <= n_tables - 1; -0.0 counts as 0;
+ *   tables  a = (long long) x the lower one, b = a + 1 the upper one -- except at a == n_tables - 1, where b = a;
+ *   weight  w = x - a;
+ *   blend   the gamma interval and the mu interval of a sample are found once; the sixteen node words {S, S_u, S_mu, S_umu}
+ *           of the cell's four corners are read from table a and from table b, each pair blended with one
+ *           fma(w, q_b - q_a, q_a), then ONE bicubic; k = fma(w, k_b - k_a, k_a).  The bicubic is linear in its node words
+ *           and the spline solve is linear in the data, for either kind of ends: this is the spline of the blended data;
+ *   f       = norm sin^k xi e^S / (gamma^2 beta) inside the table, 0 outside, with the derivatives of the plain form -- the
+ *           NaN at |mu| = 1 with a prefactor included;
+ *   else    a NaN, or an index out of range, is a NaN normalisation: every selected slot of the row is NaN with
+ *           RIMPHONY_ST_NORM_FAIL.
+ * The normalisation is per row and nothing is integrated at install: norm = 1 / (4 pi int nbar dgamma) over [gamma_0,
+ * gamma_last] with nbar(gamma) = 1/2 int (1 - mu^2)^(k/2) e^S dmu over the blended surface at the blended k, the quadrature
+ * the plain form runs once per table as the set comes in (31 Kronrod points on every mu cell, the end cells of a set with a
+ * prefactor under their substitution).  Its cost is linear in n_mu: 56, 512 and 2080 ms for 4096 rows on 8, 64 and 256 mu
+ * nodes of a 128-node family on an MI355X (50, 466, 1903 ms with a prefactor), where the two persistent kernels of such a
+ * batch take 473 ms (941 ms); per sample the blend costs +14 % (Symphony, group kernel) and +44 % (Faraday) on the plain
+ * nodes form, +36 % and +51 % with a prefactor (profiles/tabulated_2d_family_times.txt).  Keep the mu nodes few.
+ * A row at an integer x carries the BITS of the same table installed through rimphony_ctx_set_tables_2d_ends on the same
+ * nodes with the same sin_k and ends: values, status words, work counters, the normalisation and calc_f -- with one caveat:
+ * fma(0, d, -0.0) is +0.0, so a node word that is -0.0 enters the bicubic as +0.0 (the sign of a zero node word is not kept).
+ * The existing entries keep refusing a non-integer index.
+ * The blend is linear in the index, exact where ln n is linear in the parameter the tables are spaced in, and elsewhere has
+ * the error of linear interpolation of ln n between neighbouring tables (profiles/tabulated_2d_family_accuracy.txt).
+ * RIMPHONY_TAB_GROUP chooses between the group kernel and one wave per coefficient as for the other forms (the same bits).
+ * Not offered: families of the uniform-grid 2-D forms as forms of their own (pass the nodes); families of the 1-D forms with
+ * g or on given gamma nodes; install from device memory; families in two parameters; higher-order blending across tables;
+ * one normalisation shared by rows with equal x. */
+int rimphony_ctx_set_tables_2d_family(rimphony_ctx *ctx, size_t n_tables, size_t n_nodes, const double *gamma, size_t n_mu,
+                                      const double *mu, const double *log_n, const double *sin_k, int ends_gamma, int ends_mu);
 
 /* Diagnostics: the installed table set as the kernels read it, copied to `out` (HOST, `cap` doubles).  *n_doubles is the
  * size of the set in doubles, 0 (and nothing copied) where the context has none; RIMPHONY_EINVAL, with *n_doubles still set,

@@ -129,6 +129,18 @@ extern "C" {
         log_n: *const c_double,
         sin_k: *const c_double,
     ) -> c_int;
+    pub fn rimphony_ctx_set_tables_2d_family(
+        ctx: *mut rimphony_ctx,
+        n_tables: usize,
+        n_nodes: usize,
+        gamma: *const c_double,
+        n_mu: usize,
+        mu: *const c_double,
+        log_n: *const c_double,
+        sin_k: *const c_double,
+        ends_gamma: c_int,
+        ends_mu: c_int,
+    ) -> c_int;
     pub fn rimphony_ctx_set_tables_grid(
         ctx: *mut rimphony_ctx,
         n_tables: usize,
@@ -416,6 +428,27 @@ impl HipContext {
             rimphony_ctx_set_tables_family(
                 self.raw, log_n.len() / n_nodes, n_nodes, gamma_lo, gamma_hi, log_n.as_ptr(),
                 if sin_k.is_empty() { std::ptr::null() } else { sin_k.as_ptr() },
+            )
+        };
+        if rc != RIMPHONY_OK {
+            return Err(error_text(rc));
+        }
+        Ok(())
+    }
+
+    /// A family of 2-D surfaces on gamma and mu nodes of the caller's choosing (include/rimphony_hip.h:
+    /// rimphony_ctx_set_tables_2d_family): `log_n` holds n_tables surfaces of gamma.len() * mu.len() values, mu fastest; the
+    /// parameter of a row is then a real index into the tables, whose node words every sample blends.  `sin_k` empty, or one
+    /// exponent in [0, 100] per table; `ends_gamma`, `ends_mu`: 0 natural, 1 not-a-knot.
+    pub fn set_tables_2d_family(&self, gamma: &[f64], mu: &[f64], log_n: &[f64], sin_k: &[f64], ends_gamma: c_int, ends_mu: c_int) -> Result<(), String> {
+        let per = gamma.len() * mu.len();
+        if per == 0 || log_n.len() % per != 0 || (!sin_k.is_empty() && sin_k.len() != log_n.len() / per) {
+            return Err(error_text(RIMPHONY_EINVAL));
+        }
+        let rc = unsafe {
+            rimphony_ctx_set_tables_2d_family(
+                self.raw, log_n.len() / per, gamma.len(), gamma.as_ptr(), mu.len(), mu.as_ptr(), log_n.as_ptr(),
+                if sin_k.is_empty() { std::ptr::null() } else { sin_k.as_ptr() }, ends_gamma, ends_mu,
             )
         };
         if rc != RIMPHONY_OK {

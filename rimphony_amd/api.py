@@ -16,6 +16,7 @@ behaviour; see src/lib.rs of pkgw/rimphony):
                                                     of ln n(gamma), spline-interpolated inside the integrand
   TabulatedFamily(gamma_lo, gamma_hi, log_n, ...)   a set of such tables with a continuous parameter: .at(value) is the member
                                                     between two stored tables, blended inside the integrand
+  TabulatedFamily2D(gamma, mu, log_n, ...)          the same for surfaces ln n(gamma, mu) on given gamma and mu nodes
 
 plus the batched compute() the north star adds: `compute_batch`.  PyTorch is
 used only as plumbing (device buffers, the current HIP stream).  Everything is
@@ -466,6 +467,29 @@ class Context:
                                                              m.ctypes.data_as(dp), t.ctypes.data_as(dp),
                                                              None if k is None else k.ctypes.data_as(dp)),
                    "rimphony_ctx_set_tables_2d_nodes")
+
+    def set_tables_2d_family(self, gamma, mu, log_n, sin_k=None, ends=None):
+        """The context's table set as a FAMILY of surfaces: gamma, mu and log_n [n_tables][n_nodes][n_mu] as for
+        set_tables_2d_nodes, and the one parameter of a TABULATED row a real index x in [0, n_tables - 1].  Every sample finds
+        its cell once, blends the cell's sixteen node words from tables floor(x) and floor(x) + 1 with the weight x - floor(x)
+        and evaluates one bicubic; sin_k (a scalar, or one value per table, each in [0, 100]) gives each table a sin^k xi
+        prefactor whose exponent is blended likewise; ends as for set_tables_2d.  The normalisation is per row, integrated over
+        the blended surface with every batch -- its cost grows with the number of mu nodes
+        (profiles/tabulated_2d_family_times.txt).  A row at an integer x carries the bits of that table installed through
+        set_tables_2d_nodes; an x outside the range is a NaN row.  Replaces the previous set of any form; log_n None clears it.
+        Synchronous; host arrays only (include/rimphony_hip.h: rimphony_ctx_set_tables_2d_family)."""
+        ends = check_ends(ends) or (TAB_ENDS_NATURAL, TAB_ENDS_NATURAL)
+        if log_n is None:
+            capi.check(self.lib.rimphony_ctx_set_tables_2d_family(self.handle, 0, 0, None, 0, None, None, None, 0, 0),
+                       "rimphony_ctx_set_tables_2d_family")
+            return
+        g, m, t = check_tables_2d_nodes(gamma, mu, log_n)
+        k = None if sin_k is None else check_sin_k(sin_k, t.shape[0])
+        dp = ctypes.POINTER(ctypes.c_double)
+        capi.check(self.lib.rimphony_ctx_set_tables_2d_family(self.handle, t.shape[0], t.shape[1], g.ctypes.data_as(dp), t.shape[2],
+                                                              m.ctypes.data_as(dp), t.ctypes.data_as(dp),
+                                                              None if k is None else k.ctypes.data_as(dp), ends[0], ends[1]),
+                   "rimphony_ctx_set_tables_2d_family")
 
     def _set_tables_2d_ends(self, gamma, gamma_lo, gamma_hi, mu, t, sin_k, ends):
         """set_tables_2d, set_tables_2d_grid and set_tables_2d_nodes for a numpy log_n with a choice of ends: gamma, mu and
@@ -1194,12 +1218,17 @@ class TabulatedFamily:
         self.log_n = check_tables(self.gamma_lo, self.gamma_hi, log_n)
         n = self.log_n.shape[0]
         self.sin_k = None if sin_k is None else check_sin_k(sin_k, n)
-        self.param = np.arange(n, dtype=np.float64) if param is None else np.ascontiguousarray(param, dtype=np.float64)
-        if self.param.shape != (n,):
-            raise ValueError("param: expected one value per table (%d), got shape %r" % (n, self.param.shape))
-        d = np.diff(self.param)
-        if not np.isfinite(self.param).all() or not ((d > 0).all() or (d < 0).all()):
+        self.param = self._check_param(param, n)
+
+    @staticmethod
+    def _check_param(param, n):
+        param = np.arange(n, dtype=np.float64) if param is None else np.ascontiguousarray(param, dtype=np.float64)
+        if param.shape != (n,):
+            raise ValueError("param: expected one value per table (%d), got shape %r" % (n, param.shape))
+        d = np.diff(param)
+        if not np.isfinite(param).all() or not ((d > 0).all() or (d < 0).all()):
             raise ValueError("param: expected finite, strictly monotonic values")
+        return param
 
     @classmethod
     def from_function(cls, fn, gamma_lo, gamma_hi, param, n_nodes=4096, sin_k=None):
@@ -1231,6 +1260,35 @@ class TabulatedFamily:
     def at(self, value):
         """The member of the family at `value`: full_calculation, calc_f and calc_f_derivatives, as TabulatedDistribution."""
         return _FamilyMember(self, float(self.index(float(value))))
+
+
+class TabulatedFamily2D(TabulatedFamily):
+    """A family of tabulated SURFACES with a continuous parameter: log_n [n_tables][n_nodes][n_mu] = ln n(gamma_i, mu_j) on the
+    gamma nodes and mu nodes of TabulatedDistribution2DNodes, table i belonging to param[i]; sin_k optionally one sin^k xi
+    exponent per table; ends as for Context.set_tables_2d (Context.set_tables_2d_family).  Everything else is
+    TabulatedFamily's: the blend is linear in the index, index() piecewise linear in param, at(value) the one-point object."""
+
+    def __init__(self, gamma, mu, log_n, sin_k=None, param=None, ends=None):
+        self.gamma, self.mu, self.log_n = check_tables_2d_nodes(gamma, mu, log_n)
+        n = self.log_n.shape[0]
+        self.sin_k = None if sin_k is None else check_sin_k(sin_k, n)
+        self.ends = check_ends(ends)
+        self.param = self._check_param(param, n)
+
+    @classmethod
+    def from_function(cls, fn, gamma, mu, param, sin_k=None, ends=None):
+        """Tabulate n(gamma, mu; a) = fn(gamma, mu, a) (vectorised over gamma [n_nodes][1] and mu [1][n_mu], positive) for
+        every a of param at the given nodes; sin_k and ends as in the constructor."""
+        g = check_gamma_nodes(gamma)
+        m = check_mu_nodes(mu)
+        param = np.atleast_1d(np.asarray(param, dtype=np.float64))
+        log_n = np.stack([np.log(np.broadcast_to(np.asarray(fn(g[:, None], m[None, :], float(a)), dtype=np.float64), (len(g), len(m))))
+                          for a in param])
+        return cls(g, m, log_n, sin_k, param, ends)
+
+    def _install(self, ctx):
+        ctx.set_tables_2d_family(self.gamma, self.mu, self.log_n, self.sin_k, self.ends)
+        return ctx
 
 
 class _FamilyMember(_DistributionFunction):

@@ -44,6 +44,11 @@ __device__ inline double hyperg_2F1_at_1(double a, double b, double c)
     return rim_exp(lc + lcab - lca - lcb);
 }
 
+// nbar(gamma) of a row of a family of 2-D surfaces (dev_symphony.h: tab_2d_norm_integrand on the row's line).  Defined by the
+// units of those forms, next to the Kronrod tables it reads (tab_2d_family_unit.h); no other instantiation of norm_kernel names it.
+template <int KIND>
+__device__ double tab_2d_family_nbar(const DistParams &d, double g);
+
 template <int KIND>
 __global__ __launch_bounds__(64) void norm_kernel(ParamPtrs pp, size_t n, double *norm, unsigned long long *queue,
                                                     double *spill_base)
@@ -63,11 +68,13 @@ __global__ __launch_bounds__(64) void norm_kernel(ParamPtrs pp, size_t n, double
         DistParams d;
         load_params<KIND>(pp, i, d);
         // (the tabulated kind: dist_prepare replaces the table index in par[0], so the index is judged first)
-        constexpr bool TAB = KIND == DIST_TABULATED || KIND == DIST_TABULATED_PITCHY || KIND == DIST_TABULATED_GRID || tab_kind_family(KIND);
+        constexpr bool TAB = KIND == DIST_TABULATED || KIND == DIST_TABULATED_PITCHY || KIND == DIST_TABULATED_GRID || tab_kind_family(KIND) ||
+            tab_kind_2d_family(KIND);
         // (a family judges a real index: x in [0, n_tables - 1])
         size_t fam_a;
         double fam_w;
-        const bool tab_ok = !TAB || (tab_kind_family(KIND) ? tab_family_row(pp.p[1], d.par[0], fam_a, fam_w) : tab_row_ok(pp.p[1], d.par[0]));
+        const bool tab_ok = !TAB || (tab_kind_family(KIND) || tab_kind_2d_family(KIND) ? tab_family_row(pp.p[1], d.par[0], fam_a, fam_w)
+                                                                                       : tab_row_ok(pp.p[1], d.par[0]));
         dist_prepare<KIND>(d, RIM_NAN);
 
         double lo, hi, epsrel, pa = 1.;
@@ -86,7 +93,9 @@ __global__ __launch_bounds__(64) void norm_kernel(ParamPtrs pp, size_t n, double
         } else { lo = 0.; hi = rim_sqrt(60. * d.par[0] + 4.); epsrel = 1e-10; }
 
         // (the tabulated kind's integrand, n(gamma) of its table, is dev_symphony.h's: the tests' table oracle shares it)
+        // (a family of 2-D surfaces: nbar of the row's blended surface, the quadrature the plain 2-D forms run per table at install)
         auto f = [&](double x, bool active) -> double {
+            if constexpr (tab_kind_2d_family(KIND)) return active ? tab_2d_family_nbar<KIND>(d, x) : 0.;
             if (TAB) return active ? tab_norm_integrand<KIND>(d, x) : 0.;
             return active ? norm_integrand<KIND>(d, x) : 0.;
         };

@@ -47,14 +47,20 @@ enum { DIST_POWER_LAW = 0, DIST_THERMAL_JUETTNER = 1, DIST_PITCHY_PL = 2, DIST_P
        // ln gamma, without and with a sin^k xi prefactor per table, and a row's parameter a REAL index x into them.  A sample
        // blends the node words of tables a = floor(x) and a + 1 with the weight w = x - a and evaluates one cubic
        // (tab_spline_family); with a prefactor k is blended likewise.  The older forms keep the code they always ran.
-       DIST_TABULATED_FAMILY = 14, DIST_TABULATED_FAMILY_PITCHY = 15 };
+       DIST_TABULATED_FAMILY = 14, DIST_TABULATED_FAMILY_PITCHY = 15,
+       // nor these two: a FAMILY of 2-D surfaces on given gamma and mu nodes (rim_tab_build_2d_family), without and with a
+       // sin^k xi prefactor per table.  The set and the lookup of DIST_TABULATED_2D_NODES; a row's parameter is a real index x
+       // as in the families above, and a sample blends the sixteen node words of its cell from tables a = floor(x) and a + 1
+       // and evaluates one bicubic (tab_bicubic_family).  The older forms keep the code they always ran.
+       DIST_TABULATED_2D_FAMILY = 16, DIST_TABULATED_2D_FAMILY_PITCHY = 17 };
 constexpr bool tab_kind_family(int kind) { return kind == DIST_TABULATED_FAMILY || kind == DIST_TABULATED_FAMILY_PITCHY; }
+constexpr bool tab_kind_2d_family(int kind) { return kind == DIST_TABULATED_2D_FAMILY || kind == DIST_TABULATED_2D_FAMILY_PITCHY; }
 constexpr bool dist_is_tab(int kind)
 {
     return kind == DIST_TABULATED || kind == DIST_TABULATED_ISO || kind == DIST_TABULATED_2D || kind == DIST_TABULATED_PITCHY ||
         kind == DIST_TABULATED_GRID || kind == DIST_TABULATED_2D_GRID || kind == DIST_TABULATED_2D_PITCHY ||
         kind == DIST_TABULATED_2D_GRID_PITCHY || kind == DIST_TABULATED_2D_NODES || kind == DIST_TABULATED_2D_NODES_PITCHY ||
-        tab_kind_family(kind);
+        tab_kind_family(kind) || tab_kind_2d_family(kind);
 }
 // the 2-D forms: on nodes uniform in ln gamma, on given gamma nodes (mu uniform), on given gamma and mu nodes, and which of
 // them carry a sin^k prefactor
@@ -63,7 +69,8 @@ constexpr bool tab_kind_2d_on_grid(int kind) { return kind == DIST_TABULATED_2D_
 constexpr bool tab_kind_2d_nodes(int kind) { return kind == DIST_TABULATED_2D_NODES || kind == DIST_TABULATED_2D_NODES_PITCHY; }
 constexpr bool tab_kind_2d_pitchy(int kind)
 {
-    return kind == DIST_TABULATED_2D_PITCHY || kind == DIST_TABULATED_2D_GRID_PITCHY || kind == DIST_TABULATED_2D_NODES_PITCHY;
+    return kind == DIST_TABULATED_2D_PITCHY || kind == DIST_TABULATED_2D_GRID_PITCHY || kind == DIST_TABULATED_2D_NODES_PITCHY ||
+        kind == DIST_TABULATED_2D_FAMILY_PITCHY;
 }
 enum { STOKES_I = 0, STOKES_Q = 1, STOKES_V = 2 };
 enum { COEFF_EMISSION = 0, COEFF_ABSORPTION = 1, COEFF_FARADAY = 2 };
@@ -212,9 +219,62 @@ RIM_DEV void tab_family_line(double *line, double k, double w, double pa)
     line[4] = 0.; line[5] = 0.; line[6] = 0.; line[7] = pa;
 }
 
+// A family of 2-D surfaces (rim_tab_build_2d_family): the set of rim_tab_build_2d_nodes word for word -- header, table headers,
+// both guides, both node arrays, [n_tables][n_nodes][n_mu][4] node data, no trailing copy -- with TAB_2D_NORM of every table
+// header a NaN: nothing is integrated at install.  The index rule of a row is tab_family_row's.  Every batch row has a
+// 64-byte line, laid out as a table header, so that what reads a table's header reads the line:
+//   TAB_2D_LAST, TAB_2D_INVH, TAB_2D_H   the mu geometry of the set (the same in every table header);
+//   TAB_2D_NORM                          the weight w (a row's normalisation travels in d.norm);
+//   TAB_2D_K                             k_a + w (k_b - k_a), b = a + 1 or, at the last table, a (0 without a prefactor);
+//   TAB_2D_MU_GUIDE, TAB_2D_MU_NODES     the distance in doubles from THE LINE to the set's mu guide and mu nodes;
+//   TAB_2D_ENDS                          the distance in doubles from the node data of table a to those of table b: one
+//                                        table's worth, or 0 at the last table.
+// par[0] of a prepared row names the line.  A row whose index names no table gets a = 0, w = 0: every read stays inside the set.
+RIM_DEV double tab_family_blend(double w, double qa, double qb) { return rim_fma(w, qb - qa, qa); }
+RIM_DEV void tab_2d_family_line(double *line, const double *hdr, size_t a, double w)
+{
+    const size_t nt = (size_t) hdr[TAB_HDR_NTABLES], nn = (size_t) hdr[TAB_HDR_NNODES], nmu = (size_t) -hdr[TAB_HDR_NMU];
+    const size_t b = a + 1 < nt ? a + 1 : a;
+    const double *tha = hdr + TAB_HDR_DOUBLES + a * TAB_2D_HDR, *thb = hdr + TAB_HDR_DOUBLES + b * TAB_2D_HDR;
+    const long long to_set = ((long long) (uintptr_t) tha - (long long) (uintptr_t) line) / (long long) sizeof(double);
+    line[TAB_2D_LAST] = tha[TAB_2D_LAST];
+    line[TAB_2D_INVH] = tha[TAB_2D_INVH];
+    line[TAB_2D_H] = tha[TAB_2D_H];
+    line[TAB_2D_NORM] = w;
+    line[TAB_2D_K] = tab_family_blend(w, tha[TAB_2D_K], thb[TAB_2D_K]);
+    line[TAB_2D_MU_GUIDE] = (double) (to_set + (long long) tha[TAB_2D_MU_GUIDE]);
+    line[TAB_2D_MU_NODES] = (double) (to_set + (long long) tha[TAB_2D_MU_NODES]);
+    line[TAB_2D_ENDS] = (double) ((b - a) * nn * nmu * 4);
+}
+
 template <int KIND>
 RIM_DEV void dist_prepare(DistParams &d, double norm)
 {
+    if (tab_kind_2d_family(KIND)) {
+        // In: par[0] the real index x, par[1] the bit pattern of the set's address, par[2] that of the row's line
+        // (tab_2d_family_line).  Out: what a row of a 2-D set on given nodes carries, with the line where the table's header
+        // is: par[0] the line, par[1] the node data of table a -- those of table b lie line[TAB_2D_ENDS] doubles further on --,
+        // par[2] the set's u nodes, par[3] 1 / (cell width), par[4] the index of the last guide cell, inv_gamma_cutoff the
+        // guide's address.  DistParams does not grow.
+        const double *hdr = (const double *) (uintptr_t) rim_bits(d.par[1]);
+        size_t a;
+        double w;
+        const bool ok = tab_family_row(hdr, d.par[0], a, w);
+        const size_t nt = (size_t) hdr[TAB_HDR_NTABLES], nn = (size_t) hdr[TAB_HDR_NNODES], cells = (size_t) hdr[TAB_HDR_H];
+        const size_t nmu = (size_t) -hdr[TAB_HDR_NMU];
+        const double *guide = hdr + tab_2d_grid_guide_at(nt);
+        const size_t at = tab_2d_nodes_nodes_at(nt, nn, cells, nmu, (size_t) hdr[TAB_HDR_DOUBLES + TAB_2D_H]);
+        d.par[0] = d.par[2];
+        d.par[1] = rim_frombits((uint64_t) (uintptr_t) (hdr + at + a * nn * nmu * 4));
+        d.par[2] = rim_frombits((uint64_t) (uintptr_t) (guide + tab_grid_guide_doubles(cells)));
+        d.par[3] = hdr[TAB_HDR_INVH];
+        d.par[4] = hdr[TAB_HDR_H] - 1.;
+        d.inv_gamma_cutoff = rim_frombits((uint64_t) (uintptr_t) guide);
+        d.inv_kappa_width = hdr[TAB_HDR_GLO];
+        d.neg_inverse_t = hdr[TAB_HDR_GHI];
+        d.norm = ok ? norm : RIM_NAN;
+        return;
+    }
     if (tab_kind_family(KIND)) {
         // In: par[0] the real index x, par[1] the bit pattern of the set's address and, with a prefactor, par[2] that of the
         // row's line (tab_family_line).  Out: what an isotropic row carries, par[1] the address of row a -- row b is the
@@ -415,7 +475,11 @@ RIM_DEV void tab_spline_family(const DistParams &d, double gamma, double &hval, 
 RIM_DEV bool tab_has_pitch(const DistParams &d) { return rim_bits(d.par[0]) != 0; }
 // the same where the normalisation asks (norm_kernel): par[0] of a family without a prefactor is a weight, not an address
 template <int KIND>
-RIM_DEV bool tab_norm_has_pitch(const DistParams &d) { return KIND == DIST_TABULATED_FAMILY ? false : tab_has_pitch(d); }
+RIM_DEV bool tab_norm_has_pitch(const DistParams &d)
+{
+    // (nor is that of a family of 2-D surfaces a pitch row: it names the row's line, and the factor is under the integral)
+    return KIND == DIST_TABULATED_FAMILY || tab_kind_2d_family(KIND) ? false : tab_has_pitch(d);
+}
 template <int KIND>
 RIM_DEV bool tab_kind_has_pitch(const DistParams &d)
 {
@@ -423,7 +487,7 @@ RIM_DEV bool tab_kind_has_pitch(const DistParams &d)
     // row does)
     return KIND == DIST_TABULATED_2D || KIND == DIST_TABULATED_PITCHY || KIND == DIST_TABULATED_GRID ||
         KIND == DIST_TABULATED_2D_GRID || tab_kind_2d_pitchy(KIND) || KIND == DIST_TABULATED_2D_NODES ||
-        KIND == DIST_TABULATED_FAMILY_PITCHY ||
+        KIND == DIST_TABULATED_FAMILY_PITCHY || KIND == DIST_TABULATED_2D_FAMILY ||
         (KIND != DIST_TABULATED_ISO && KIND != DIST_TABULATED_FAMILY && tab_has_pitch(d));
 }
 
@@ -656,6 +720,49 @@ RIM_DEV void tab_bicubic_nodes(const DistParams &d, double gamma, double mu, dou
     dsdmu = dsdtm * minvh;
 }
 
+// tab_bicubic_nodes for a row of a family of 2-D surfaces (d: dist_prepare<DIST_TABULATED_2D_FAMILY> or <.._PITCHY>): the cell is
+// found once, as tab_bicubic_nodes finds it; then, Hermite step by Hermite step along mu, the four node words of the step are
+// read from table a and from table b, each pair blended with one rim_fma(w, q_b - q_a, q_a) -- w = 0 gives q_a itself, but for
+// the sign of a zero --, and the step evaluated: eight words in flight, not thirty-two.  The bicubic is linear in its node
+// words and the spline solve is linear in the data, so this is the spline of the blended data.  w and the distance to table b
+// are two wave-uniform words of the row's line.  Every read stays inside the set.
+RIM_DEV void tab_bicubic_family(const DistParams &d, double gamma, double mu, double &sval, double &dsdu, double &dsdmu)
+{
+    const double *th = (const double *) (uintptr_t) rim_bits(d.par[0]);
+    const double *nodes = (const double *) (uintptr_t) rim_bits(d.par[1]);
+    const double *un = (const double *) (uintptr_t) rim_bits(d.par[2]);
+    const double *mn = th + (long long) th[TAB_2D_MU_NODES];
+    const double w = th[TAB_2D_NORM];
+    const long long to_b = (long long) th[TAB_2D_ENDS];
+    const double u = rim_log(gamma);
+    const long long i = tab_2d_grid_interval(d, u);
+    const double *q = un + 2 * i;
+    const double uinvh = q[1], uh = q[2] - q[0];
+    const double tu = (u - q[0]) * uinvh;
+    const long long j = tab_2d_nodes_mu_interval(th, mn, mu);
+    const double *r = mn + 2 * j;
+    const double minvh = r[1], mh = r[2] - r[0];
+    const double tm = (mu - r[0]) * minvh;
+    const long long nmu = (long long) th[TAB_2D_LAST] + 2;
+    const double *a = nodes + (i * nmu + j) * 4;        // nodes (i, j), (i, j + 1) of table a
+    const double *b = a + nmu * 4;                      // nodes (i + 1, j), (i + 1, j + 1) of table a
+    const double *a2 = a + to_b, *b2 = b + to_b;        // the same of table b
+    double va, dva, wa, dwa, vb, dvb, wb, dwb;
+    tab_hermite4(tab_family_blend(w, a[0], a2[0]), tab_family_blend(w, a[2], a2[2]), tab_family_blend(w, a[4], a2[4]),
+                 tab_family_blend(w, a[6], a2[6]), mh, tm, va, dva);
+    tab_hermite4(tab_family_blend(w, a[1], a2[1]), tab_family_blend(w, a[3], a2[3]), tab_family_blend(w, a[5], a2[5]),
+                 tab_family_blend(w, a[7], a2[7]), mh, tm, wa, dwa);
+    tab_hermite4(tab_family_blend(w, b[0], b2[0]), tab_family_blend(w, b[2], b2[2]), tab_family_blend(w, b[4], b2[4]),
+                 tab_family_blend(w, b[6], b2[6]), mh, tm, vb, dvb);
+    tab_hermite4(tab_family_blend(w, b[1], b2[1]), tab_family_blend(w, b[3], b2[3]), tab_family_blend(w, b[5], b2[5]),
+                 tab_family_blend(w, b[7], b2[7]), mh, tm, wb, dwb);
+    double dsdtu, dsdtm, unused;
+    tab_hermite4(va, wa, vb, wb, uh, tu, sval, dsdtu);
+    tab_hermite4(dva, dwa, dvb, dwb, uh, tu, dsdtm, unused);
+    dsdu = dsdtu * uinvh;
+    dsdmu = dsdtm * minvh;
+}
+
 // nbar(gamma) = 1/2 int exp(S(ln gamma, mu)) dmu of a 2-D table: the integrand of its normalisation.  The 31-point Kronrod
 // rule (xgk, wgk: gk31_table.h) on every mu cell, summed in node order -- the rule P of a pitch row uses.  KIND: the form
 // of the set, one of the six 2-D forms.
@@ -668,6 +775,8 @@ RIM_DEV void tab_bicubic_nodes(const DistParams &d, double gamma, double mu, dou
 //
 // On given mu nodes every cell has its own centre and half width, from its two node words, and h of the substitution is the
 // end cell's own width: a graded set may make that cell 1e-5 wide, and the singular derivative is inside it all the same.
+//
+// A family of 2-D surfaces takes the same path on its row's line: the blended surface, the blended k.
 template <int KIND = DIST_TABULATED_2D>
 RIM_DEV double tab_2d_norm_integrand(const DistParams &d, double g, const double *xgk, const double *wgk)
 {
@@ -675,7 +784,7 @@ RIM_DEV double tab_2d_norm_integrand(const DistParams &d, double g, const double
     const long long cells = (long long) th[TAB_2D_LAST] + 1;
     const double h = th[TAB_2D_H];
     double sum = 0.;
-    if (tab_kind_2d_nodes(KIND)) {
+    if (tab_kind_2d_nodes(KIND) || tab_kind_2d_family(KIND)) {
         const double *mn = th + (long long) th[TAB_2D_MU_NODES];
         const double sk = tab_kind_2d_pitchy(KIND) ? th[TAB_2D_K] : 0.;
         for (long long j = 0; j < cells; j++) {
@@ -700,7 +809,8 @@ RIM_DEV double tab_2d_norm_integrand(const DistParams &d, double g, const double
                     mu = centre + half * xgk[k];
                     if (tab_kind_2d_pitchy(KIND)) sin2 = 1. - mu * mu;
                 }
-                tab_bicubic_nodes(d, g, mu, sval, dsdu, dsdmu);
+                if (tab_kind_2d_family(KIND)) tab_bicubic_family(d, g, mu, sval, dsdu, dsdmu);
+                else tab_bicubic_nodes(d, g, mu, sval, dsdu, dsdmu);
                 if (tab_kind_2d_pitchy(KIND)) acc += wgk[k] * (jac * (RimMath<0>::pow(rim_sqrt(sin2), sk) * rim_exp(sval)));
                 else acc += wgk[k] * rim_exp(sval);
             }
@@ -762,10 +872,12 @@ RIM_DEV void tab_calc_f_both(const DistParams &d, double gamma, double cos_xi, d
 {
     f = 0.; dfdg = 0.; dfdcx = 0.;
     if (gamma < d.inv_kappa_width || gamma > d.neg_inverse_t) return;
-    if (KIND == DIST_TABULATED_2D || KIND == DIST_TABULATED_2D_GRID || KIND == DIST_TABULATED_2D_NODES) {
+    if (KIND == DIST_TABULATED_2D || KIND == DIST_TABULATED_2D_GRID || KIND == DIST_TABULATED_2D_NODES ||
+        KIND == DIST_TABULATED_2D_FAMILY) {
         // f = norm exp(S(ln gamma, mu)) / (gamma^2 beta), d f / d mu = f S_mu: one exponential per sample
         double sval, dsdu, dsdmu;
-        if (KIND == DIST_TABULATED_2D_NODES) tab_bicubic_nodes(d, gamma, cos_xi, sval, dsdu, dsdmu);
+        if (KIND == DIST_TABULATED_2D_FAMILY) tab_bicubic_family(d, gamma, cos_xi, sval, dsdu, dsdmu);
+        else if (KIND == DIST_TABULATED_2D_NODES) tab_bicubic_nodes(d, gamma, cos_xi, sval, dsdu, dsdmu);
         else if (KIND == DIST_TABULATED_2D_GRID) tab_bicubic_grid(d, gamma, cos_xi, sval, dsdu, dsdmu);
         else tab_bicubic(d, gamma, cos_xi, sval, dsdu, dsdmu);
         const double beta2 = rim_sqrt(1. - rim_div_moderate(1., gamma * gamma));
@@ -777,11 +889,13 @@ RIM_DEV void tab_calc_f_both(const DistParams &d, double gamma, double cos_xi, d
     if (tab_kind_2d_pitchy(KIND)) {
         // f = norm sin^k xi exp(S) / (gamma^2 beta), d f / d mu = f (S_mu - k mu / sin^2 xi): the factor and its term as the
         // pitchy kinds and DIST_TABULATED_PITCHY form them, k a wave-uniform load from the table's header.  A mu a rounding
-        // beyond +-1 is a NaN here (the square root), where the plain 2-D forms extrapolate the end cell.
+        // beyond +-1 is a NaN here (the square root), where the plain 2-D forms extrapolate the end cell.  (A family: the
+        // blended k of the row's line.)
         const double *th = (const double *) (uintptr_t) rim_bits(d.par[0]);
         const double k = th[TAB_2D_K];
         double sval, dsdu, dsdmu;
-        if (tab_kind_2d_nodes(KIND)) tab_bicubic_nodes(d, gamma, cos_xi, sval, dsdu, dsdmu);
+        if (tab_kind_2d_family(KIND)) tab_bicubic_family(d, gamma, cos_xi, sval, dsdu, dsdmu);
+        else if (tab_kind_2d_nodes(KIND)) tab_bicubic_nodes(d, gamma, cos_xi, sval, dsdu, dsdmu);
         else if (tab_kind_2d_on_grid(KIND)) tab_bicubic_grid(d, gamma, cos_xi, sval, dsdu, dsdmu);
         else tab_bicubic(d, gamma, cos_xi, sval, dsdu, dsdmu);
         const double sin_xi = rim_sqrt(1. - cos_xi * cos_xi);

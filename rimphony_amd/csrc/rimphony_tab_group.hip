@@ -10,7 +10,8 @@
 // set on given nodes, is rimphony_tab_2d_grid_group.hip's; those of the 2-D forms with a sin^k prefactor are
 // rimphony_tab_2d_pitchy_group.hip's and rimphony_tab_2d_grid_pitchy_group.hip's, those of the 2-D form on given gamma and mu
 // nodes rimphony_tab_2d_nodes_group.hip's and rimphony_tab_2d_nodes_pitchy_group.hip's, those of the families of energy tables
-// rimphony_tab_family_group.hip's and rimphony_tab_family_pitchy_group.hip's.  They live with the
+// rimphony_tab_family_group.hip's and rimphony_tab_family_pitchy_group.hip's, those of the families of 2-D surfaces
+// rimphony_tab_2d_family_group.hip's and rimphony_tab_2d_family_pitchy_group.hip's.  They live with the
 // budget of rimphony_group.hip's: RIM_GROUP_WAVES waves per SIMD and the same LDS block.  The kind has no Faraday group
 // (RIMPHONY_FARADAY_GROUP is measured slower for the analytic kinds: DESIGN.md section 5).
 #include "group_kernel.h"
@@ -28,6 +29,8 @@ const void *rim_tab_group_kernel(int tab_kind)
         else if constexpr (KIND == DIST_TABULATED_2D_NODES_PITCHY) return rim_tab_2d_nodes_pitchy_group_kernel();
         else if constexpr (KIND == DIST_TABULATED_FAMILY) return rim_tab_family_group_kernel();
         else if constexpr (KIND == DIST_TABULATED_FAMILY_PITCHY) return rim_tab_family_pitchy_group_kernel();
+        else if constexpr (KIND == DIST_TABULATED_2D_FAMILY) return rim_tab_2d_family_group_kernel();
+        else if constexpr (KIND == DIST_TABULATED_2D_FAMILY_PITCHY) return rim_tab_2d_family_pitchy_group_kernel();
         else return reinterpret_cast<const void *>(group_kernel<SymGroupProblem<KIND>>);
     });
 }

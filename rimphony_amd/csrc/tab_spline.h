@@ -52,6 +52,10 @@
 // batch names a real index x and its samples blend the node words of tables floor(x) and floor(x) + 1.  The rows of an
 // isotropic set with the last one repeated, and the headers of a sin^k set without g where the family has a prefactor.
 //
+// A 2-D set on given gamma and mu nodes may be a family too (rim_tab_check_2d_family, rim_tab_build_2d_family): the set of
+// rim_tab_build_2d_nodes with every table's normalisation word a NaN -- a row's samples blend the node words of two tables and
+// its normalisation is integrated per row.
+//
 // Plain C++ with the elementary functions of detmath.h, so that the library (hipcc's host pass) and the tests' table
 // oracle (g++) produce the same bits from the same table.
 #ifndef RIM_TAB_SPLINE_H
@@ -757,6 +761,26 @@ inline void rim_tab_build_family(size_t n_tables, size_t n_nodes, double gamma_l
     if (!sin_k) return;
     for (size_t t = 0; t < n_tables; t++)
         rim_tab_build_pitchy_table(blob.data() + rows_end + row, t, sin_k[t], 0, nullptr, 0., nullptr, nullptr);
+}
+
+// A FAMILY of 2-D surfaces on given gamma and mu nodes (dev_symphony.h: tab_2d_family_line, tab_bicubic_family), with or
+// without a sin^k xi prefactor per table (sin_k null: without).  The check is the plain form's own.
+inline int rim_tab_check_2d_family(size_t n_tables, size_t n_nodes, const double *gamma, size_t n_mu, const double *mu,
+                                   const double *log_n, const double *sin_k)
+{
+    return rim_tab_check_2d_nodes(n_tables, n_nodes, gamma, n_mu, mu, log_n, sin_k);
+}
+
+// The family as one block of doubles; rim_tab_check_2d_family() has passed.  The set of rim_tab_build_2d_nodes word for word
+// -- the tensor-product solve is linear in the data for either kind of ends, so a blend of two solved tables is the solved
+// blend; no trailing copy: a row at the last table blends it with itself --, but for TAB_2D_NORM of every table header, which
+// is a NaN and stays one: the normalisation is per row.  TAB_2D_ENDS records the ends as ever.
+inline void rim_tab_build_2d_family(size_t n_tables, size_t n_nodes, const double *gamma, size_t n_mu, const double *mu,
+                                    const double *log_n, const double *sin_k, std::vector<double> &blob, int ends_u = 0, int ends_mu = 0)
+{
+    using namespace rim;
+    rim_tab_build_2d_nodes(n_tables, n_nodes, gamma, n_mu, mu, log_n, sin_k, blob, ends_u, ends_mu);
+    for (size_t t = 0; t < n_tables; t++) blob[(size_t) TAB_HDR_DOUBLES + t * TAB_2D_HDR + TAB_2D_NORM] = RIM_NAN;
 }
 
 #endif

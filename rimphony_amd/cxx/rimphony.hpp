@@ -177,6 +177,23 @@ public:
                                                sin_k.empty() ? nullptr : sin_k.data()),
               "rimphony_ctx_set_tables_2d_nodes");
     }
+    // A FAMILY of 2-D surfaces (rimphony_ctx_set_tables_2d_family): gamma, mu, log_n [n_tables][n_nodes][n_mu] and sin_k as for
+    // set_tables_2d_nodes, the ends as for set_tables_2d_ends.  The one parameter of a RIMPHONY_TABULATED row is then a real
+    // index x in [0, n_tables - 1]; every sample blends the node words of tables floor(x) and floor(x) + 1 with the weight
+    // x - floor(x), and k likewise; the normalisation is integrated per row.
+    void set_tables_2d_family(size_t n_tables, const std::vector<double> &gamma, const std::vector<double> &mu,
+                              const std::vector<double> &log_n, const std::vector<double> &sin_k = {},
+                              int ends_gamma = RIMPHONY_TAB_ENDS_NATURAL, int ends_mu = RIMPHONY_TAB_ENDS_NATURAL) const
+    {
+        if (log_n.size() != n_tables * gamma.size() * mu.size())
+            throw std::runtime_error("set_tables_2d_family: log_n must hold n_tables * n_nodes * n_mu values");
+        if (!sin_k.empty() && sin_k.size() != n_tables)
+            throw std::runtime_error("set_tables_2d_family: sin_k must be empty or hold n_tables values");
+        check(rimphony_ctx_set_tables_2d_family(ctx_, n_tables, gamma.size(), n_tables ? gamma.data() : nullptr, mu.size(),
+                                                n_tables ? mu.data() : nullptr, n_tables ? log_n.data() : nullptr,
+                                                sin_k.empty() ? nullptr : sin_k.data(), ends_gamma, ends_mu),
+              "rimphony_ctx_set_tables_2d_family");
+    }
     // Any 2-D form from ln n in device memory (rimphony_ctx_set_tables_2d_device): d_log_n [n_tables][n_nodes][n_mu] on this
     // context's GPU, produced on `stream`.  gamma empty: n_nodes nodes uniform in ln gamma from gamma_lo to gamma_hi, else
     // gamma holds the nodes and the two are not read; mu empty: n_mu nodes uniform in mu, else mu holds them (mu without
@@ -551,6 +568,67 @@ private:
     double glo_, ghi_;
     size_t n_tables_;
     std::vector<double> log_n_, sin_k_, param_;
+};
+
+// A family of tabulated SURFACES with a continuous parameter (include/rimphony_hip.h: rimphony_ctx_set_tables_2d_family): log_n
+// [n_tables][n_nodes][n_mu], mu fastest, on the gamma and mu nodes of set_tables_2d_nodes, table i belonging to param[i]
+// (strictly monotonic; empty: the index itself), sin_k empty or one exponent per table, the ends of the spline per axis.
+// index() and at() as TabulatedFamily has them.
+class TabulatedFamily2D {
+public:
+    class Member : public DistributionFunction {
+    protected:
+        int abi_kind() const override { return RIMPHONY_TABULATED; }
+        std::vector<double> abi_params() const override { return {x_}; }      // the real index
+    public:
+        Member(const TabulatedFamily2D &family, double x) : family_(family), x_(x) {}
+        double index() const { return x_; }
+        void install(const Context &ctx) const { family_.install(ctx); }
+        double calc_f(const Context &ctx, double gamma, double cos_xi) const
+        { install(ctx); return DistributionFunction::calc_f(ctx, gamma, cos_xi); }
+        std::array<double, 2> calc_f_derivatives(const Context &ctx, double gamma, double cos_xi) const
+        { install(ctx); return DistributionFunction::calc_f_derivatives(ctx, gamma, cos_xi); }
+        FullSynchrotronCalculator full_calculation(std::shared_ptr<Context> ctx) const
+        {
+            install(*ctx);
+            return FullSynchrotronCalculator(std::move(ctx), RIMPHONY_TABULATED, {x_});
+        }
+    private:
+        const TabulatedFamily2D &family_;
+        double x_;
+    };
+    TabulatedFamily2D(std::vector<double> gamma, std::vector<double> mu, size_t n_tables, std::vector<double> log_n,
+                      std::vector<double> sin_k = {}, std::vector<double> param = {}, int ends_gamma = RIMPHONY_TAB_ENDS_NATURAL,
+                      int ends_mu = RIMPHONY_TAB_ENDS_NATURAL)
+        : gamma_(std::move(gamma)), mu_(std::move(mu)), n_tables_(n_tables), log_n_(std::move(log_n)), sin_k_(std::move(sin_k)),
+          param_(std::move(param)), ends_gamma_(ends_gamma), ends_mu_(ends_mu)
+    {
+        if (n_tables_ == 0 || log_n_.size() != n_tables_ * gamma_.size() * mu_.size())
+            throw std::runtime_error("TabulatedFamily2D: log_n must hold n_tables * n_nodes * n_mu values");
+        if (param_.empty()) for (size_t i = 0; i < n_tables_; i++) param_.push_back((double) i);
+        if (param_.size() != n_tables_) throw std::runtime_error("TabulatedFamily2D: param must hold n_tables values");
+        for (size_t i = 1; i + 1 < n_tables_; i++)
+            if (!((param_[i] - param_[i - 1]) * (param_[i + 1] - param_[i]) > 0.)) throw std::runtime_error("TabulatedFamily2D: param must be strictly monotonic");
+        if (n_tables_ == 2 && !(param_[0] != param_[1])) throw std::runtime_error("TabulatedFamily2D: param must be strictly monotonic");
+    }
+    void install(const Context &ctx) const { ctx.set_tables_2d_family(n_tables_, gamma_, mu_, log_n_, sin_k_, ends_gamma_, ends_mu_); }
+    // the real index of a value: piecewise linear in param; throws outside it
+    double index(double value) const
+    {
+        if (n_tables_ == 1) { if (value == param_[0]) return 0.; throw std::runtime_error("TabulatedFamily2D: value outside param"); }
+        const bool up = param_[0] < param_[1];
+        for (size_t i = 0; i + 1 < n_tables_; i++) {
+            const double a = param_[i], b = param_[i + 1];
+            if (up ? (value >= a && value <= b) : (value <= a && value >= b)) return (double) i + (value - a) / (b - a);
+        }
+        throw std::runtime_error("TabulatedFamily2D: value outside param");
+    }
+    Member at(double value) const { return Member(*this, index(value)); }
+private:
+    std::vector<double> gamma_, mu_;
+    size_t n_tables_;
+    std::vector<double> log_n_, sin_k_, param_;
+    int ends_gamma_, ends_mu_;
 };
 
 // A distribution given as a surface: log_n [n_nodes][n_mu], mu fastest, = ln n(gamma, mu) at nodes uniform in ln gamma and
