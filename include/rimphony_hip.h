@@ -444,7 +444,8 @@ int rimphony_ctx_set_tables_2d_device_ends(rimphony_ctx *ctx, size_t n_tables, s
  * is that of linear interpolation of ln n between neighbouring tables.
  * RIMPHONY_TAB_GROUP chooses between the group kernel and one wave per coefficient as for the other forms (the same bits).
  * Not offered: families of the forms with g or on given gamma nodes (2-D surfaces: rimphony_ctx_set_tables_2d_family); families
- * in two parameters; higher-order blending across tables; a crank-out subcommand; a bench leg. */
+ * in two parameters; higher-order blending across the tables of this form, which stays linear (2-D surfaces:
+ * rimphony_ctx_set_tables_2d_family_cubic); a crank-out subcommand; a bench leg. */
 int rimphony_ctx_set_tables_family(rimphony_ctx *ctx, size_t n_tables, size_t n_nodes, double gamma_lo, double gamma_hi,
                                    const double *log_n, const double *sin_k);
 
@@ -489,10 +490,51 @@ int rimphony_ctx_set_tables_family(rimphony_ctx *ctx, size_t n_tables, size_t n_
  * the error of linear interpolation of ln n between neighbouring tables (profiles/tabulated_2d_family_accuracy.txt).
  * RIMPHONY_TAB_GROUP chooses between the group kernel and one wave per coefficient as for the other forms (the same bits).
  * Not offered: families of the uniform-grid 2-D forms as forms of their own (pass the nodes); families of the 1-D forms with
- * g or on given gamma nodes; install from device memory; families in two parameters; higher-order blending across tables;
- * one normalisation shared by rows with equal x. */
+ * g or on given gamma nodes; install from device memory; families in two parameters; a blend of higher order than cubic
+ * (cubic: rimphony_ctx_set_tables_2d_family_cubic); one normalisation shared by rows with equal x. */
 int rimphony_ctx_set_tables_2d_family(rimphony_ctx *ctx, size_t n_tables, size_t n_nodes, const double *gamma, size_t n_mu,
                                       const double *mu, const double *log_n, const double *sin_k, int ends_gamma, int ends_mu);
+
+/* The family of 2-D surfaces of rimphony_ctx_set_tables_2d_family blended CUBICALLY across its tables: a 4-point Lagrange cubic
+ * in the parameter the tables are spaced in, chosen at install, per set.  For a simulation stored at a handful of snapshots,
+ * where the linear blend's error -- a quarter per doubling of the tables -- cannot be bought down with more tables.
+ *   n_tables .. ends_mu
+ *           exactly what rimphony_ctx_set_tables_2d_family accepts, with n_tables >= 4;
+ *   param   NULL, or HOST [n_tables]: the knots c_t the tables are spaced in (a temperature, 1 / T, a time), finite and strictly
+ *           monotonic, increasing or decreasing.  NULL: c_t = t.
+ * Checked as the linear entry checks (RIMPHONY_EINVAL, the previous set stays) -- fewer than four tables and knots that are
+ * not finite or not monotonic included; n_tables = 0 clears the set; the call replaces a set of any form and a set of any form
+ * replaces it; rimphony_debug_tables reads the set back: the set of rimphony_ctx_set_tables_2d_family word for word, followed
+ * by the n_tables knot words.  No new solve and no extra memory per table: the bicubic is linear in its node words and the
+ * spline solve is linear in the data, so a fixed combination of solved tables is the solved combination.
+ * The parameter of a row stays the real index x, with the rule of the linear entry: valid where x is finite and
+ * 0 <= x <= n_tables - 1, a = (long long) x, w = x - a, b = a + 1 (b = a at the last table).  Then, per row:
+ *   p       = fma(w, c_b - c_a, c_a): at an integer x a knot, bit for bit;
+ *   stencil the tables s .. s + 3 with s = min(max(a - 1, 0), n_tables - 4);
+ *   weights L_i = prod over j != i, j ascending, starting from 1, of (p - c_{s+j}) / (c_{s+i} - c_{s+j}): at a knot exactly 1
+ *           for that table and a zero for the others;
+ *   k       with sin_k, fma(L_3, k_3, fma(L_2, k_2, fma(L_1, k_1, L_0 k_0))) over the stencil.  A cubic may overshoot: a row
+ *           whose blended k is not in [0, 100] is a NaN row with RIMPHONY_ST_NORM_FAIL.  Space sin_k smoothly;
+ *   blend   the gamma interval and the mu interval of a sample are found once; each of the cell's sixteen node words is
+ *           fma(L_3, q_3, fma(L_2, q_2, fma(L_1, q_1, L_0 q_0))) of the stencil's four tables, then ONE bicubic;
+ *   f, the NaN rows and the per-row normalisation: as for the linear entry, over the blended surface at the blended k.
+ * A row at an integer x carries the BITS of that table installed through rimphony_ctx_set_tables_2d_ends with the same nodes,
+ * sin_k and ends -- values, status words, work counters, the normalisation and calc_f --, with the linear entry's caveat: the
+ * sign of a zero node word is not kept.
+ * Accuracy and cost (profiles/tabulated_2d_family_cubic_accuracy.txt, profiles/tabulated_2d_family_cubic_times.txt): exact,
+ * to the accuracy of the plain form, where ln n is a cubic polynomial in the knots; elsewhere the error of 4-point
+ * interpolation, fourth order in the spacing: on a Juettner shape whose anisotropy depends on T, spaced in 1 / T, 1.4e-3 on 4
+ * tables and 1.1e-4 on 8 where the linear blend has 1.1e-2 and 2.6e-3 -- four tables blended cubically beat eight blended
+ * linearly.  A sample reads four runs of node words instead of two: measured on an MI355X against the linear blend of the same
+ * four 1 MiB tables at the same x, +21 % per Symphony sample (group kernel) and +40 % per Faraday sample; with a prefactor 2.3 x
+ * on both (its kernels spill 300 B more per lane); the per-row normalisation of 4096 rows 81 against 56 ms on 8 mu nodes and 741
+ * against 515 ms on 64 (84 / 50 and 777 / 470 ms with a prefactor).
+ * RIMPHONY_TAB_GROUP chooses between the group kernel and one wave per coefficient as for the other forms (the same bits).
+ * Not offered: cubic blending for the families of energy tables (rimphony_ctx_set_tables_family stays linear); what the linear
+ * entry does not offer. */
+int rimphony_ctx_set_tables_2d_family_cubic(rimphony_ctx *ctx, size_t n_tables, size_t n_nodes, const double *gamma, size_t n_mu,
+                                            const double *mu, const double *log_n, const double *sin_k, int ends_gamma, int ends_mu,
+                                            const double *param);
 
 /* Diagnostics: the installed table set as the kernels read it, copied to `out` (HOST, `cap` doubles).  *n_doubles is the
  * size of the set in doubles, 0 (and nothing copied) where the context has none; RIMPHONY_EINVAL, with *n_doubles still set,

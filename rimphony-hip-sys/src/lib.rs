@@ -141,6 +141,19 @@ extern "C" {
         ends_gamma: c_int,
         ends_mu: c_int,
     ) -> c_int;
+    pub fn rimphony_ctx_set_tables_2d_family_cubic(
+        ctx: *mut rimphony_ctx,
+        n_tables: usize,
+        n_nodes: usize,
+        gamma: *const c_double,
+        n_mu: usize,
+        mu: *const c_double,
+        log_n: *const c_double,
+        sin_k: *const c_double,
+        ends_gamma: c_int,
+        ends_mu: c_int,
+        param: *const c_double,
+    ) -> c_int;
     pub fn rimphony_ctx_set_tables_grid(
         ctx: *mut rimphony_ctx,
         n_tables: usize,
@@ -449,6 +462,26 @@ impl HipContext {
             rimphony_ctx_set_tables_2d_family(
                 self.raw, log_n.len() / per, gamma.len(), gamma.as_ptr(), mu.len(), mu.as_ptr(), log_n.as_ptr(),
                 if sin_k.is_empty() { std::ptr::null() } else { sin_k.as_ptr() }, ends_gamma, ends_mu,
+            )
+        };
+        if rc != RIMPHONY_OK {
+            return Err(error_text(rc));
+        }
+        Ok(())
+    }
+
+    /// The same family blended cubically across its tables (include/rimphony_hip.h: rimphony_ctx_set_tables_2d_family_cubic):
+    /// at least four tables; `param` empty (the knots are the indices), or one finite knot per table, strictly monotonic.
+    pub fn set_tables_2d_family_cubic(&self, gamma: &[f64], mu: &[f64], log_n: &[f64], sin_k: &[f64], ends_gamma: c_int, ends_mu: c_int, param: &[f64]) -> Result<(), String> {
+        let per = gamma.len() * mu.len();
+        if per == 0 || log_n.len() % per != 0 || (!sin_k.is_empty() && sin_k.len() != log_n.len() / per) || (!param.is_empty() && param.len() != log_n.len() / per) {
+            return Err(error_text(RIMPHONY_EINVAL));
+        }
+        let rc = unsafe {
+            rimphony_ctx_set_tables_2d_family_cubic(
+                self.raw, log_n.len() / per, gamma.len(), gamma.as_ptr(), mu.len(), mu.as_ptr(), log_n.as_ptr(),
+                if sin_k.is_empty() { std::ptr::null() } else { sin_k.as_ptr() }, ends_gamma, ends_mu,
+                if param.is_empty() { std::ptr::null() } else { param.as_ptr() },
             )
         };
         if rc != RIMPHONY_OK {

@@ -84,6 +84,10 @@ def build_hip(force=False, verbose=False):
                                     os.path.join(CSRC, "rimphony_tab_2d_family.hip"), os.path.join(CSRC, "rimphony_tab_2d_family_group.hip"),
                                     os.path.join(CSRC, "rimphony_tab_2d_family_pitchy.hip"),
                                     os.path.join(CSRC, "rimphony_tab_2d_family_pitchy_group.hip"),
+                                    os.path.join(CSRC, "rimphony_tab_2d_family_cubic.hip"),
+                                    os.path.join(CSRC, "rimphony_tab_2d_family_cubic_group.hip"),
+                                    os.path.join(CSRC, "rimphony_tab_2d_family_cubic_pitchy.hip"),
+                                    os.path.join(CSRC, "rimphony_tab_2d_family_cubic_pitchy_group.hip"),
                                     os.path.join(CSRC, "rimphony_tab_install.hip"),
                                     "-ldl", "-o", LIB]
     if verbose:
@@ -182,6 +186,12 @@ def build_tab2d_family_oracle():
     """The same for families of 2-D surfaces on given gamma and mu nodes, a real index per row
     (tests/support/tab2d_family_oracle.cpp)."""
     return _build_dist_oracle("tab2d_family_oracle.cpp", "liboracle_tab2dfamily.so")
+
+
+def build_tab2d_family_cubic_oracle():
+    """The same for families of 2-D surfaces blended cubically across their tables
+    (tests/support/tab2d_family_cubic_oracle.cpp)."""
+    return _build_dist_oracle("tab2d_family_cubic_oracle.cpp", "liboracle_tab2dfamilycubic.so")
 
 
 def build_pitchy_beam_oracle():

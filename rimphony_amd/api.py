@@ -468,7 +468,7 @@ class Context:
                                                              None if k is None else k.ctypes.data_as(dp)),
                    "rimphony_ctx_set_tables_2d_nodes")
 
-    def set_tables_2d_family(self, gamma, mu, log_n, sin_k=None, ends=None):
+    def set_tables_2d_family(self, gamma, mu, log_n, sin_k=None, ends=None, blend="linear", param=None):
         """The context's table set as a FAMILY of surfaces: gamma, mu and log_n [n_tables][n_nodes][n_mu] as for
         set_tables_2d_nodes, and the one parameter of a TABULATED row a real index x in [0, n_tables - 1].  Every sample finds
         its cell once, blends the cell's sixteen node words from tables floor(x) and floor(x) + 1 with the weight x - floor(x)
@@ -477,8 +477,36 @@ class Context:
         the blended surface with every batch -- its cost grows with the number of mu nodes
         (profiles/tabulated_2d_family_times.txt).  A row at an integer x carries the bits of that table installed through
         set_tables_2d_nodes; an x outside the range is a NaN row.  Replaces the previous set of any form; log_n None clears it.
-        Synchronous; host arrays only (include/rimphony_hip.h: rimphony_ctx_set_tables_2d_family)."""
+        Synchronous; host arrays only (include/rimphony_hip.h: rimphony_ctx_set_tables_2d_family).
+
+        blend="cubic" blends FOUR neighbouring tables with a 4-point Lagrange cubic in `param` -- one finite knot per table,
+        strictly monotonic; None: the index itself --, and k likewise (rimphony_ctx_set_tables_2d_family_cubic).  At least four
+        tables.  A row whose blended k overshoots [0, 100] is a NaN row: space sin_k smoothly.  Fourth order in the spacing
+        of the tables where the linear blend is second order, for four runs of node words per sample instead of two
+        (profiles/tabulated_2d_family_cubic_accuracy.txt, profiles/tabulated_2d_family_cubic_times.txt).  The linear blend
+        has no knots: a param with blend="linear" is a ValueError."""
+        if blend not in ("linear", "cubic"):
+            raise ValueError("blend: expected 'linear' or 'cubic', got %r" % (blend,))
+        if blend == "linear" and param is not None:
+            raise ValueError("param: the linear blend has no knots (blend='cubic' takes them)")
         ends = check_ends(ends) or (TAB_ENDS_NATURAL, TAB_ENDS_NATURAL)
+        if blend == "cubic":
+            dp = ctypes.POINTER(ctypes.c_double)
+            if log_n is None:
+                capi.check(self.lib.rimphony_ctx_set_tables_2d_family_cubic(self.handle, 0, 0, None, 0, None, None, None, 0, 0, None),
+                           "rimphony_ctx_set_tables_2d_family_cubic")
+                return
+            g, m, t = check_tables_2d_nodes(gamma, mu, log_n)
+            k = None if sin_k is None else check_sin_k(sin_k, t.shape[0])
+            if t.shape[0] < 4:
+                raise ValueError("log_n: the cubic blend needs at least 4 tables, got %d" % t.shape[0])
+            c = None if param is None else TabulatedFamily._check_param(param, t.shape[0])
+            entry = self.lib.rimphony_ctx_set_tables_2d_family_cubic
+            capi.check(entry(self.handle, t.shape[0], t.shape[1], g.ctypes.data_as(dp), t.shape[2], m.ctypes.data_as(dp),
+                             t.ctypes.data_as(dp), None if k is None else k.ctypes.data_as(dp), ends[0], ends[1],
+                             None if c is None else c.ctypes.data_as(dp)),
+                       "rimphony_ctx_set_tables_2d_family_cubic")
+            return
         if log_n is None:
             capi.check(self.lib.rimphony_ctx_set_tables_2d_family(self.handle, 0, 0, None, 0, None, None, None, 0, 0),
                        "rimphony_ctx_set_tables_2d_family")
@@ -1266,28 +1294,38 @@ class TabulatedFamily2D(TabulatedFamily):
     """A family of tabulated SURFACES with a continuous parameter: log_n [n_tables][n_nodes][n_mu] = ln n(gamma_i, mu_j) on the
     gamma nodes and mu nodes of TabulatedDistribution2DNodes, table i belonging to param[i]; sin_k optionally one sin^k xi
     exponent per table; ends as for Context.set_tables_2d (Context.set_tables_2d_family).  Everything else is
-    TabulatedFamily's: the blend is linear in the index, index() piecewise linear in param, at(value) the one-point object."""
+    TabulatedFamily's: the blend is linear in the index, index() piecewise linear in param, at(value) the one-point object.
+    blend="cubic": a 4-point Lagrange cubic in param across four neighbouring tables instead (at least four tables;
+    Context.set_tables_2d_family); index(), at() and the row's parameter stay as they are."""
 
-    def __init__(self, gamma, mu, log_n, sin_k=None, param=None, ends=None):
+    def __init__(self, gamma, mu, log_n, sin_k=None, param=None, ends=None, blend="linear"):
         self.gamma, self.mu, self.log_n = check_tables_2d_nodes(gamma, mu, log_n)
         n = self.log_n.shape[0]
         self.sin_k = None if sin_k is None else check_sin_k(sin_k, n)
         self.ends = check_ends(ends)
         self.param = self._check_param(param, n)
+        if blend not in ("linear", "cubic"):
+            raise ValueError("blend: expected 'linear' or 'cubic', got %r" % (blend,))
+        if blend == "cubic" and n < 4:
+            raise ValueError("log_n: the cubic blend needs at least 4 tables, got %d" % n)
+        self.blend = blend
 
     @classmethod
-    def from_function(cls, fn, gamma, mu, param, sin_k=None, ends=None):
+    def from_function(cls, fn, gamma, mu, param, sin_k=None, ends=None, blend="linear"):
         """Tabulate n(gamma, mu; a) = fn(gamma, mu, a) (vectorised over gamma [n_nodes][1] and mu [1][n_mu], positive) for
-        every a of param at the given nodes; sin_k and ends as in the constructor."""
+        every a of param at the given nodes; sin_k, ends and blend as in the constructor."""
         g = check_gamma_nodes(gamma)
         m = check_mu_nodes(mu)
         param = np.atleast_1d(np.asarray(param, dtype=np.float64))
         log_n = np.stack([np.log(np.broadcast_to(np.asarray(fn(g[:, None], m[None, :], float(a)), dtype=np.float64), (len(g), len(m))))
                           for a in param])
-        return cls(g, m, log_n, sin_k, param, ends)
+        return cls(g, m, log_n, sin_k, param, ends, blend)
 
     def _install(self, ctx):
-        ctx.set_tables_2d_family(self.gamma, self.mu, self.log_n, self.sin_k, self.ends)
+        if self.blend == "cubic":
+            ctx.set_tables_2d_family(self.gamma, self.mu, self.log_n, self.sin_k, self.ends, "cubic", self.param)
+        else:
+            ctx.set_tables_2d_family(self.gamma, self.mu, self.log_n, self.sin_k, self.ends)
         return ctx
 
 

@@ -25,7 +25,7 @@ SYMBOLS = [
     "rimphony_ctx_set_tables_2d_pitchy", "rimphony_ctx_set_tables_2d_grid_pitchy", "rimphony_ctx_set_tables_2d_nodes",
     "rimphony_ctx_set_tables_2d_device", "rimphony_debug_tables",
     "rimphony_ctx_set_tables_2d_ends", "rimphony_ctx_set_tables_2d_device_ends",
-    "rimphony_ctx_set_tables_family", "rimphony_ctx_set_tables_2d_family",
+    "rimphony_ctx_set_tables_family", "rimphony_ctx_set_tables_2d_family", "rimphony_ctx_set_tables_2d_family_cubic",
 ]
 
 
@@ -194,6 +194,9 @@ def load():
     if hasattr(lib, "rimphony_ctx_set_tables_2d_family"):
         lib.rimphony_ctx_set_tables_2d_family.restype = c_int
         lib.rimphony_ctx_set_tables_2d_family.argtypes = [c_void_p, c_size_t, c_size_t, dp, c_size_t, dp, dp, dp, c_int, c_int]
+    if hasattr(lib, "rimphony_ctx_set_tables_2d_family_cubic"):
+        lib.rimphony_ctx_set_tables_2d_family_cubic.restype = c_int
+        lib.rimphony_ctx_set_tables_2d_family_cubic.argtypes = [c_void_p, c_size_t, c_size_t, dp, c_size_t, dp, dp, dp, c_int, c_int, dp]
     if hasattr(lib, "rimphony_ctx_set_tables_grid"):
         lib.rimphony_ctx_set_tables_grid.restype = c_int
         lib.rimphony_ctx_set_tables_grid.argtypes = [c_void_p, c_size_t, c_size_t, dp, dp, c_size_t, dp, dp]

@@ -26,7 +26,9 @@ __device__ inline void load_params(const ParamPtrs &pp, size_t i, DistParams &d)
         // (a family with a sin^k prefactor: p[2] is the context's array of row lines, dev_symphony.h: tab_family_line)
         if (KIND == DIST_TABULATED_FAMILY_PITCHY) d.par[2] = rim_frombits((uint64_t) (uintptr_t) (pp.p[2] + i * TAB_FAMILY_LINE));
         // (a family of 2-D surfaces, with a prefactor or without: the same array, a line the size of a table header per row)
-        if (tab_kind_2d_family(KIND)) d.par[2] = rim_frombits((uint64_t) (uintptr_t) (pp.p[2] + i * TAB_2D_HDR));
+        // (blended cubically across the tables: a wider line, with the row's four weights behind those words)
+        if (tab_kind_2d_family(KIND))
+            d.par[2] = rim_frombits((uint64_t) (uintptr_t) (pp.p[2] + i * (tab_kind_2d_family_cubic(KIND) ? TAB_2D_CUBIC_LINE : TAB_2D_HDR)));
         return;
     }
     constexpr int NP = (KIND == DIST_POWER_LAW) ? 4 : (KIND == DIST_THERMAL_JUETTNER) ? 1 : (KIND == DIST_PITCHY_PL) ? 5 : 4;

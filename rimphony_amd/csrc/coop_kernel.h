@@ -73,8 +73,11 @@ __global__ __launch_bounds__(64) void norm_kernel(ParamPtrs pp, size_t n, double
         // (a family judges a real index: x in [0, n_tables - 1])
         size_t fam_a;
         double fam_w;
-        const bool tab_ok = !TAB || (tab_kind_family(KIND) || tab_kind_2d_family(KIND) ? tab_family_row(pp.p[1], d.par[0], fam_a, fam_w)
-                                                                                       : tab_row_ok(pp.p[1], d.par[0]));
+        bool tab_ok = !TAB || (tab_kind_family(KIND) || tab_kind_2d_family(KIND) ? tab_family_row(pp.p[1], d.par[0], fam_a, fam_w)
+                                                                                 : tab_row_ok(pp.p[1], d.par[0]));
+        // (a cubic blend of the tables' k may leave [0, 100] between two knots: such a row names no distribution either)
+        if constexpr (KIND == DIST_TABULATED_2D_FAMILY_CUBIC_PITCHY)
+            tab_ok = tab_ok && tab_2d_family_cubic_k_ok((const double *) (uintptr_t) rim_bits(d.par[2]));
         dist_prepare<KIND>(d, RIM_NAN);
 
         double lo, hi, epsrel, pa = 1.;

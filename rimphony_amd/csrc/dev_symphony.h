@@ -52,9 +52,23 @@ enum { DIST_POWER_LAW = 0, DIST_THERMAL_JUETTNER = 1, DIST_PITCHY_PL = 2, DIST_P
        // sin^k xi prefactor per table.  The set and the lookup of DIST_TABULATED_2D_NODES; a row's parameter is a real index x
        // as in the families above, and a sample blends the sixteen node words of its cell from tables a = floor(x) and a + 1
        // and evaluates one bicubic (tab_bicubic_family).  The older forms keep the code they always ran.
-       DIST_TABULATED_2D_FAMILY = 16, DIST_TABULATED_2D_FAMILY_PITCHY = 17 };
+       DIST_TABULATED_2D_FAMILY = 16, DIST_TABULATED_2D_FAMILY_PITCHY = 17,
+       // nor these two: the same family blended CUBICALLY across its tables (rim_tab_build_2d_family_cubic), without and with a
+       // sin^k xi prefactor per table.  The set of DIST_TABULATED_2D_FAMILY followed by one knot word per table; a sample blends
+       // the sixteen node words of its cell from FOUR neighbouring tables with the Lagrange weights of the row's line
+       // (tab_2d_family_cubic_line) and evaluates one bicubic (tab_bicubic_family_cubic).  The linear forms keep their code.
+       DIST_TABULATED_2D_FAMILY_CUBIC = 18, DIST_TABULATED_2D_FAMILY_CUBIC_PITCHY = 19 };
 constexpr bool tab_kind_family(int kind) { return kind == DIST_TABULATED_FAMILY || kind == DIST_TABULATED_FAMILY_PITCHY; }
-constexpr bool tab_kind_2d_family(int kind) { return kind == DIST_TABULATED_2D_FAMILY || kind == DIST_TABULATED_2D_FAMILY_PITCHY; }
+constexpr bool tab_kind_2d_family_cubic(int kind)
+{
+    return kind == DIST_TABULATED_2D_FAMILY_CUBIC || kind == DIST_TABULATED_2D_FAMILY_CUBIC_PITCHY;
+}
+// (a family of 2-D surfaces under either blending rule: what the two rules share -- the set, the index rule, the per-row
+// normalisation -- asks this; what they do not asks tab_kind_2d_family_cubic)
+constexpr bool tab_kind_2d_family(int kind)
+{
+    return kind == DIST_TABULATED_2D_FAMILY || kind == DIST_TABULATED_2D_FAMILY_PITCHY || tab_kind_2d_family_cubic(kind);
+}
 constexpr bool dist_is_tab(int kind)
 {
     return kind == DIST_TABULATED || kind == DIST_TABULATED_ISO || kind == DIST_TABULATED_2D || kind == DIST_TABULATED_PITCHY ||
@@ -70,7 +84,7 @@ constexpr bool tab_kind_2d_nodes(int kind) { return kind == DIST_TABULATED_2D_NO
 constexpr bool tab_kind_2d_pitchy(int kind)
 {
     return kind == DIST_TABULATED_2D_PITCHY || kind == DIST_TABULATED_2D_GRID_PITCHY || kind == DIST_TABULATED_2D_NODES_PITCHY ||
-        kind == DIST_TABULATED_2D_FAMILY_PITCHY;
+        kind == DIST_TABULATED_2D_FAMILY_PITCHY || kind == DIST_TABULATED_2D_FAMILY_CUBIC_PITCHY;
 }
 enum { STOKES_I = 0, STOKES_Q = 1, STOKES_V = 2 };
 enum { COEFF_EMISSION = 0, COEFF_ABSORPTION = 1, COEFF_FARADAY = 2 };
@@ -247,6 +261,64 @@ RIM_DEV void tab_2d_family_line(double *line, const double *hdr, size_t a, doubl
     line[TAB_2D_ENDS] = (double) ((b - a) * nn * nmu * 4);
 }
 
+// The same family blended CUBICALLY across its tables (rim_tab_build_2d_family_cubic): the set above word for word, followed
+// by n_tables >= 4 knot words c_t, finite and strictly monotonic -- the parameter the tables are spaced in.  The index rule of
+// a row stays tab_family_row's.  Every batch row has a line of TAB_2D_CUBIC_LINE words (128 bytes): the eight words of the
+// line above, then the four Lagrange weights, the base table of the stencil and the row's parameter p.  Of the first eight,
+//   TAB_2D_K        is fma(L_3, k_3, fma(L_2, k_2, fma(L_1, k_1, L_0 k_0))) over the stencil's tables (0 without a prefactor);
+//   TAB_2D_ENDS     the distance in doubles between the node data of neighbouring tables: always one table's worth;
+// the others are as above (TAB_2D_NORM keeps w, for whoever reads a line back).  The rule, whose order defines the bits:
+//   p    = fma(w, c_b - c_a, c_a), b = a + 1 or, at the last table, a: at an integer x a knot, bit for bit;
+//   s    = min(max(a - 1, 0), n_tables - 4), the stencil is tables s .. s + 3;
+//   L_i  = prod over j != i, j ascending, starting from 1, of (p - c_{s+j}) / (c_{s+i} - c_{s+j}): at a knot exactly 1 for
+//          that knot's table and a zero for the others.
+// A row whose index names no table gets a = 0, w = 0, so s = 0 and p = c_0: every read stays inside the set.
+enum { TAB_2D_CUBIC_L = TAB_2D_HDR, TAB_2D_CUBIC_BASE = TAB_2D_HDR + 4, TAB_2D_CUBIC_P = TAB_2D_HDR + 5, TAB_2D_CUBIC_LINE = 16 };
+RIM_DEV size_t tab_2d_family_cubic_base(size_t nt, size_t a) { const size_t s = a > 0 ? a - 1 : 0; return s + 4 > nt ? nt - 4 : s; }
+RIM_DEV double tab_family_blend4(const double *l, double q0, double q1, double q2, double q3)
+{
+    return rim_fma(l[3], q3, rim_fma(l[2], q2, rim_fma(l[1], q1, l[0] * q0)));
+}
+// the knot words of such a set: straight behind the node data
+RIM_DEV const double *tab_2d_family_cubic_knots(const double *hdr)
+{
+    const size_t nt = (size_t) hdr[TAB_HDR_NTABLES], nn = (size_t) hdr[TAB_HDR_NNODES], cells = (size_t) hdr[TAB_HDR_H];
+    const size_t nmu = (size_t) -hdr[TAB_HDR_NMU];
+    return hdr + tab_2d_nodes_nodes_at(nt, nn, cells, nmu, (size_t) hdr[TAB_HDR_DOUBLES + TAB_2D_H]) + nt * nn * nmu * 4;
+}
+RIM_DEV void tab_2d_family_cubic_line(double *line, const double *hdr, size_t a, double w)
+{
+    const size_t nt = (size_t) hdr[TAB_HDR_NTABLES], nn = (size_t) hdr[TAB_HDR_NNODES], nmu = (size_t) -hdr[TAB_HDR_NMU];
+    const size_t b = a + 1 < nt ? a + 1 : a;
+    const size_t s = tab_2d_family_cubic_base(nt, a);
+    const double *c = tab_2d_family_cubic_knots(hdr);
+    const double *th = hdr + TAB_HDR_DOUBLES + s * TAB_2D_HDR;
+    const long long to_set = ((long long) (uintptr_t) th - (long long) (uintptr_t) line) / (long long) sizeof(double);
+    const double p = rim_fma(w, c[b] - c[a], c[a]);
+    double *l = line + TAB_2D_CUBIC_L;
+    for (int i = 0; i < 4; i++) {
+        double v = 1.;
+        for (int j = 0; j < 4; j++)
+            if (j != i) v = v * ((p - c[s + j]) / (c[s + i] - c[s + j]));
+        l[i] = v;
+    }
+    line[TAB_2D_LAST] = th[TAB_2D_LAST];
+    line[TAB_2D_INVH] = th[TAB_2D_INVH];
+    line[TAB_2D_H] = th[TAB_2D_H];
+    line[TAB_2D_NORM] = w;
+    line[TAB_2D_K] = tab_family_blend4(l, th[TAB_2D_K], th[TAB_2D_HDR + TAB_2D_K], th[2 * TAB_2D_HDR + TAB_2D_K],
+                                       th[3 * TAB_2D_HDR + TAB_2D_K]);
+    line[TAB_2D_MU_GUIDE] = (double) (to_set + (long long) th[TAB_2D_MU_GUIDE]);
+    line[TAB_2D_MU_NODES] = (double) (to_set + (long long) th[TAB_2D_MU_NODES]);
+    line[TAB_2D_ENDS] = (double) (nn * nmu * 4);
+    line[TAB_2D_CUBIC_BASE] = (double) s;
+    line[TAB_2D_CUBIC_P] = p;
+    line[TAB_2D_CUBIC_P + 1] = 0.; line[TAB_2D_CUBIC_P + 2] = 0.;
+}
+// is the blended k of a row's line an exponent the prefactor takes?  A cubic may overshoot between knots; such a row is a NaN
+// row (norm_kernel and the tests' oracle ask this).  Without a prefactor the word is 0.
+RIM_DEV bool tab_2d_family_cubic_k_ok(const double *line) { return line[TAB_2D_K] >= 0. && line[TAB_2D_K] <= 100.; }
+
 template <int KIND>
 RIM_DEV void dist_prepare(DistParams &d, double norm)
 {
@@ -255,7 +327,8 @@ RIM_DEV void dist_prepare(DistParams &d, double norm)
         // (tab_2d_family_line).  Out: what a row of a 2-D set on given nodes carries, with the line where the table's header
         // is: par[0] the line, par[1] the node data of table a -- those of table b lie line[TAB_2D_ENDS] doubles further on --,
         // par[2] the set's u nodes, par[3] 1 / (cell width), par[4] the index of the last guide cell, inv_gamma_cutoff the
-        // guide's address.  DistParams does not grow.
+        // guide's address.  DistParams does not grow.  (The cubic blend: par[2] names a line of tab_2d_family_cubic_line, and
+        // par[1] the node data of the stencil's base table.)
         const double *hdr = (const double *) (uintptr_t) rim_bits(d.par[1]);
         size_t a;
         double w;
@@ -265,7 +338,8 @@ RIM_DEV void dist_prepare(DistParams &d, double norm)
         const double *guide = hdr + tab_2d_grid_guide_at(nt);
         const size_t at = tab_2d_nodes_nodes_at(nt, nn, cells, nmu, (size_t) hdr[TAB_HDR_DOUBLES + TAB_2D_H]);
         d.par[0] = d.par[2];
-        d.par[1] = rim_frombits((uint64_t) (uintptr_t) (hdr + at + a * nn * nmu * 4));
+        const size_t first = tab_kind_2d_family_cubic(KIND) ? tab_2d_family_cubic_base(nt, a) : a;
+        d.par[1] = rim_frombits((uint64_t) (uintptr_t) (hdr + at + first * nn * nmu * 4));
         d.par[2] = rim_frombits((uint64_t) (uintptr_t) (guide + tab_grid_guide_doubles(cells)));
         d.par[3] = hdr[TAB_HDR_INVH];
         d.par[4] = hdr[TAB_HDR_H] - 1.;
@@ -487,7 +561,7 @@ RIM_DEV bool tab_kind_has_pitch(const DistParams &d)
     // row does)
     return KIND == DIST_TABULATED_2D || KIND == DIST_TABULATED_PITCHY || KIND == DIST_TABULATED_GRID ||
         KIND == DIST_TABULATED_2D_GRID || tab_kind_2d_pitchy(KIND) || KIND == DIST_TABULATED_2D_NODES ||
-        KIND == DIST_TABULATED_FAMILY_PITCHY || KIND == DIST_TABULATED_2D_FAMILY ||
+        KIND == DIST_TABULATED_FAMILY_PITCHY || KIND == DIST_TABULATED_2D_FAMILY || KIND == DIST_TABULATED_2D_FAMILY_CUBIC ||
         (KIND != DIST_TABULATED_ISO && KIND != DIST_TABULATED_FAMILY && tab_has_pitch(d));
 }
 
@@ -763,6 +837,49 @@ RIM_DEV void tab_bicubic_family(const DistParams &d, double gamma, double mu, do
     dsdmu = dsdtm * minvh;
 }
 
+// tab_bicubic_family under the CUBIC blend (d: dist_prepare<DIST_TABULATED_2D_FAMILY_CUBIC> or <.._PITCHY>): the cell is found
+// once; then, Hermite step by Hermite step along mu, the four node words of the step are read from the stencil's four tables
+// and blended with the row's Lagrange weights, fma(L_3, q_3, fma(L_2, q_2, fma(L_1, q_1, L_0 q_0))): sixteen words in flight,
+// not sixty-four.  Weights 0, 1, 0, 0 in some order give that table's word itself, but for the sign of a zero.  The weights
+// and the table stride are five wave-uniform words of the row's line.  Every read stays inside the set.
+RIM_DEV void tab_bicubic_family_cubic(const DistParams &d, double gamma, double mu, double &sval, double &dsdu, double &dsdmu)
+{
+    const double *th = (const double *) (uintptr_t) rim_bits(d.par[0]);
+    const double *nodes = (const double *) (uintptr_t) rim_bits(d.par[1]);
+    const double *un = (const double *) (uintptr_t) rim_bits(d.par[2]);
+    const double *mn = th + (long long) th[TAB_2D_MU_NODES];
+    const double l[4] = { th[TAB_2D_CUBIC_L], th[TAB_2D_CUBIC_L + 1], th[TAB_2D_CUBIC_L + 2], th[TAB_2D_CUBIC_L + 3] };
+    const long long st = (long long) th[TAB_2D_ENDS];
+    const double u = rim_log(gamma);
+    const long long i = tab_2d_grid_interval(d, u);
+    const double *q = un + 2 * i;
+    const double uinvh = q[1], uh = q[2] - q[0];
+    const double tu = (u - q[0]) * uinvh;
+    const long long j = tab_2d_nodes_mu_interval(th, mn, mu);
+    const double *r = mn + 2 * j;
+    const double minvh = r[1], mh = r[2] - r[0];
+    const double tm = (mu - r[0]) * minvh;
+    const long long nmu = (long long) th[TAB_2D_LAST] + 2;
+    const double *a = nodes + (i * nmu + j) * 4;        // nodes (i, j), (i, j + 1) of the stencil's base table
+    const double *b = a + nmu * 4;                      // nodes (i + 1, j), (i + 1, j + 1) of it
+    const double *a1 = a + st, *a2 = a1 + st, *a3 = a2 + st;    // the same of the three tables above it
+    const double *b1 = b + st, *b2 = b1 + st, *b3 = b2 + st;
+    double va, dva, wa, dwa, vb, dvb, wb, dwb;
+    tab_hermite4(tab_family_blend4(l, a[0], a1[0], a2[0], a3[0]), tab_family_blend4(l, a[2], a1[2], a2[2], a3[2]),
+                 tab_family_blend4(l, a[4], a1[4], a2[4], a3[4]), tab_family_blend4(l, a[6], a1[6], a2[6], a3[6]), mh, tm, va, dva);
+    tab_hermite4(tab_family_blend4(l, a[1], a1[1], a2[1], a3[1]), tab_family_blend4(l, a[3], a1[3], a2[3], a3[3]),
+                 tab_family_blend4(l, a[5], a1[5], a2[5], a3[5]), tab_family_blend4(l, a[7], a1[7], a2[7], a3[7]), mh, tm, wa, dwa);
+    tab_hermite4(tab_family_blend4(l, b[0], b1[0], b2[0], b3[0]), tab_family_blend4(l, b[2], b1[2], b2[2], b3[2]),
+                 tab_family_blend4(l, b[4], b1[4], b2[4], b3[4]), tab_family_blend4(l, b[6], b1[6], b2[6], b3[6]), mh, tm, vb, dvb);
+    tab_hermite4(tab_family_blend4(l, b[1], b1[1], b2[1], b3[1]), tab_family_blend4(l, b[3], b1[3], b2[3], b3[3]),
+                 tab_family_blend4(l, b[5], b1[5], b2[5], b3[5]), tab_family_blend4(l, b[7], b1[7], b2[7], b3[7]), mh, tm, wb, dwb);
+    double dsdtu, dsdtm, unused;
+    tab_hermite4(va, wa, vb, wb, uh, tu, sval, dsdtu);
+    tab_hermite4(dva, dwa, dvb, dwb, uh, tu, dsdtm, unused);
+    dsdu = dsdtu * uinvh;
+    dsdmu = dsdtm * minvh;
+}
+
 // nbar(gamma) = 1/2 int exp(S(ln gamma, mu)) dmu of a 2-D table: the integrand of its normalisation.  The 31-point Kronrod
 // rule (xgk, wgk: gk31_table.h) on every mu cell, summed in node order -- the rule P of a pitch row uses.  KIND: the form
 // of the set, one of the six 2-D forms.
@@ -809,7 +926,8 @@ RIM_DEV double tab_2d_norm_integrand(const DistParams &d, double g, const double
                     mu = centre + half * xgk[k];
                     if (tab_kind_2d_pitchy(KIND)) sin2 = 1. - mu * mu;
                 }
-                if (tab_kind_2d_family(KIND)) tab_bicubic_family(d, g, mu, sval, dsdu, dsdmu);
+                if (tab_kind_2d_family_cubic(KIND)) tab_bicubic_family_cubic(d, g, mu, sval, dsdu, dsdmu);
+                else if (tab_kind_2d_family(KIND)) tab_bicubic_family(d, g, mu, sval, dsdu, dsdmu);
                 else tab_bicubic_nodes(d, g, mu, sval, dsdu, dsdmu);
                 if (tab_kind_2d_pitchy(KIND)) acc += wgk[k] * (jac * (RimMath<0>::pow(rim_sqrt(sin2), sk) * rim_exp(sval)));
                 else acc += wgk[k] * rim_exp(sval);
@@ -873,10 +991,11 @@ RIM_DEV void tab_calc_f_both(const DistParams &d, double gamma, double cos_xi, d
     f = 0.; dfdg = 0.; dfdcx = 0.;
     if (gamma < d.inv_kappa_width || gamma > d.neg_inverse_t) return;
     if (KIND == DIST_TABULATED_2D || KIND == DIST_TABULATED_2D_GRID || KIND == DIST_TABULATED_2D_NODES ||
-        KIND == DIST_TABULATED_2D_FAMILY) {
+        KIND == DIST_TABULATED_2D_FAMILY || KIND == DIST_TABULATED_2D_FAMILY_CUBIC) {
         // f = norm exp(S(ln gamma, mu)) / (gamma^2 beta), d f / d mu = f S_mu: one exponential per sample
         double sval, dsdu, dsdmu;
-        if (KIND == DIST_TABULATED_2D_FAMILY) tab_bicubic_family(d, gamma, cos_xi, sval, dsdu, dsdmu);
+        if (KIND == DIST_TABULATED_2D_FAMILY_CUBIC) tab_bicubic_family_cubic(d, gamma, cos_xi, sval, dsdu, dsdmu);
+        else if (KIND == DIST_TABULATED_2D_FAMILY) tab_bicubic_family(d, gamma, cos_xi, sval, dsdu, dsdmu);
         else if (KIND == DIST_TABULATED_2D_NODES) tab_bicubic_nodes(d, gamma, cos_xi, sval, dsdu, dsdmu);
         else if (KIND == DIST_TABULATED_2D_GRID) tab_bicubic_grid(d, gamma, cos_xi, sval, dsdu, dsdmu);
         else tab_bicubic(d, gamma, cos_xi, sval, dsdu, dsdmu);
@@ -894,7 +1013,8 @@ RIM_DEV void tab_calc_f_both(const DistParams &d, double gamma, double cos_xi, d
         const double *th = (const double *) (uintptr_t) rim_bits(d.par[0]);
         const double k = th[TAB_2D_K];
         double sval, dsdu, dsdmu;
-        if (tab_kind_2d_family(KIND)) tab_bicubic_family(d, gamma, cos_xi, sval, dsdu, dsdmu);
+        if (tab_kind_2d_family_cubic(KIND)) tab_bicubic_family_cubic(d, gamma, cos_xi, sval, dsdu, dsdmu);
+        else if (tab_kind_2d_family(KIND)) tab_bicubic_family(d, gamma, cos_xi, sval, dsdu, dsdmu);
         else if (tab_kind_2d_nodes(KIND)) tab_bicubic_nodes(d, gamma, cos_xi, sval, dsdu, dsdmu);
         else if (tab_kind_2d_on_grid(KIND)) tab_bicubic_grid(d, gamma, cos_xi, sval, dsdu, dsdmu);
         else tab_bicubic(d, gamma, cos_xi, sval, dsdu, dsdmu);

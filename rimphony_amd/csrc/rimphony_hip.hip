@@ -334,9 +334,9 @@ struct rimphony_ctx {
     unsigned long long hb_task;
     // what hipOccupancyMaxActiveBlocksPerMultiprocessor answered (-1: the query failed), asked once per context
     // (= per device) and instantiation: coop_kernel<P> by problem (0 Symphony, 1 Heyvaerts) and distribution kind,
-    int resident[2][18];            // (kind 4 fourteen times: the cell of a table set is its DIST_TABULATED* value, tab_kind below)
+    int resident[2][20];            // (kind 4 sixteen times: the cell of a table set is its DIST_TABULATED* value, tab_kind below)
     int resident_f32[4];            // ... the Symphony kernels' fp32-integrand variants,
-    int resident_group[2][18];      // ... group_kernel<P> [Symphony groups / Faraday pair][kind] (kind 4: the cells of `resident`; no Faraday pair)
+    int resident_group[2][20];      // ... group_kernel<P> [Symphony groups / Faraday pair][kind] (kind 4: the cells of `resident`; no Faraday pair)
     // 0: this context has the GPU to itself (it holds the device's lock file); 1: another context or process had
     // the device first -- smaller persistent grids, no cooperative tail (see rimphony_ctx_create)
     int shared_mode;
@@ -356,8 +356,8 @@ struct rimphony_ctx {
     RimDevBuf<double> d_tab;
     int tab_kind = DIST_TABULATED_ISO;  // the form of that set as its DIST_TABULATED* value (tab_launch.h): which instantiation of the kind's kernels runs
     // a family with a sin^k prefactor, and a family of 2-D surfaces with one or without: one 64-byte line per row of the batch
-    // in flight (dev_symphony.h: tab_family_line, tab_2d_family_line), written by the normalisation's launch and read by every
-    // later kernel of the batch
+    // in flight (dev_symphony.h: tab_family_line, tab_2d_family_line; 128 bytes where the surfaces are blended cubically:
+    // tab_2d_family_cubic_line), written by the normalisation's launch and read by every later kernel of the batch
     RimDevBuf<double> d_famline;
 };
 
@@ -768,6 +768,24 @@ extern "C" int rimphony_ctx_set_tables_2d_family(rimphony_ctx *c, size_t n_table
     return install_tables(c, blob, sin_k ? DIST_TABULATED_2D_FAMILY_PITCHY : DIST_TABULATED_2D_FAMILY);
 }
 
+// The same family blended CUBICALLY across its tables: the set above followed by one knot word per table, `param` or 0, 1, 2 ..
+// A sample blends the node words of four neighbouring tables with the Lagrange weights of its row
+// (rimphony_tab_2d_family_cubic.hip; with sin_k rimphony_tab_2d_family_cubic_pitchy.hip).  The linear family's check and, on
+// top of it, at least four tables and finite, strictly monotonic knots.
+extern "C" int rimphony_ctx_set_tables_2d_family_cubic(rimphony_ctx *c, size_t n_tables, size_t n_nodes, const double *gamma, size_t n_mu,
+                                                       const double *mu, const double *log_n, const double *sin_k, int ends_gamma,
+                                                       int ends_mu, const double *param)
+{
+    if (!c || rim_tab_check_ends(ends_gamma, ends_mu)) return RIMPHONY_EINVAL;
+    std::vector<double> blob;
+    if (n_tables) {
+        if (rim_tab_check_2d_family_cubic(n_tables, n_nodes, gamma, n_mu, mu, log_n, sin_k, param)) return RIMPHONY_EINVAL;
+        try { rim_tab_build_2d_family_cubic(n_tables, n_nodes, gamma, n_mu, mu, log_n, sin_k, param, blob, ends_gamma, ends_mu); }
+        catch (const std::bad_alloc &) { return RIMPHONY_ENOMEM; }
+    }
+    return install_tables(c, blob, sin_k ? DIST_TABULATED_2D_FAMILY_CUBIC_PITCHY : DIST_TABULATED_2D_FAMILY_CUBIC);
+}
+
 // A set on gamma nodes of its own, always this form: the sin^k form's contents on the given nodes.  The host solves the
 // spline and fills the guide (tab_spline.h: rim_tab_build_grid); where there are pitch rows, P is integrated by the sin^k
 // form's kernel, which reads the tail of the set as a set of its own.
@@ -998,10 +1016,14 @@ static int check_batch_args(int kind, std::initializer_list<const void *> head, 
 // their address in pp.p[2] (load_params), where the normalisation's launch writes them.  Any other set: nothing.
 static_assert(TAB_FAMILY_LINE == TAB_2D_HDR, "one array serves the lines of either kind of family");
 static bool tab_kind_has_lines(int tab_kind) { return tab_kind == DIST_TABULATED_FAMILY_PITCHY || tab_kind_2d_family(tab_kind); }
+// (the line of a family of 2-D surfaces blended cubically is wider: load_params strides by the same rule)
+static size_t tab_kind_line_doubles(int tab_kind) { return tab_kind_2d_family_cubic(tab_kind) ? TAB_2D_CUBIC_LINE : TAB_FAMILY_LINE; }
 static int family_lines(rimphony_ctx *c, int kind, size_t n, ParamPtrs &pp)
 {
     if (kind != RIMPHONY_TABULATED || !tab_kind_has_lines(c->tab_kind)) return RIMPHONY_OK;
-    const int rc = c->d_famline.grow(n, n * TAB_FAMILY_LINE * sizeof(double), "the rows' lines of a table family");
+    // (counted in doubles, not rows: the buffer outlives a change of form, and the forms' lines differ in width)
+    const size_t doubles = n * tab_kind_line_doubles(c->tab_kind);
+    const int rc = c->d_famline.grow(doubles, doubles * sizeof(double), "the rows' lines of a table family");
     if (rc) return rc;
     pp.p[2] = c->d_famline.p;
     return RIMPHONY_OK;
@@ -1228,7 +1250,8 @@ static const bool RIM_TAB_GROUP_DEFAULT[5] = {      // [tab_kind - DIST_TABULATE
 // (A family of energy tables has no line of its own either: it takes the line of the plain form its integer rows are -- the
 // isotropic form's, or with a prefactor the sin^k form's -- until profiles/tabulated_family_times.txt says otherwise.  A family
 // of 2-D surfaces takes the 2-D form's, as every 2-D form does; measured for it, the group kernel is 1.5 x (no prefactor) and
-// 2.0 x (sin^k) faster per Symphony sample than one wave per coefficient: profiles/tabulated_2d_family_times.txt.)
+// 2.0 x (sin^k) faster per Symphony sample than one wave per coefficient: profiles/tabulated_2d_family_times.txt.  The same
+// family blended cubically takes the same line: profiles/tabulated_2d_family_cubic_times.txt.)
 static bool rim_tab_runs_group(const rimphony_ctx *c)
 {
     if (c->knobs.tab_group >= 0) return c->knobs.tab_group != 0;

@@ -141,7 +141,7 @@ auto rim_with_kind(int kind, F &&f)
 
 // The same for the tabulated distribution, whose instantiations go by the form of the installed table set: the set's
 // DIST_TABULATED* value (dev_symphony.h), which is what a context remembers, the cell of its occupancy caches and the
-// argument of tab_launch.h.  Anything but the thirteen named forms is DIST_TABULATED, a set with pitch rows.
+// argument of tab_launch.h.  Anything but the fifteen named forms is DIST_TABULATED, a set with pitch rows.
 template <class F>
 auto rim_with_tab_kind(int tab_kind, F &&f)
 {
@@ -160,6 +160,8 @@ auto rim_with_tab_kind(int tab_kind, F &&f)
     case DIST_TABULATED_FAMILY_PITCHY: return f(std::integral_constant<int, DIST_TABULATED_FAMILY_PITCHY>{});
     case DIST_TABULATED_2D_FAMILY: return f(std::integral_constant<int, DIST_TABULATED_2D_FAMILY>{});
     case DIST_TABULATED_2D_FAMILY_PITCHY: return f(std::integral_constant<int, DIST_TABULATED_2D_FAMILY_PITCHY>{});
+    case DIST_TABULATED_2D_FAMILY_CUBIC: return f(std::integral_constant<int, DIST_TABULATED_2D_FAMILY_CUBIC>{});
+    case DIST_TABULATED_2D_FAMILY_CUBIC_PITCHY: return f(std::integral_constant<int, DIST_TABULATED_2D_FAMILY_CUBIC_PITCHY>{});
     default: return f(std::integral_constant<int, DIST_TABULATED>{});
     }
 }

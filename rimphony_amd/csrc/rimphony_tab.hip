@@ -26,6 +26,8 @@
 // DIST_TABULATED_FAMILY_PITCHY): rimphony_tab_family.hip, rimphony_tab_family_pitchy.hip, norm_kernel included.
 // And the families of 2-D surfaces on given nodes (DIST_TABULATED_2D_FAMILY, DIST_TABULATED_2D_FAMILY_PITCHY):
 // rimphony_tab_2d_family.hip, rimphony_tab_2d_family_pitchy.hip, norm_kernel included.
+// And the same families blended cubically across their tables (DIST_TABULATED_2D_FAMILY_CUBIC, .._CUBIC_PITCHY):
+// rimphony_tab_2d_family_cubic.hip, rimphony_tab_2d_family_cubic_pitchy.hip, norm_kernel included.
 #include <hip/hip_runtime.h>
 #include "coop_kernel.h"
 #include "tab_launch.h"
@@ -129,6 +131,8 @@ RimCoopKernelInfo rim_tab_coop_kernel(int problem, int tab_kind)
         else if constexpr (KIND == DIST_TABULATED_FAMILY_PITCHY) return rim_tab_family_pitchy_coop_kernel(problem);
         else if constexpr (KIND == DIST_TABULATED_2D_FAMILY) return rim_tab_2d_family_coop_kernel(problem);
         else if constexpr (KIND == DIST_TABULATED_2D_FAMILY_PITCHY) return rim_tab_2d_family_pitchy_coop_kernel(problem);
+        else if constexpr (KIND == DIST_TABULATED_2D_FAMILY_CUBIC) return rim_tab_2d_family_cubic_coop_kernel(problem);
+        else if constexpr (KIND == DIST_TABULATED_2D_FAMILY_CUBIC_PITCHY) return rim_tab_2d_family_cubic_pitchy_coop_kernel(problem);
         else return problem ? coop_info<HeyvaertsProblem<KIND>>() : coop_info<SymphonyProblem<KIND>>();
     });
 }
@@ -146,6 +150,8 @@ void rim_tab_launch_norm(int tab_kind, unsigned grid, hipStream_t st, const Para
         else if constexpr (KIND == DIST_TABULATED_FAMILY_PITCHY) rim_tab_family_pitchy_launch_norm(grid, st, pp, n, d_norm, queue, spill);
         else if constexpr (KIND == DIST_TABULATED_2D_FAMILY) rim_tab_2d_family_launch_norm(grid, st, pp, n, d_norm, queue, spill);
         else if constexpr (KIND == DIST_TABULATED_2D_FAMILY_PITCHY) rim_tab_2d_family_pitchy_launch_norm(grid, st, pp, n, d_norm, queue, spill);
+        else if constexpr (KIND == DIST_TABULATED_2D_FAMILY_CUBIC) rim_tab_2d_family_cubic_launch_norm(grid, st, pp, n, d_norm, queue, spill);
+        else if constexpr (KIND == DIST_TABULATED_2D_FAMILY_CUBIC_PITCHY) rim_tab_2d_family_cubic_pitchy_launch_norm(grid, st, pp, n, d_norm, queue, spill);
         else
             hipLaunchKernelGGL(norm_kernel<KIND>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pp, n, d_norm, queue, spill);
     });
@@ -165,6 +171,8 @@ void rim_tab_launch_integrand(int tab_kind, unsigned grid, hipStream_t st, const
         else if constexpr (KIND == DIST_TABULATED_FAMILY_PITCHY) rim_tab_family_pitchy_launch_integrand(grid, st, pa, d_norm, count, d_n, d_gamma, d_out);
         else if constexpr (KIND == DIST_TABULATED_2D_FAMILY) rim_tab_2d_family_launch_integrand(grid, st, pa, d_norm, count, d_n, d_gamma, d_out);
         else if constexpr (KIND == DIST_TABULATED_2D_FAMILY_PITCHY) rim_tab_2d_family_pitchy_launch_integrand(grid, st, pa, d_norm, count, d_n, d_gamma, d_out);
+        else if constexpr (KIND == DIST_TABULATED_2D_FAMILY_CUBIC) rim_tab_2d_family_cubic_launch_integrand(grid, st, pa, d_norm, count, d_n, d_gamma, d_out);
+        else if constexpr (KIND == DIST_TABULATED_2D_FAMILY_CUBIC_PITCHY) rim_tab_2d_family_cubic_pitchy_launch_integrand(grid, st, pa, d_norm, count, d_n, d_gamma, d_out);
         else hipLaunchKernelGGL(integrand_kernel_n<KIND>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pa, d_norm, count, d_n, d_gamma, d_out);
     });
 }
@@ -183,6 +191,8 @@ void rim_tab_launch_gamma_integral(int tab_kind, unsigned grid, hipStream_t st, 
         else if constexpr (KIND == DIST_TABULATED_FAMILY_PITCHY) rim_tab_family_pitchy_launch_gamma_integral(grid, st, pa, d_norm, count, d_n, d_out, spill);
         else if constexpr (KIND == DIST_TABULATED_2D_FAMILY) rim_tab_2d_family_launch_gamma_integral(grid, st, pa, d_norm, count, d_n, d_out, spill);
         else if constexpr (KIND == DIST_TABULATED_2D_FAMILY_PITCHY) rim_tab_2d_family_pitchy_launch_gamma_integral(grid, st, pa, d_norm, count, d_n, d_out, spill);
+        else if constexpr (KIND == DIST_TABULATED_2D_FAMILY_CUBIC) rim_tab_2d_family_cubic_launch_gamma_integral(grid, st, pa, d_norm, count, d_n, d_out, spill);
+        else if constexpr (KIND == DIST_TABULATED_2D_FAMILY_CUBIC_PITCHY) rim_tab_2d_family_cubic_pitchy_launch_gamma_integral(grid, st, pa, d_norm, count, d_n, d_out, spill);
         else hipLaunchKernelGGL(gamma_integral_kernel<KIND>, dim3(grid), dim3(64), RIM_DYN_LDS, st, pa, d_norm, count, d_n, d_out, spill);
     });
 }

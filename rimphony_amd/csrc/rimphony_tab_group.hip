@@ -11,7 +11,8 @@
 // rimphony_tab_2d_pitchy_group.hip's and rimphony_tab_2d_grid_pitchy_group.hip's, those of the 2-D form on given gamma and mu
 // nodes rimphony_tab_2d_nodes_group.hip's and rimphony_tab_2d_nodes_pitchy_group.hip's, those of the families of energy tables
 // rimphony_tab_family_group.hip's and rimphony_tab_family_pitchy_group.hip's, those of the families of 2-D surfaces
-// rimphony_tab_2d_family_group.hip's and rimphony_tab_2d_family_pitchy_group.hip's.  They live with the
+// rimphony_tab_2d_family_group.hip's and rimphony_tab_2d_family_pitchy_group.hip's, those of the same families blended
+// cubically rimphony_tab_2d_family_cubic_group.hip's and rimphony_tab_2d_family_cubic_pitchy_group.hip's.  They live with the
 // budget of rimphony_group.hip's: RIM_GROUP_WAVES waves per SIMD and the same LDS block.  The kind has no Faraday group
 // (RIMPHONY_FARADAY_GROUP is measured slower for the analytic kinds: DESIGN.md section 5).
 #include "group_kernel.h"
@@ -31,6 +32,8 @@ const void *rim_tab_group_kernel(int tab_kind)
         else if constexpr (KIND == DIST_TABULATED_FAMILY_PITCHY) return rim_tab_family_pitchy_group_kernel();
         else if constexpr (KIND == DIST_TABULATED_2D_FAMILY) return rim_tab_2d_family_group_kernel();
         else if constexpr (KIND == DIST_TABULATED_2D_FAMILY_PITCHY) return rim_tab_2d_family_pitchy_group_kernel();
+        else if constexpr (KIND == DIST_TABULATED_2D_FAMILY_CUBIC) return rim_tab_2d_family_cubic_group_kernel();
+        else if constexpr (KIND == DIST_TABULATED_2D_FAMILY_CUBIC_PITCHY) return rim_tab_2d_family_cubic_pitchy_group_kernel();
         else return reinterpret_cast<const void *>(group_kernel<SymGroupProblem<KIND>>);
     });
 }

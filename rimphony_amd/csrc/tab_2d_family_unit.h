@@ -10,6 +10,11 @@
 // nbar(gamma) = 1/2 int (1 - mu^2)^(k/2) exp(S) dmu by the Kronrod rule on every mu cell, the end cells of a set with a
 // prefactor under 1 - |mu| = h v^4 -- the quadrature the plain form runs once per table as the set comes in
 // (tab_2d_pitchy_unit.h), run here once per row.  Every later kernel of the batch reads the line as it reads a table's header.
+//
+// The units of the CUBIC blend across the tables include this too (rimphony_tab_2d_family_cubic.hip:
+// DIST_TABULATED_2D_FAMILY_CUBIC; rimphony_tab_2d_family_cubic_pitchy.hip: DIST_TABULATED_2D_FAMILY_CUBIC_PITCHY): their
+// prologue writes a 128-byte line per row -- the same eight words, then the four Lagrange weights, the stencil's base table
+// and the row's parameter (tab_2d_family_cubic_line) --, and a sample blends four tables (tab_bicubic_family_cubic).
 #include <hip/hip_runtime.h>
 #include "coop_kernel.h"
 #include "tab_launch.h"
@@ -35,7 +40,8 @@ __global__ void tab_2d_family_lines_kernel(ParamPtrs pp, size_t n, double *lines
     size_t a;
     double w;
     tab_family_row(set, pp.p[0][i], a, w);
-    tab_2d_family_line(lines + i * TAB_2D_HDR, set, a, w);
+    if constexpr (tab_kind_2d_family_cubic(KIND)) tab_2d_family_cubic_line(lines + i * TAB_2D_CUBIC_LINE, set, a, w);
+    else tab_2d_family_line(lines + i * TAB_2D_HDR, set, a, w);
 }
 
 void RIM_T2F_LAUNCH_NORM(unsigned grid, hipStream_t st, const ParamPtrs &pp, size_t n, double *d_norm, unsigned long long *queue,

@@ -23,7 +23,8 @@ struct RimCoopKernelInfo {
 // on gamma nodes of its own, DIST_TABULATED_2D_PITCHY and DIST_TABULATED_2D_GRID_PITCHY for those two with a sin^k xi prefactor,
 // DIST_TABULATED_2D_NODES and DIST_TABULATED_2D_NODES_PITCHY for a 2-D set on gamma and mu nodes of its own, without and with one,
 // DIST_TABULATED_FAMILY and DIST_TABULATED_FAMILY_PITCHY for a family of energy tables, without and with one,
-// DIST_TABULATED_2D_FAMILY and DIST_TABULATED_2D_FAMILY_PITCHY for a family of 2-D surfaces on given nodes, without and with one.
+// DIST_TABULATED_2D_FAMILY and DIST_TABULATED_2D_FAMILY_PITCHY for a family of 2-D surfaces on given nodes, without and with one,
+// DIST_TABULATED_2D_FAMILY_CUBIC and DIST_TABULATED_2D_FAMILY_CUBIC_PITCHY for such a family blended cubically across its tables.
 
 // coop_kernel<SymphonyProblem<K>> (problem 0) or coop_kernel<HeyvaertsProblem<K>> (1)
 RimCoopKernelInfo rim_tab_coop_kernel(int problem, int tab_kind);
@@ -42,6 +43,8 @@ const void *rim_tab_family_group_kernel();              // rimphony_tab_family_g
 const void *rim_tab_family_pitchy_group_kernel();       // rimphony_tab_family_pitchy_group.hip
 const void *rim_tab_2d_family_group_kernel();           // rimphony_tab_2d_family_group.hip
 const void *rim_tab_2d_family_pitchy_group_kernel();    // rimphony_tab_2d_family_pitchy_group.hip
+const void *rim_tab_2d_family_cubic_group_kernel();     // rimphony_tab_2d_family_cubic_group.hip
+const void *rim_tab_2d_family_cubic_pitchy_group_kernel();      // rimphony_tab_2d_family_cubic_pitchy_group.hip
 // norm_kernel, integrand_kernel_n and gamma_integral_kernel of the kind: enqueue only, the caller asks hipGetLastError().
 // An isotropic set runs their DIST_TABULATED instantiations (rimphony_internal.h: rim_tab_seam_kind).  (The rows of a 2-D set
 // read their table's normalisation, which rim_tab_launch_table_norms computed when the set came in: one wave per table,
@@ -132,6 +135,24 @@ void rim_tab_2d_family_pitchy_launch_integrand(unsigned grid, hipStream_t st, co
                                                const double *d_n, const double *d_gamma, double *d_out);
 void rim_tab_2d_family_pitchy_launch_gamma_integral(unsigned grid, hipStream_t st, const PointArgs &pa, const double *d_norm, size_t count,
                                                     const double *d_n, double *d_out, double *spill);
+
+// The same for such a family blended cubically across its tables: DIST_TABULATED_2D_FAMILY_CUBIC in
+// rimphony_tab_2d_family_cubic.hip, DIST_TABULATED_2D_FAMILY_CUBIC_PITCHY in rimphony_tab_2d_family_cubic_pitchy.hip (the same
+// text, tab_2d_family_unit.h); the rows' lines are 128 bytes each (tab_2d_family_cubic_line).
+RimCoopKernelInfo rim_tab_2d_family_cubic_coop_kernel(int problem);
+void rim_tab_2d_family_cubic_launch_norm(unsigned grid, hipStream_t st, const ParamPtrs &pp, size_t n, double *d_norm, unsigned long long *queue,
+                                         double *spill);
+void rim_tab_2d_family_cubic_launch_integrand(unsigned grid, hipStream_t st, const PointArgs &pa, const double *d_norm, size_t count,
+                                              const double *d_n, const double *d_gamma, double *d_out);
+void rim_tab_2d_family_cubic_launch_gamma_integral(unsigned grid, hipStream_t st, const PointArgs &pa, const double *d_norm, size_t count,
+                                                   const double *d_n, double *d_out, double *spill);
+RimCoopKernelInfo rim_tab_2d_family_cubic_pitchy_coop_kernel(int problem);
+void rim_tab_2d_family_cubic_pitchy_launch_norm(unsigned grid, hipStream_t st, const ParamPtrs &pp, size_t n, double *d_norm,
+                                                unsigned long long *queue, double *spill);
+void rim_tab_2d_family_cubic_pitchy_launch_integrand(unsigned grid, hipStream_t st, const PointArgs &pa, const double *d_norm, size_t count,
+                                                     const double *d_n, const double *d_gamma, double *d_out);
+void rim_tab_2d_family_cubic_pitchy_launch_gamma_integral(unsigned grid, hipStream_t st, const PointArgs &pa, const double *d_norm, size_t count,
+                                                          const double *d_n, double *d_out, double *spill);
 
 // A 2-D set installed from device memory (rimphony_tab_install.hip, tab_install.h): *d_flag, zeroed by the caller, becomes 1
 // where one of the `count` values at d_log_n is not finite; the three families of sweeps that fill the node data of `s`, in

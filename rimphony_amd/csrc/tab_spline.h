@@ -783,4 +783,32 @@ inline void rim_tab_build_2d_family(size_t n_tables, size_t n_nodes, const doubl
     for (size_t t = 0; t < n_tables; t++) blob[(size_t) TAB_HDR_DOUBLES + t * TAB_2D_HDR + TAB_2D_NORM] = RIM_NAN;
 }
 
+// The same family blended CUBICALLY across its tables (dev_symphony.h: tab_2d_family_cubic_line, tab_bicubic_family_cubic).
+// The linear family's check; at least four tables, the stencil of a 4-point Lagrange cubic; `param`, where given, the knots
+// the tables are spaced in: finite and strictly monotonic, increasing or decreasing (null: the index itself).
+inline int rim_tab_check_2d_family_cubic(size_t n_tables, size_t n_nodes, const double *gamma, size_t n_mu, const double *mu,
+                                         const double *log_n, const double *sin_k, const double *param)
+{
+    if (n_tables < 4) return 1;
+    if (rim_tab_check_2d_family(n_tables, n_nodes, gamma, n_mu, mu, log_n, sin_k)) return 1;
+    if (!param) return 0;
+    for (size_t t = 0; t < n_tables; t++)
+        if (!(param[t] - param[t] == 0.)) return 1;         // NaN or infinite
+    const bool up = param[1] > param[0];
+    for (size_t t = 0; t + 1 < n_tables; t++)
+        if (!(up ? param[t + 1] > param[t] : param[t + 1] < param[t])) return 1;
+    return 0;
+}
+
+// That family as one block of doubles; rim_tab_check_2d_family_cubic() has passed.  The set of rim_tab_build_2d_family word for
+// word -- any fixed linear combination of solved tables is the solved combination, so the cubic needs no solve of its own --
+// followed by the n_tables knot words.
+inline void rim_tab_build_2d_family_cubic(size_t n_tables, size_t n_nodes, const double *gamma, size_t n_mu, const double *mu,
+                                          const double *log_n, const double *sin_k, const double *param, std::vector<double> &blob,
+                                          int ends_u = 0, int ends_mu = 0)
+{
+    rim_tab_build_2d_family(n_tables, n_nodes, gamma, n_mu, mu, log_n, sin_k, blob, ends_u, ends_mu);
+    for (size_t t = 0; t < n_tables; t++) blob.push_back(param ? param[t] : (double) t);
+}
+
 #endif

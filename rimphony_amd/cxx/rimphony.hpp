@@ -194,6 +194,26 @@ public:
                                                 sin_k.empty() ? nullptr : sin_k.data(), ends_gamma, ends_mu),
               "rimphony_ctx_set_tables_2d_family");
     }
+    // The same family blended CUBICALLY across its tables (rimphony_ctx_set_tables_2d_family_cubic): at least four tables; param
+    // empty (the knots are the indices) or one finite knot per table, strictly monotonic.  The parameter of a row stays the
+    // real index; every sample blends the node words of four neighbouring tables with the row's Lagrange weights.
+    void set_tables_2d_family_cubic(size_t n_tables, const std::vector<double> &gamma, const std::vector<double> &mu,
+                                    const std::vector<double> &log_n, const std::vector<double> &sin_k = {},
+                                    int ends_gamma = RIMPHONY_TAB_ENDS_NATURAL, int ends_mu = RIMPHONY_TAB_ENDS_NATURAL,
+                                    const std::vector<double> &param = {}) const
+    {
+        if (log_n.size() != n_tables * gamma.size() * mu.size())
+            throw std::runtime_error("set_tables_2d_family_cubic: log_n must hold n_tables * n_nodes * n_mu values");
+        if (!sin_k.empty() && sin_k.size() != n_tables)
+            throw std::runtime_error("set_tables_2d_family_cubic: sin_k must be empty or hold n_tables values");
+        if (!param.empty() && param.size() != n_tables)
+            throw std::runtime_error("set_tables_2d_family_cubic: param must be empty or hold n_tables values");
+        check(rimphony_ctx_set_tables_2d_family_cubic(ctx_, n_tables, gamma.size(), n_tables ? gamma.data() : nullptr, mu.size(),
+                                                      n_tables ? mu.data() : nullptr, n_tables ? log_n.data() : nullptr,
+                                                      sin_k.empty() ? nullptr : sin_k.data(), ends_gamma, ends_mu,
+                                                      param.empty() ? nullptr : param.data()),
+              "rimphony_ctx_set_tables_2d_family_cubic");
+    }
     // Any 2-D form from ln n in device memory (rimphony_ctx_set_tables_2d_device): d_log_n [n_tables][n_nodes][n_mu] on this
     // context's GPU, produced on `stream`.  gamma empty: n_nodes nodes uniform in ln gamma from gamma_lo to gamma_hi, else
     // gamma holds the nodes and the two are not read; mu empty: n_mu nodes uniform in mu, else mu holds them (mu without
@@ -573,7 +593,8 @@ private:
 // A family of tabulated SURFACES with a continuous parameter (include/rimphony_hip.h: rimphony_ctx_set_tables_2d_family): log_n
 // [n_tables][n_nodes][n_mu], mu fastest, on the gamma and mu nodes of set_tables_2d_nodes, table i belonging to param[i]
 // (strictly monotonic; empty: the index itself), sin_k empty or one exponent per table, the ends of the spline per axis.
-// index() and at() as TabulatedFamily has them.
+// index() and at() as TabulatedFamily has them.  cubic: blend four neighbouring tables with a 4-point Lagrange cubic in param
+// instead of two linearly (rimphony_ctx_set_tables_2d_family_cubic; at least four tables).
 class TabulatedFamily2D {
 public:
     class Member : public DistributionFunction {
@@ -599,10 +620,11 @@ public:
     };
     TabulatedFamily2D(std::vector<double> gamma, std::vector<double> mu, size_t n_tables, std::vector<double> log_n,
                       std::vector<double> sin_k = {}, std::vector<double> param = {}, int ends_gamma = RIMPHONY_TAB_ENDS_NATURAL,
-                      int ends_mu = RIMPHONY_TAB_ENDS_NATURAL)
+                      int ends_mu = RIMPHONY_TAB_ENDS_NATURAL, bool cubic = false)
         : gamma_(std::move(gamma)), mu_(std::move(mu)), n_tables_(n_tables), log_n_(std::move(log_n)), sin_k_(std::move(sin_k)),
-          param_(std::move(param)), ends_gamma_(ends_gamma), ends_mu_(ends_mu)
+          param_(std::move(param)), ends_gamma_(ends_gamma), ends_mu_(ends_mu), cubic_(cubic)
     {
+        if (cubic_ && n_tables_ < 4) throw std::runtime_error("TabulatedFamily2D: the cubic blend needs at least 4 tables");
         if (n_tables_ == 0 || log_n_.size() != n_tables_ * gamma_.size() * mu_.size())
             throw std::runtime_error("TabulatedFamily2D: log_n must hold n_tables * n_nodes * n_mu values");
         if (param_.empty()) for (size_t i = 0; i < n_tables_; i++) param_.push_back((double) i);
@@ -611,7 +633,11 @@ public:
             if (!((param_[i] - param_[i - 1]) * (param_[i + 1] - param_[i]) > 0.)) throw std::runtime_error("TabulatedFamily2D: param must be strictly monotonic");
         if (n_tables_ == 2 && !(param_[0] != param_[1])) throw std::runtime_error("TabulatedFamily2D: param must be strictly monotonic");
     }
-    void install(const Context &ctx) const { ctx.set_tables_2d_family(n_tables_, gamma_, mu_, log_n_, sin_k_, ends_gamma_, ends_mu_); }
+    void install(const Context &ctx) const
+    {
+        if (cubic_) ctx.set_tables_2d_family_cubic(n_tables_, gamma_, mu_, log_n_, sin_k_, ends_gamma_, ends_mu_, param_);
+        else ctx.set_tables_2d_family(n_tables_, gamma_, mu_, log_n_, sin_k_, ends_gamma_, ends_mu_);
+    }
     // the real index of a value: piecewise linear in param; throws outside it
     double index(double value) const
     {
@@ -629,6 +655,7 @@ private:
     size_t n_tables_;
     std::vector<double> log_n_, sin_k_, param_;
     int ends_gamma_, ends_mu_;
+    bool cubic_;
 };
 
 // A distribution given as a surface: log_n [n_nodes][n_mu], mu fastest, = ln n(gamma, mu) at nodes uniform in ln gamma and
